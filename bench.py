@@ -2,6 +2,12 @@
 """Benchmark of the multigrid hot path on MI355X (contract: see task README).
 
   python bench.py --gpus N --steps K --warmup W [--workload 128F|256V|64F] [--ordering colour|lex]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the
+benchmark measures (isolated-sweep roofline, residual kernel, the 256^3 V-cycle config, batched and
+concurrent solves, HBM stream rates, time to tolerance, 16^3 parity, the CPU baseline).  `--dump-outputs DIR`
+writes what the last timed step left (rank 0's field and the timed steps' residual norms) as .npy files.
 
 A "step" is ONE multigrid cycle (one level-0 iteration of solver.multigrid:
 pre-smoothing, residual, restriction, coarse-grid recursion, prolongation,
@@ -64,6 +70,7 @@ SWEEP_FLOP_PER_CELL = 1500.0   # minimal band LDL^T line swe
 FP64_PEAK_TFLOPS = 78.6        # MI355X vector FP64
 SC_CYCLE, LR_CYCLE = [1, 2, 3], [4, 5, 6]
 SWEEP_SAMPLES = 10             # isolated-sweep timings: event brackets per direction (min / median / max are reported)
+DUMP_MAX_VALUES = 1 << 20      # --dump-outputs: a larger field is written as a fixed, seeded sample of this many edges
 
 
 def build_problem(em, name, freq):
@@ -522,6 +529,20 @@ def parity_16(em):
     return out
 
 
+def dump_outputs(outdir, efield, norms):
+    """What the timed path hands its caller after the last step: the level-0 electric field (real and imaginary parts,
+    float64; beyond DUMP_MAX_VALUES edges the same seeded sample in every run) and the end-of-cycle residual norms of
+    the timed steps."""
+    os.makedirs(outdir, exist_ok=True)
+    e = np.asarray(efield).ravel()
+    if e.size > DUMP_MAX_VALUES:
+        e = e[np.sort(np.random.default_rng(0).choice(e.size, DUMP_MAX_VALUES, replace=False))]
+    arrays = {"efield_re": e.real, "efield_im": e.imag} if np.iscomplexobj(e) else {"efield": e}
+    arrays["residual_norms"] = np.asarray(norms)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start the N ranks as FRESH child processes (this
     process has not initialised the GPU), relay rank 0's JSON line, fail if any rank fails."""
@@ -581,8 +602,16 @@ def main():
                     help="harness self-test (no GPU): every rank reports its rank environment and exits")
     ap.add_argument("--fail-rank", type=int, default=-1, help="harness self-test: this rank exits with code 3")
     ap.add_argument("--freq-offset", type=int, default=0,
-                    help="rank r solves FREQS[(r + offset) % 8] (tests: the single-rank run of another rank's frequency)")
+                    help="rank r solves FREQS[(r + offset) %% 8] (tests: the single-rank run of another rank's frequency)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline and residual-kernel timings, config_256V, "
+                         "batched and concurrent solves, HBM stream rates, time to tolerance, parity, CPU baseline (the --no-* "
+                         "options and --batch / --multi select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write rank 0's field and residual norms as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus, sys.argv[1:])
@@ -660,6 +689,8 @@ def main():
         norms = dev.cycles(args.steps, SC_CYCLE[rot:] + SC_CYCLE[:rot], LR_CYCLE[rot:] + LR_CYCLE[:rot])
         sync()
         t = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:     # before anything else (the isolated sweeps of --full) touches the field
+            dump_outputs(args.dump_outputs, dev.get_efield(), norms)
         tt = torch.tensor([t], device="cuda", dtype=torch.float64)
         per_rank = [t]
         if use_dist:
@@ -745,7 +776,7 @@ def main():
             mine = shard.efield_tensor(dev)
             assert torch.equal(allf[rank], mine)
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and not args.no_roofline and (args.full or args.mode == "sweep"):
         if args.ordering == "colour":
             if args.mode == "sweep":        # (for rocprofv3: one kind of launch per run)
                 # the set-up of the cycle mode -- without cycles --, so that the isolated sweeps run on the working copies a cycle would
@@ -762,7 +793,8 @@ def main():
                                   "achieved_GBs": RESID_BYTES_PER_CELL * grid.nC / (rms * 1e-3) / 1e9}
     dev.close()
 
-    single = rank == 0 and world == 1 and args.mode == "cycle"
+    # the single-GPU measurements beside the headline: --full only
+    single = args.full and rank == 0 and world == 1 and args.mode == "cycle"
     if single and not args.no_256 and args.workload != "256V":
         # BASELINE.json configs[2]: the 256^3 V-cycle and ITS level-0 sweep, the configuration the north star puts
         # the HBM-roofline target on, measured in the same run

@@ -54,11 +54,11 @@ fi
 # 1. the bench command itself (default workload + the config_256V object + time-to-tolerance solves; without the CPU
 #    baseline leg, which launches no kernels): per-kernel time; the dominant kernels' averages must agree with the
 #    roofline objects of the bench line
-run bench --kernel-trace --stats --output-format csv -d $OUT/${TAG}_bench -- python3 bench.py --no-cpu --no-dense
+run bench --kernel-trace --stats --output-format csv -d $OUT/${TAG}_bench -- python3 bench.py --full --no-cpu --no-dense
 # 1b. only the timed cycles of the default workload (where a 128^3 F-cycle spends its time)
-run cycle128 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_cycle128 -- python3 bench.py --steps 6 --warmup 3 --no-cpu --multi 0 --no-256 --no-tol --batch 0 --no-roofline
+run cycle128 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_cycle128 -- python3 bench.py --full --steps 6 --warmup 3 --no-cpu --multi 0 --no-256 --no-tol --batch 0 --no-roofline
 # 1b'. only cycles of the 256^3 V-cycle (BASELINE configs[2])
-run cycle256 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_cycle256 -- python3 bench.py --workload 256V --steps 3 --warmup 3 --no-cpu --no-tol --batch 0 --no-roofline
+run cycle256 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_cycle256 -- python3 bench.py --full --workload 256V --steps 3 --warmup 3 --no-cpu --no-tol --batch 0 --no-roofline
 # 1c. only batched cycles (8 sources through the same launches)
 run batch8 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_batch8 -- python3 tools/batch_cycle.py 128F 8 6
 if [ "$ONLY" = all ]; then
@@ -78,20 +78,20 @@ run write128d --pmc WRITE_SIZE --output-format csv -d $OUT/${TAG}_write128d -- p
 run fetch256d --pmc FETCH_SIZE --output-format csv -d $OUT/${TAG}_fetch256d -- python3 bench.py --mode sweep --source dense --workload 256V --no-cpu
 run write256d --pmc WRITE_SIZE --output-format csv -d $OUT/${TAG}_write256d -- python3 bench.py --mode sweep --source dense --workload 256V --no-cpu
 # 3b. HBM traffic of EVERY kernel of the 256^3 V-cycle (the x<->y transposes among them: HISTORY R6.4)
-run fetch256c --pmc FETCH_SIZE --output-format csv -d $OUT/${TAG}_fetch256c -- python3 bench.py --workload 256V --steps 3 --warmup 3 --no-cpu --no-tol --batch 0 --no-roofline
-run write256c --pmc WRITE_SIZE --output-format csv -d $OUT/${TAG}_write256c -- python3 bench.py --workload 256V --steps 3 --warmup 3 --no-cpu --no-tol --batch 0 --no-roofline
+run fetch256c --pmc FETCH_SIZE --output-format csv -d $OUT/${TAG}_fetch256c -- python3 bench.py --full --workload 256V --steps 3 --warmup 3 --no-cpu --no-tol --batch 0 --no-roofline
+run write256c --pmc WRITE_SIZE --output-format csv -d $OUT/${TAG}_write256c -- python3 bench.py --full --workload 256V --steps 3 --warmup 3 --no-cpu --no-tol --batch 0 --no-roofline
 run sq128 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM_RD --output-format csv -d $OUT/${TAG}_sq128 -- python3 bench.py --mode sweep --no-cpu
 fi
 # 4. un-profiled bench lines (roofline.traffic is read from profiles/traffic.json of the PREVIOUS summarise.py run)
-python3 bench.py > $OUT/${TAG}_bench_128F.json 2> $OUT/${TAG}_bench_128F.err
-python3 bench.py --no-cpu --no-256 --no-tol --batch 2,4,8,16 --batch-tune > $OUT/${TAG}_bench_128F_batch.json 2> $OUT/${TAG}_bench_128F_batch.err
-python3 bench.py --no-cpu --no-256 --no-tol --batch 0 --multi 3 > $OUT/${TAG}_bench_128F_multi3.json 2> $OUT/${TAG}_bench_128F_multi3.err
-python3 bench.py --workload 256V --steps 3 --warmup 3 --no-cpu --no-tol > $OUT/${TAG}_bench_256V.json 2> $OUT/${TAG}_bench_256V.err
+python3 bench.py --full > $OUT/${TAG}_bench_128F.json 2> $OUT/${TAG}_bench_128F.err
+python3 bench.py --full --no-cpu --no-256 --no-tol --batch 2,4,8,16 --batch-tune > $OUT/${TAG}_bench_128F_batch.json 2> $OUT/${TAG}_bench_128F_batch.err
+python3 bench.py --full --no-cpu --no-256 --no-tol --batch 0 --multi 3 > $OUT/${TAG}_bench_128F_multi3.json 2> $OUT/${TAG}_bench_128F_multi3.err
+python3 bench.py --full --workload 256V --steps 3 --warmup 3 --no-cpu --no-tol > $OUT/${TAG}_bench_256V.json 2> $OUT/${TAG}_bench_256V.err
 # capacity check: 384^3 (a 108 GB handle; not a BASELINE config)
-python3 bench.py --workload 384V --steps 3 --warmup 2 --no-cpu --no-tol --no-256 --multi 0 --batch 0 > $OUT/${TAG}_bench_384V.json 2> $OUT/${TAG}_bench_384V.err
+python3 bench.py --full --workload 384V --steps 3 --warmup 2 --no-cpu --no-tol --no-256 --multi 0 --batch 0 > $OUT/${TAG}_bench_384V.json 2> $OUT/${TAG}_bench_384V.err
 # sizes between the powers of two (launch shapes by rounds of waves, HISTORY R5.19) and fields beyond 4 GiB (k_line_sweep_qc<..., BIG>):
 # 448^3; 512^3, a 257 GB handle on the 288 GB of the device
-timeout 900 python3 bench.py --workload 448V --steps 3 --warmup 2 --no-cpu --no-tol --no-256 --multi 0 --batch 0 > $OUT/${TAG}_bench_448V.json 2> $OUT/${TAG}_bench_448V.err
-timeout 900 python3 bench.py --workload 512V --steps 3 --warmup 2 --no-cpu --no-tol --no-256 --multi 0 --batch 0 > $OUT/${TAG}_bench_512V.json 2> $OUT/${TAG}_bench_512V.err
-python3 bench.py --ordering lex --steps 1 --warmup 1 --no-cpu --no-256 --no-tol --multi 0 > $OUT/${TAG}_bench_128F_lex.json 2> $OUT/${TAG}_bench_128F_lex.err
+timeout 900 python3 bench.py --full --workload 448V --steps 3 --warmup 2 --no-cpu --no-tol --no-256 --multi 0 --batch 0 > $OUT/${TAG}_bench_448V.json 2> $OUT/${TAG}_bench_448V.err
+timeout 900 python3 bench.py --full --workload 512V --steps 3 --warmup 2 --no-cpu --no-tol --no-256 --multi 0 --batch 0 > $OUT/${TAG}_bench_512V.json 2> $OUT/${TAG}_bench_512V.err
+python3 bench.py --full --ordering lex --steps 1 --warmup 1 --no-cpu --no-256 --no-tol --multi 0 > $OUT/${TAG}_bench_128F_lex.json 2> $OUT/${TAG}_bench_128F_lex.err
 tail -c 400 $OUT/${TAG}_bench_128F.json

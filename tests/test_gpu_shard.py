@@ -107,7 +107,7 @@ def test_bench_distributed_path_one_rank(tmp_path):
         s.bind(("127.0.0.1", 0))
         env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(s.getsockname()[1]))
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "32F", "--steps", "2",
-                        "--warmup", "1", "--no-cpu", "--no-256", "--no-tol", "--multi", "0"],
+                        "--warmup", "1", "--full", "--no-cpu", "--no-256", "--no-tol", "--multi", "0"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
@@ -176,7 +176,7 @@ def test_bench_two_ranks_histories_equal_single_rank_runs(tmp_path):
     BLAS / OpenMP pools."""
     import json
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "64F", "--steps", "4", "--warmup", "2",
-            "--no-cpu", "--no-256", "--no-tol", "--batch", "0"]
+            "--full", "--no-cpu", "--no-256", "--no-tol", "--batch", "0"]
     env = dict(os.environ, EMG3D_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "OMP_NUM_THREADS"):
         env.pop(k, None)

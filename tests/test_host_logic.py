@@ -448,6 +448,25 @@ def test_bench_cycle_algorithmic_bytes():
     assert bench.cycle_alg_bytes((32, 32, 32), 'F') > bench.cycle_alg_bytes((32, 32, 32), 'V')
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.dump_outputs (`--dump-outputs DIR`): real and imaginary parts and the residual norms as float64 .npy files; a
+    field beyond DUMP_MAX_VALUES edges is written as a seeded sample, the same edges in every run."""
+    import os
+    import bench
+    rng = np.random.default_rng(3)
+    e = rng.standard_normal(50) + 1j * rng.standard_normal(50)
+    bench.dump_outputs(str(tmp_path / "a"), e, np.array([3.0, 2.0, 1.0]))
+    assert sorted(os.listdir(tmp_path / "a")) == ["efield_im.npy", "efield_re.npy", "residual_norms.npy"]
+    re_, im_ = np.load(tmp_path / "a" / "efield_re.npy"), np.load(tmp_path / "a" / "efield_im.npy")
+    assert re_.dtype == im_.dtype == np.float64 and np.array_equal(re_ + 1j * im_, e)
+    assert np.array_equal(np.load(tmp_path / "a" / "residual_norms.npy"), [3.0, 2.0, 1.0])
+    monkeypatch.setattr(bench, "DUMP_MAX_VALUES", 16)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), e, np.ones(2))
+    b = np.load(tmp_path / "b" / "efield_re.npy")
+    assert b.size == 16 and np.array_equal(b, np.load(tmp_path / "c" / "efield_re.npy")) and np.isin(b, e.real).all()
+
+
 def test_model_gradient_sign_and_chain():
     """optimize.model_gradient = the reference's last two steps of optimize.gradient (optimize.py:201-214, gridding
     'same'): d(misfit)/d(sigma) = -grad; resistivity models get MapResistivity.derivative_chain's factor -1/rho^2."""

@@ -6,7 +6,7 @@ TAG=$1; shift
 for kv in "$@"; do export "$kv"; done
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 D=/tmp/tr_$TAG
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d $D -- python3 bench.py --steps 6 --warmup 3 --no-cpu --multi 0 --no-256 --no-tol --batch 0 > /tmp/tr_$TAG.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d $D -- python3 bench.py --full --steps 6 --warmup 3 --no-cpu --multi 0 --no-256 --no-tol --batch 0 > /tmp/tr_$TAG.log 2>&1
 f=$(find $D -name "*kernel_trace.csv" | head -1)
 python3 - "$f" > gpurun_out/${TAG}_bygrid.txt <<'PY'
 import csv, sys, collections
