@@ -5,6 +5,7 @@
 ``emg3d_amd.fields``, ``models``, ``meshes`` carry only the container types the
 path needs (Field, SourceField, Model, VolumeModel, TensorMesh);
 ``emg3d_amd.maps.interp3d`` / ``fields.get_receiver_response`` are the receiver extraction.
+``emg3d_amd.maps.grid2grid`` / ``Model.interpolate2grid`` regrid models and fields (volume averaging, linear, cubic).
 """
 from emg3d_amd import core, fields, maps, meshes, models, optimize, shard, solver  # noqa
 from emg3d_amd.fields import Field, SourceField, get_h_field, get_receiver_response, get_source_field  # noqa

@@ -9,6 +9,7 @@
 #include "receivers.hpp"
 #include "source.hpp"
 #include "gradient.hpp"
+#include "regrid.hpp"
 
 #define EMG3D_HIP_VERSION EMG3D_HIP_ABI_VERSION      // include/emg3d_hip.h
 
@@ -806,6 +807,38 @@ int emg3d_edges2cellaverages(int dtype, int64_t nx, int64_t ny, int64_t nz, cons
     HIP_TRY(hipDeviceSynchronize());
     for (int c = 0; c < 3; ++c) HIP_TRY(hipMemcpy(outs[c], dout + (size_t)c * n * ts, (size_t)n * ts, hipMemcpyDeviceToHost));
         return 0;
+}
+
+int emg3d_volume_average_weights(const double* x1, int64_t n1, const double* x2, int64_t n2, double* w, int64_t* idx_in,
+                                 int64_t* idx_out, int64_t* ptr, int64_t* nseg) {
+    if (n1 < 2 || n2 < 2 || !x1 || !x2 || !w || !idx_in || !idx_out || !ptr || !nseg) return -2;
+    *nseg = volume_average_weights_host(x1, n1, x2, n2, w, idx_in, idx_out, ptr);
+    return 0;
+}
+
+int emg3d_volume_average(int dtype, int64_t nx, int64_t ny, int64_t nz, const double* edges_x, const double* edges_y,
+                         const double* edges_z, const void* values, int64_t mx, int64_t my, int64_t mz,
+                         const double* new_edges_x, const double* new_edges_y, const double* new_edges_z, void* new_values,
+                         const double* new_vol) {
+    if (nx < 1 || ny < 1 || nz < 1 || mx < 1 || my < 1 || mz < 1 || !edges_x || !edges_y || !edges_z || !values ||
+        !new_edges_x || !new_edges_y || !new_edges_z || !new_values || !new_vol) return -2;
+    const i64 n[3] = {nx, ny, nz}, m[3] = {mx, my, mz};
+    const double* e[3] = {edges_x, edges_y, edges_z};
+    const double* ne[3] = {new_edges_x, new_edges_y, new_edges_z};
+    return dtype ? volume_average_host<c128>(n, e, (const c128*)values, m, ne, (c128*)new_values, new_vol)
+                 : volume_average_host<double>(n, e, (const double*)values, m, ne, (double*)new_values, new_vol);
+}
+
+int emg3d_interp3d_grid(int dtype, int64_t nx, int64_t ny, int64_t nz, const double* px, const double* py, const double* pz,
+                        const void* values, int64_t mx, const double* xi_x, int64_t my, const double* xi_y, int64_t mz,
+                        const double* xi_z, int method, int has_fill, double fill_value, double cval, void* out) {
+    if (nx < 1 || ny < 1 || nz < 1 || mx < 1 || my < 1 || mz < 1 || !px || !py || !pz || !values || !xi_x || !xi_y || !xi_z ||
+        !out || method < 0 || method > 4) return -2;
+    const i64 n[3] = {nx, ny, nz}, m[3] = {mx, my, mz};
+    const double* p[3] = {px, py, pz};
+    const double* xi[3] = {xi_x, xi_y, xi_z};
+    return dtype ? interp3d_grid_host<c128>(n, p, (const c128*)values, m, xi, method, has_fill != 0, fill_value, cval, (c128*)out)
+                 : interp3d_grid_host<double>(n, p, (const double*)values, m, xi, method, has_fill != 0, fill_value, cval, (double*)out);
 }
 
 int emg3d_mg_gradient(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, double* grad) {

@@ -174,24 +174,20 @@ template <class T> __device__ __forceinline__ T fill_of(double v);
 template <> __device__ __forceinline__ double fill_of<double>(double v) { return v; }
 template <> __device__ __forceinline__ c128 fill_of<c128>(double v) { return mk(v, v); }
 
-// out[r] += fac[r] * (cubic B-spline interpolant of `coef` at the fractional indices coords[a][r]); thread per point.
-// fac == nullptr: out[r] = value.
-template <class T>
+// Cubic B-spline interpolant of `coef` at the fractional indices co(0), co(1), co(2) (k_spline_eval, k_spline_eval_grid).
 // edge = 0 (mode='constant'): points outside [0, n-1] get cval, stencil indices beyond the array are mirrored;
 // edge = 1 (mode='nearest', on the pre-padded array) / 2 (mode='mirror', and 'wrap' on coordinates wrapped by the caller) /
 // 3 (mode='reflect'): no point is outside -- the stencil sits at the coordinate and indices beyond the array take the edge
 // coefficient / are mirrored / are reflected (scipy's NI_EXTEND_NEAREST / _MIRROR / _REFLECT).
-__global__ __launch_bounds__(EMG_RCV_BLOCK) void k_spline_eval(T* out, const T* coef, i64 n0, i64 n1, i64 n2, const double* coords, const double* fac,
-                              i64 npts, double cval, int edge) {
-    const i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= npts) return;
+template <class T, class Co>
+__device__ __forceinline__ T spline_point(const T* coef, i64 n0, i64 n1, i64 n2, Co co, double cval, int edge) {
     const i64 nn[3] = {n0, n1, n2};
     i64 idx[3][4];
     double w[3][4];
     bool outside = false;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        double cc = coords[a * npts + r];
+        double cc = co(a);
         if (edge) {
             if (!(cc == cc) || fabs(cc) > 1e15) outside = true;             // NaN (or beyond integer range)
             if (edge == 1) cc = cc < -4.0 ? -4.0 : (cc > (double)(nn[a] + 3) ? (double)(nn[a] + 3) : cc);   // far away: all four indices clamp alike
@@ -230,8 +226,34 @@ __global__ __launch_bounds__(EMG_RCV_BLOCK) void k_spline_eval(T* out, const T* 
                 for (int a2 = 0; a2 < 4; ++a2)
                     val += c[(a0 * 4 + a1) * 4 + a2] * (w[0][a0] * w[1][a1] * w[2][a2]);
     }
+    return val;
+}
+
+// out[r] += fac[r] * (cubic B-spline interpolant of `coef` at the fractional indices coords[a][r]); thread per point.
+// fac == nullptr: out[r] = value.  edge: spline_point.
+template <class T>
+__global__ __launch_bounds__(EMG_RCV_BLOCK) void k_spline_eval(T* out, const T* coef, i64 n0, i64 n1, i64 n2, const double* coords, const double* fac,
+                              i64 npts, double cval, int edge) {
+    const i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= npts) return;
+    const T val = spline_point<T>(coef, n0, n1, n2, [&](int a) { return coords[a * npts + r]; }, cval, edge);
     if (fac) out[r] += fac[r] * val;
     else out[r] = val;
+}
+
+// The 2 x 2 x 2 weighted sum of trilinear interpolation in interval (i0, i1, i2) at normalised distances (t0, t1, t2)
+// (k_linear_eval, k_linear_eval_grid).
+template <class T>
+__device__ __forceinline__ T linear_point(const T* values, i64 s0, i64 s1, i64 s2, i64 i0, i64 i1, i64 i2, double t0, double t1,
+                                          double t2) {
+    T val = Zero<T>::v();
+    for (int a0 = 0; a0 < 2; ++a0)
+        for (int a1 = 0; a1 < 2; ++a1)
+            for (int a2 = 0; a2 < 2; ++a2) {
+                const double w = (a0 ? t0 : 1 - t0) * (a1 ? t1 : 1 - t1) * (a2 ? t2 : 1 - t2);
+                val += values[(i0 + a0) * s0 + (i1 + a1) * s1 + (i2 + a2) * s2] * w;
+            }
+    return val;
 }
 
 // Trilinear interpolation, thread per point: ii / tt = interval index and normalised distance per axis (host:
@@ -247,15 +269,7 @@ __global__ void k_linear_eval(T* out, const T* values, i64 s0, i64 s1, i64 s2, c
         val = Zero<T>::v();
         add_real(val, fill);            // fill_value is a real scalar (complex values: fill + 0j)
     } else {
-        const i64 i0 = ii[r], i1 = ii[npts + r], i2 = ii[2 * npts + r];
-        const double t0 = tt[r], t1 = tt[npts + r], t2 = tt[2 * npts + r];
-        val = Zero<T>::v();
-        for (int a0 = 0; a0 < 2; ++a0)
-            for (int a1 = 0; a1 < 2; ++a1)
-                for (int a2 = 0; a2 < 2; ++a2) {
-                    const double w = (a0 ? t0 : 1 - t0) * (a1 ? t1 : 1 - t1) * (a2 ? t2 : 1 - t2);
-                    val += values[(i0 + a0) * s0 + (i1 + a1) * s1 + (i2 + a2) * s2] * w;
-                }
+        val = linear_point<T>(values, s0, s1, s2, ii[r], ii[npts + r], ii[2 * npts + r], tt[r], tt[npts + r], tt[2 * npts + r]);
     }
     if (fac) out[r] += fac[r] * val;
     else out[r] = val;

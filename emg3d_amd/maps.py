@@ -1,5 +1,9 @@
 """Interpolation used either side of the multigrid path -- the interface of ``emg3d.maps.interp3d``
-(reference emg3d/maps.py:179-276), evaluated on the device through the C ABI (``emg3d_interp3d``)."""
+(reference emg3d/maps.py:179-276), evaluated on the device through the C ABI (``emg3d_interp3d``) -- and regridding,
+``grid2grid`` / ``volume_average`` (reference emg3d/maps.py:34-178, 453-576: ``emg3d_interp3d_grid``,
+``emg3d_volume_average``)."""
+import ctypes
+
 import numpy as np
 
 from . import _lib
@@ -28,6 +32,39 @@ def _wrap_coords(c, n):
     return c
 
 
+def _boundary_mode(pts, values, xi, mode):
+    """Boundary modes of map_coordinates other than 'constant': index coordinates on the host (O(n) work), then the cubic
+    spline of the (edge-padded) array on the device on INDEX coordinates.  ``xi``: one coordinate array per axis.  Returns
+    ``(points, values, index coordinates, method code)`` for ``emg3d_interp3d`` / ``emg3d_interp3d_grid``."""
+    co = _index_coords(pts, xi)
+    if mode == 'nearest':       # edge-padded array, stencil at the shifted coordinate, indices clamped (code 3)
+        values = np.pad(values, _NPAD, mode='edge')
+        co = [c + _NPAD for c in co]
+        code = 3
+    elif mode == 'reflect':     # stencil at the coordinate, indices reflected, "reflect" prefilter (code 4)
+        code = 4
+    else:                       # stencil at the coordinate, indices mirrored (code 2)
+        if mode == 'wrap':      # scipy's NI_EXTEND_WRAP: coordinates wrapped with period n - 1, then the mirror spline
+            co = [_wrap_coords(c, m) for c, m in zip(co, values.shape)]
+        code = 2
+    return [np.arange(m, dtype=np.float64) for m in values.shape], values, co, code
+
+
+def _check_interp_args(method, mode):
+    if mode not in ('constant', 'nearest', 'mirror', 'reflect', 'wrap'):
+        raise ValueError(f"emg3d_amd.maps.interp3d: unknown mode {mode!r} "
+                         "('constant', 'nearest', 'mirror', 'reflect', 'wrap').")
+    if method not in ('linear', 'cubic'):
+        raise ValueError(f"`method` must be 'linear' or 'cubic'; provided: {method!r}.")
+
+
+def _fill_of(fill_value):
+    fill_c = None if fill_value is None else complex(np.asarray(fill_value).ravel()[0])
+    if fill_c is not None and np.isnan(fill_c.real):
+        fill_c = complex(np.nan, fill_c.imag)
+    return fill_c
+
+
 def interp3d(points, values, new_points, method, fill_value, mode, cval=0.0):
     """Interpolate ``values`` given on the regular grid ``points`` at ``new_points`` (reference
     emg3d/maps.py:179-276): ``method`` 'linear' (``RegularGridInterpolator``; ``fill_value=None``
@@ -38,11 +75,7 @@ def interp3d(points, values, new_points, method, fill_value, mode, cval=0.0):
     ``fields.get_receiver(extrapolate=True)`` uses: the array is extended by its edge values), 'mirror', 'reflect' and 'wrap'
     (SciPy's legacy rule: coordinates wrapped with period n - 1, mirror spline) -- the prefilter and the evaluation over the
     whole array run in HBM, the boundary rule is applied to the O(n_points) index coordinates on the host."""
-    if mode not in ('constant', 'nearest', 'mirror', 'reflect', 'wrap'):
-        raise ValueError(f"emg3d_amd.maps.interp3d: unknown mode {mode!r} "
-                         "('constant', 'nearest', 'mirror', 'reflect', 'wrap').")
-    if method not in ('linear', 'cubic'):
-        raise ValueError(f"`method` must be 'linear' or 'cubic'; provided: {method!r}.")
+    _check_interp_args(method, mode)
     lib = _lib.load()
     values = np.asarray(values)
     dtype = np.dtype(np.complex128 if np.iscomplexobj(values) else np.float64)
@@ -54,27 +87,11 @@ def interp3d(points, values, new_points, method, fill_value, mode, cval=0.0):
     n = int(xi[0].size)
     code = 0 if method == 'linear' else 1
     if code == 1 and mode != 'constant' and all(p.size >= 4 for p in pts):
-        # boundary modes of map_coordinates: index coordinates on the host (O(n) work), then the cubic spline of the
-        # (edge-padded) array on the device on INDEX coordinates (method codes 2, 3)
-        co = _index_coords(pts, [c.ravel() for c in xi])
-        if mode == 'nearest':       # edge-padded array, stencil at the shifted coordinate, indices clamped (code 3)
-            values = np.pad(values, _NPAD, mode='edge')
-            co = [c + _NPAD for c in co]
-            code = 3
-        elif mode == 'reflect':     # stencil at the coordinate, indices reflected, "reflect" prefilter (code 4)
-            code = 4
-        else:                       # stencil at the coordinate, indices mirrored (code 2)
-            if mode == 'wrap':      # scipy's NI_EXTEND_WRAP: coordinates wrapped with period n - 1, then the mirror spline
-                co = [_wrap_coords(c, m) for c, m in zip(co, values.shape)]
-            code = 2
-        pts = [np.arange(m, dtype=np.float64) for m in values.shape]
-        xi = co
+        pts, values, xi, code = _boundary_mode(pts, values, [c.ravel() for c in xi], mode)
     vals = np.ascontiguousarray(values.astype(dtype, copy=False).ravel(order='F'))
     flat = np.ascontiguousarray(np.stack([np.asarray(c).ravel() for c in xi]))
     out = np.empty(max(n, 1), dtype=dtype)
-    fill_c = None if fill_value is None else complex(np.asarray(fill_value).ravel()[0])
-    if fill_c is not None and np.isnan(fill_c.real):
-        fill_c = complex(np.nan, fill_c.imag)
+    fill_c = _fill_of(fill_value)
     if n:
         _lib.check(lib.emg3d_interp3d(_lib.dtype_code(dtype), *(int(p.size) for p in pts), *(_lib.ptr(p) for p in pts),
                                       _lib.ptr(vals), n, _lib.ptr(flat), code,
@@ -85,6 +102,131 @@ def interp3d(points, values, new_points, method, fill_value, mode, cval=0.0):
         bad = np.isnan(out.real)
         out[bad] = complex(np.nan, np.nan)
     return out[:n].reshape(shape)
+
+
+def interp3d_grid(points, values, new_axes, method, fill_value, mode, cval=0.0):
+    """``interp3d`` on the tensor product of the coordinate vectors ``new_axes = (x, y, z)``: returns the F-ordered
+    ``(x.size, y.size, z.size)`` array whose entry ``[i, j, k]`` is ``interp3d(points, values, (x[i], y[j], z[k]), ...)``
+    bit for bit, without materialising the points (``emg3d_interp3d_grid``: index coordinates and intervals per axis)."""
+    _check_interp_args(method, mode)
+    lib = _lib.load()
+    values = np.asarray(values)
+    dtype = np.dtype(np.complex128 if np.iscomplexobj(values) else np.float64)
+    pts = [np.ascontiguousarray(p, dtype=np.float64) for p in points]
+    if values.shape != tuple(p.size for p in pts):
+        raise ValueError(f"There are {tuple(p.size for p in pts)} points and {values.shape} values.")
+    xi = [np.ascontiguousarray(np.ravel(c), dtype=np.float64) for c in new_axes]
+    shape = tuple(c.size for c in xi)
+    code = 0 if method == 'linear' else 1
+    if code == 1 and mode != 'constant' and all(p.size >= 4 for p in pts):
+        pts, values, xi, code = _boundary_mode(pts, values, xi, mode)
+        xi = [np.ascontiguousarray(c, dtype=np.float64) for c in xi]
+    vals = np.ascontiguousarray(values.astype(dtype, copy=False).ravel(order='F'))
+    out = np.empty(shape, dtype=dtype, order='F')
+    fill_c = _fill_of(fill_value)
+    if out.size:
+        _lib.check(lib.emg3d_interp3d_grid(_lib.dtype_code(dtype), *(int(p.size) for p in pts), *(_lib.ptr(p) for p in pts),
+                                           _lib.ptr(vals), shape[0], _lib.ptr(xi[0]), shape[1], _lib.ptr(xi[1]), shape[2],
+                                           _lib.ptr(xi[2]), code, 0 if fill_c is None else 1,
+                                           0.0 if fill_c is None else fill_c.real, float(cval), _lib.ptr(out)),
+                   "emg3d_interp3d_grid")
+    if code < 2 and fill_c is not None and dtype.kind == 'c' and np.isnan(fill_c.real) and np.isnan(fill_c.imag):
+        bad = np.isnan(out.real)            # a complex NaN fill value: both parts (as interp3d)
+        out[bad] = complex(np.nan, np.nan)
+    return out
+
+
+def _volume_average_weights(x1, x2):
+    """Weights and indices of volume averaging along one axis (reference emg3d/maps.py:526-576): the old edges ``x1`` and
+    the new edges ``x2`` -> ``(hs, ix1, ix2)``: the length of every segment of the union of the edges that lies in the new
+    grid, the old cell and the new cell holding it (``emg3d_volume_average_weights``, host work, no device)."""
+    w, ix1, ix2, _ = _volume_average_segments(x1, x2)
+    return w, ix1.astype(np.int32), ix2.astype(np.int32)
+
+
+def _volume_average_segments(x1, x2):
+    """``(w, ix1, ix2, ptr)``: ``_volume_average_weights`` plus the per-new-cell segment offsets (new cell ``o`` owns
+    segments ``ptr[o]:ptr[o+1]``)."""
+    lib = _lib.load()
+    x1 = np.ascontiguousarray(x1, dtype=np.float64)
+    x2 = np.ascontiguousarray(x2, dtype=np.float64)
+    cap = max(x1.size + x2.size - 1, 1)
+    w = np.empty(cap)
+    ix1 = np.empty(cap, dtype=np.int64)
+    ix2 = np.empty(cap, dtype=np.int64)
+    ptr = np.empty(max(x2.size, 1), dtype=np.int64)
+    ns = ctypes.c_int64(0)
+    _lib.check(lib.emg3d_volume_average_weights(_lib.ptr(x1), x1.size, _lib.ptr(x2), x2.size, _lib.ptr(w), _lib.ptr(ix1),
+                                                _lib.ptr(ix2), _lib.ptr(ptr), ctypes.byref(ns)),
+               "emg3d_volume_average_weights")
+    n = ns.value
+    return w[:n], ix1[:n], ix2[:n], ptr
+
+
+def volume_average(edges_x, edges_y, edges_z, values, new_edges_x, new_edges_y, new_edges_z, new_values, new_vol):
+    """Volume averaging (reference emg3d/maps.py:453-523): the volume-weighted averages of ``values`` (on the grid of
+    ``edges_*``) over the cells of the new grid are ADDED to ``new_values`` (in place), which is then divided by
+    ``new_vol`` -- on the device (``emg3d_volume_average``: one thread per new cell, the reference's order of
+    operations, bit for bit)."""
+    lib = _lib.load()
+    values = np.asarray(values)
+    dtype = np.dtype(np.complex128 if np.iscomplexobj(values) or np.iscomplexobj(new_values) else np.float64)
+    edges = [np.ascontiguousarray(e, dtype=np.float64) for e in (edges_x, edges_y, edges_z)]
+    new_edges = [np.ascontiguousarray(e, dtype=np.float64) for e in (new_edges_x, new_edges_y, new_edges_z)]
+    n = tuple(e.size - 1 for e in edges)
+    m = tuple(e.size - 1 for e in new_edges)
+    if values.shape != n or np.shape(new_values) != m or np.shape(new_vol) != m:
+        raise ValueError(f"volume_average: values {values.shape} on a {n} grid, new_values {np.shape(new_values)} and "
+                         f"new_vol {np.shape(new_vol)} on a {m} grid.")
+    vals = values.astype(dtype, copy=False).ravel(order='F')            # a view when `values` is F-ordered already
+    vals = np.ascontiguousarray(vals)
+    out = np.ascontiguousarray(np.asarray(new_values, dtype=dtype).ravel(order='F'))
+    vol = np.ascontiguousarray(np.asarray(new_vol, dtype=np.float64).ravel(order='F'))
+    _lib.check(lib.emg3d_volume_average(_lib.dtype_code(dtype), *n, *(_lib.ptr(e) for e in edges), _lib.ptr(vals), *m,
+                                        *(_lib.ptr(e) for e in new_edges), _lib.ptr(out), _lib.ptr(vol)),
+               "emg3d_volume_average")
+    new_values[...] = out.reshape(m, order='F')
+
+
+def grid2grid(grid, values, new_grid, method='linear', extrapolate=True, log=False):
+    """Interpolate ``values`` located on ``grid`` to ``new_grid`` (reference emg3d/maps.py:34-178).
+
+    ``values``: model parameters on the cells, one field component (edges: cell centres and nodes per axis, chosen by the
+    array's shape), or a :class:`emg3d_amd.fields.Field` (regridded per component; returns ``values.__class__(fx, fy,
+    fz)``).  ``method``: 'linear', 'cubic' (fewer than four points along an axis: 'linear') or 'volume' (volume averaging,
+    cells only).  ``extrapolate``: points outside ``grid`` take the nearest value ('cubic') or are extrapolated ('linear');
+    ``False``: they are 0 ('volume' always takes the nearest cell).  ``log``: the same on ``log10(values)``, then ``10**``
+    (both on the host).
+
+    'volume' runs ``emg3d_volume_average``, 'linear' / 'cubic' run ``emg3d_interp3d_grid`` on the tensor product of the
+    new grid's vectors: the reference's results bit for bit ('volume') or with its SciPy arithmetic ('linear', 'cubic')."""
+    if hasattr(values, 'field') and np.ndim(values.field) == 1:
+        fx, fy, fz = (grid2grid(grid, np.asarray(c), new_grid, method, extrapolate, log)
+                      for c in (values.fx, values.fy, values.fz))
+        return values.__class__(fx, fy, fz)
+    values = np.asarray(values)
+    if tuple(grid.vnC) != values.shape and method == 'volume':
+        raise ValueError("``method='volume'`` not implemented for fields.")
+    if method not in ('linear', 'cubic', 'volume'):
+        raise ValueError(f"`method` must be 'linear', 'cubic' or 'volume'; provided: {method!r}.")
+    if log:
+        values = np.log10(values)
+    if method == 'volume':
+        new_values = np.zeros(new_grid.vnC, dtype=values.dtype, order='F')
+        vol = new_grid.cell_volumes.reshape(new_grid.vnC, order='F')
+        volume_average(grid.nodes_x, grid.nodes_y, grid.nodes_z, values, new_grid.nodes_x, new_grid.nodes_y,
+                       new_grid.nodes_z, new_values, vol)
+    else:
+        points, new_points = [], []
+        for i, c in enumerate('xyz'):
+            kind = 'nodes_' if values.shape[i] == grid.shape_nodes[i] else 'cell_centers_'
+            points.append(getattr(grid, kind + c))
+            new_points.append(getattr(new_grid, kind + c))
+        if extrapolate:
+            new_values = interp3d_grid(points, values, new_points, method, None, 'nearest')
+        else:
+            new_values = interp3d_grid(points, values, new_points, method, 0.0, 'constant')
+    return 10**new_values if log else new_values
 
 
 def edges2cellaverages(ex, ey, ez, vol, out_x, out_y, out_z):

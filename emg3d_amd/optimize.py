@@ -7,12 +7,13 @@ containers (xarray; out of scope).  Everything field-sized stays in HBM on ONE h
     misfit (host scalars) -> residual source (receivers as sources, built on the device) -> back-propagation solve
     -> gradient kernel (-Re(lambda E s mu_0), edges -> cells) -> nC doubles come back.
 
-The loop over (source, frequency) pairs and the mapping of the gradient to the model grid (``maps.grid2grid``)
-belong to the caller, as in the reference.
+The loop over (source, frequency) pairs belongs to the caller, as in the reference; ``model_gradient(...,
+model_grid=)`` maps the gradient to the model grid as the reference does (``maps.grid2grid(grid, -grad, model_grid,
+'cubic')``, optimize.py:201-211) and applies the chain rule there.
 """
 import numpy as np
 
-from . import fields, models, solver
+from . import fields, maps, models, solver
 
 
 def misfit(synthetic, observed, weights):
@@ -84,16 +85,24 @@ def gradient(grid, model, src, freq, rec, observed, weights=None, strength=0, de
     return phi, grad, dict(synthetic=synthetic, forward=finfo, backward=binfo)
 
 
-def model_gradient(grid, model, grad):
-    """d(misfit) / d(model property) on the computational grid from ``gradient()``'s ``grad``: the reference's last two
-    steps without the regridding (optimize.py:201-214 with ``gridding='same'``): the sign, then the chain rule of the
-    model's property map -- conductivity: identity; resistivity rho: d sigma / d rho = -1 / rho^2
-    (``maps.MapResistivity.derivative_chain``, emg3d/maps.py)."""
+def model_gradient(grid, model, grad, model_grid=None):
+    """d(misfit) / d(model property) from ``gradient()``'s ``grad`` (on the computational grid ``grid``): the reference's
+    last steps (optimize.py:201-214): the sign, the mapping to the model grid, then the chain rule of the model's property
+    map -- conductivity: identity; resistivity rho: d sigma / d rho = -1 / rho^2 (``maps.MapResistivity.derivative_chain``,
+    emg3d/maps.py).
+
+    ``model_grid=None``: ``model`` lives on ``grid`` (the reference's ``gridding='same'``), nothing is regridded.
+    Otherwise ``model`` lives on ``model_grid``: ``-grad`` is mapped there with ``maps.grid2grid(grid, -grad, model_grid,
+    method='cubic')`` and the chain rule takes the property on ``model_grid``."""
     out = -np.asarray(grad)
+    vnC = grid.vnC
+    if model_grid is not None:
+        out = maps.grid2grid(grid, out, model_grid, method='cubic')
+        vnC = model_grid.vnC
     mapping = getattr(model, 'mapping', 'Resistivity')
     if mapping == 'Conductivity':
         return out
     if mapping == 'Resistivity':
-        rho = np.asarray(model.property_x).reshape(grid.vnC, order='F')
+        rho = np.asarray(model.property_x).reshape(vnC, order='F')
         return out * (-1.0 / rho ** 2)
     raise NotImplementedError(f"model_gradient: property map {mapping!r} (apply its derivative_chain to -grad).")

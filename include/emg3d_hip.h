@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 103
+#define EMG3D_HIP_ABI_VERSION 104
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -227,9 +227,33 @@ int emg3d_edges2cellaverages(int dtype, int64_t nx, int64_t ny, int64_t nz, cons
  * emg3d/optimize.py:176-199: grad = sum_c edges2cellaverages_c(-Re(bfield * efield * smu0)) with the cell volumes
  * of the handle's grid.  bfield = the handle's level-0 field (the back-propagated solution, simulations.py:1131-1143),
  * efield = workspace vector `efield_vec` (the forward solution, saved with emg3d_mg_vec_copy(id, -2)).  grad: nC
- * doubles, F-ordered.  (The reference then maps -grad to the model grid, maps.grid2grid: gridding, out of scope.)
+ * doubles, F-ordered.  (The reference then maps -grad to the model grid: emg3d_interp3d_grid, optimize.model_gradient.)
  * Overwrites the residual buffer.                                                                                */
 int emg3d_mg_gradient(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, double* grad);
+
+/* ---- regridding ---------------------------------------------------------------------------------------------------
+ * maps._volume_average_weights(x1, x2), reference emg3d/maps.py:526-576, for one axis: x1 (n1 >= 2 edges, old grid) and
+ * x2 (n2 >= 2 edges, new grid), ascending.  Every interval of the sorted union of the edges whose centre lies in
+ * [x2[0], x2[n2-1]] is a segment: w = its length, idx_in = the x1 cell holding the centre (clipped to the first / last
+ * cell), idx_out = the x2 cell holding it; *nseg segments (at most n1 + n2 - 1: the capacity of w / idx_in / idx_out),
+ * sorted by idx_out.  ptr (n2 entries): new cell o owns segments [ptr[o], ptr[o+1]).  O(n) host work, no device.      */
+int emg3d_volume_average_weights(const double* x1, int64_t n1, const double* x2, int64_t n2, double* w, int64_t* idx_in,
+                                 int64_t* idx_out, int64_t* ptr, int64_t* nseg);
+/* maps.volume_average(edges_x, edges_y, edges_z, values, new_edges_x, new_edges_y, new_edges_z, new_values, new_vol),
+ * reference emg3d/maps.py:453-523, on the device: values F-ordered (nx,ny,nz) of dtype on the grid of the edges (nx+1,
+ * ny+1, nz+1 of them), new_values F-ordered (mx,my,mz) of dtype: the volume-weighted sums are ADDED into it, then it is
+ * divided by new_vol (F-ordered (mx,my,mz) doubles), in the reference's order of operations (bit for bit).             */
+int emg3d_volume_average(int dtype, int64_t nx, int64_t ny, int64_t nz, const double* edges_x, const double* edges_y,
+                         const double* edges_z, const void* values, int64_t mx, int64_t my, int64_t mz,
+                         const double* new_edges_x, const double* new_edges_y, const double* new_edges_z, void* new_values,
+                         const double* new_vol);
+/* emg3d_interp3d on the tensor product of three coordinate vectors xi_x (mx), xi_y (my), xi_z (mz): out is F-ordered
+ * (mx,my,mz), out[i + mx (j + my k)] = emg3d_interp3d at (xi_x[i], xi_y[j], xi_z[k]) bit for bit; method / has_fill /
+ * fill_value / cval as there (maps.grid2grid, reference emg3d/maps.py:34-178, uses 0, 1 and 3).  The per-axis work is
+ * O(mx + my + mz) on the host.                                                                                        */
+int emg3d_interp3d_grid(int dtype, int64_t nx, int64_t ny, int64_t nz, const double* px, const double* py, const double* pz,
+                        const void* values, int64_t mx, const double* xi_x, int64_t my, const double* xi_y, int64_t mz,
+                        const double* xi_z, int method, int has_fill, double fill_value, double cval, void* out);
 
 /* ---- batched systems: several sources through the same launches ------------------------------------------
  * The reference solves one (source, frequency) system per solver.solve call; a survey has many sources per
