@@ -525,21 +525,17 @@ static void* efield_ptr(MG<T>* m) {
     return m->err ? nullptr : (void*)p;
 }
 
+// emg3d_sweep_plan: the selection function of sweep_plan.hpp on a bare shape (cu_count > 0: a device of that size with the MI355X's
+// 160 KB of LDS per workgroup, whatever this machine has; else the current device)
 template <class T>
 static int sweep_plan_impl(i64 nx, i64 ny, i64 nz, int dir, int order, int nsys, int cu_count, char* name, int64_t* info) {
-    MG<T> m;
-    if (cu_count > 0) {                     // a device of that size, whatever this machine has
-        m.cu_count = cu_count;
-        m.tha_lds_state = 1; m.tha_lds_limit = 160 * 1024;
-    } else m.device = current_device();
-    m.order = order; m.nsys = nsys;
-    m.lv0 = std::make_shared<Level<T>>();
-    Level<T>& L = *m.lv0;
-    L.nC[0] = nx; L.nC[1] = ny; L.nC[2] = nz;
-    MG<T>::shape_level(L);
-    i64 inf[6];
-    m.plan_sweep(L, dir - 1, name, inf);
-    for (int k = 0; k < 6; ++k) info[k] = inf[k];
+    SweepKnobs K;
+    if (cu_count > 0) K.simds = 4 * (i64)cu_count;
+    else sweep_device_knobs<T>(K, current_device());
+    K.order = order; K.nsys = nsys;
+    const SweepPlan p = plan_sweep(K, SweepShape{{nx, ny, nz}, (int)sizeof(T)}, dir - 1);
+    memcpy(name, p.name, sizeof p.name);
+    info[0] = p.nmax; info[1] = p.lpw; info[2] = p.rounds; info[3] = p.fac_kind; info[4] = p.split ? 1 : 0; info[5] = p.big ? 1 : 0;
     return 0;
 }
 

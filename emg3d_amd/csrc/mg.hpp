@@ -26,6 +26,7 @@
 #include "smooth_thm.hpp"
 #include "smooth_tha.hpp"
 #include "sweep_launch.hpp"     // the four sweep families are compiled in units of their own; this file launches through these
+#include "sweep_plan.hpp"       // ... and which of them serves a (level, direction) is decided there, on the host
 
 template <class T>
 struct Level {
@@ -70,6 +71,9 @@ struct Level {
     int fac_kind[3] = {0, 0, 0};  // 0: one-sided, 15 numbers per block (k_line_sweep_rp / _qpl, k_line_sweep); 3: mirrored
                                   // two-sided (k_line_factor_m, for k_line_sweep_thm); 4: one-sided compact (11 numbers per
                                   // block, k_line_sweep_qc)
+    // the launch selection of each direction (MG::plan), computed for plan_key = order + 2 * systems (-1: not yet)
+    SweepPlan plan[3];
+    int plan_key[3] = {-1, -1, -1};
 };
 
 // Transfer operators between a level and the next coarser one of a hierarchy.
@@ -236,6 +240,20 @@ struct emg3d_mg {
 // returning the error.  A broken handle launches nothing; every entry point answers hipErrorOutOfMemory until it is destroyed.
 #define MG_LAUNCH(...) do { if (!broken) hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 
+// The device's part of the selection knobs (sweep_plan.hpp): its SIMDs, its LDS per workgroup, and whether k_line_sweep_tha gets the
+// dynamic LDS it needs -- more than 64 KB must be asked for per instantiation and device, once (tha_attrs, on the current device).
+static_assert(SWEEP_THA_LPW == THA_LPW && SWEEP_THA_RING == tha_ring_depth<3>() && SWEEP_THA_RING == tha_ring_depth<2>() &&
+              SWEEP_THA_MAX_DYN_LDS == THA_MAX_DYN_LDS && SWEEP_THA_STATIC_LDS == THA_STATIC_LDS, "sweep_plan.hpp restates smooth_tha.hpp");
+template <class T>
+inline void sweep_device_knobs(SweepKnobs& K, int device) {
+    int cus = 0, lds = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
+    if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) { (void)hipGetLastError(); lds = 0; }
+    K.simds = 4 * (i64)cus;
+    K.lds_limit = lds;
+    K.tha_lds_granted = lds >= THA_MAX_DYN_LDS + THA_STATIC_LDS && tha_attrs<T>(THA_MAX_DYN_LDS);
+}
+
 template <class T>
 struct MG : emg3d_mg {
     int device = 0;
@@ -257,36 +275,21 @@ struct MG : emg3d_mg {
     static const int NORM_SLOTS = 4096;
     int err = 0;
     bool broken = false;        // a device allocation failed: arrays are missing, nothing is launched any more (MG_LAUNCH)
-    // ---- kernel selection -----------------------------------------------------------------------------------------
-    // The product library runs the measured defaults (why each is what it is: DESIGN.md 3; the A/B numbers behind them:
-    // profiles/HISTORY.md) and reads six documented variables: EMG3D_POOL_GB, EMG3D_GRAPH, EMG3D_LOG, EMG3D_LOG_SETUP,
-    // EMG3D_BATCH_TUNE, EMG3D_PLACE_TRIES.  The lab build (-DEMG3D_LAB: libemg3d_hip_lab.so, used by tests/test_gpu_variants.py and
-    // tools/) also compiles the superseded kernels and reads one variable per knob below (LAB_ENV, common.hpp).
-    int sweep_kernel = LAB_ENV_CH("EMG3D_SWEEP") == 't' ? 1 : 0;       // 1: thread-per-line kernel everywhere
-    bool use_xt = LAB_ENV("EMG3D_XT", 1) != 0;                          // x-lines on x<->y transposed working copies ...
-    i64 xt_min_cells = LAB_ENV("EMG3D_XT_MIN", 8192);                   // ... on levels of at least this many cells
-    int th_lpw = (int)LAB_ENV("EMG3D_TH_LPW", 0);                       // lines per pair of waves 4|8|12 (0: by launch size)
-    // 8 lines per pair of waves, or 12 (60 instead of 40 useful lanes per load instruction: a wave 15 % longer) where that saves a
-    // ROUND of waves: the kernel keeps a SIMD's issue slots 43-80 % busy, so W waves on S SIMDs last ceil(W / S) rounds whatever the
-    // registers would allow (HISTORY R5.19: 136^3 -- 4624 lines = 1156 waves at 8 lines per pair -- 0.166 ms against 0.092 at 128^3;
-    // with 12 lines per pair 772 waves, 0.121 ms).  Single systems of 4097 ... 6144 lines per colour and batched launches (several waves
-    // per SIMD either way: 16 128 lines 4 -> 3 rounds) take 12.  The lane mapping does not touch a line's arithmetic.
-    int th_lines_per_pair(const LineArgs<T>& a) const {
-        if (th_lpw == 4 || th_lpw == 8 || th_lpw == 12) return th_lpw;
-        const i64 lines = a.nA[0] * a.nB2[0] * (i64)nsys, simds = (i64)simd_count();
-        const i64 r8 = (2 * ((lines + 7) / 8) + simds - 1) / simds, r12 = (2 * ((lines + 11) / 12) + simds - 1) / simds;
-        return (23 * r12 < 20 * r8) ? 12 : 8;
-    }
-    mutable int cu_count = 0;
-    int simd_count() const {
-        if (cu_count == 0) {
-            int v = 0;
-            if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || v <= 0) { (void)hipGetLastError(); v = 256; }
-            cu_count = v;
+    // ---- kernel selection: sweep_plan.hpp ------------------------------------------------------------------------------------
+    // The product library reads six documented variables: EMG3D_POOL_GB, EMG3D_GRAPH, EMG3D_LOG, EMG3D_LOG_SETUP, EMG3D_BATCH_TUNE,
+    // EMG3D_PLACE_TRIES; the lab build (-DEMG3D_LAB) one per knob (LAB_ENV, common.hpp).  The selection's knobs and the device's size
+    // are filled once per handle; the plan of a (level, direction) is kept on the Level.
+    SweepKnobs knobs;
+    bool knobs_device = false;          // the device's part of `knobs` has been asked for
+    const SweepPlan& plan(Level<T>& L, int dir) {
+        if (!knobs_device) { sweep_device_knobs<T>(knobs, device); knobs_device = true; }
+        if (L.plan_key[dir] != order + 2 * nsys) {
+            knobs.order = order; knobs.nsys = nsys;
+            L.plan[dir] = plan_sweep(knobs, SweepShape{{L.nC[0], L.nC[1], L.nC[2]}, (int)sizeof(T)}, dir);
+            L.plan_key[dir] = order + 2 * nsys;
         }
-        return cu_count * 4;
+        return L.plan[dir];
     }
-    int force_lpw = (int)LAB_ENV("EMG3D_LPW", 0);                       // k_line_sweep_rp: lines per wave 4|8|12 (0: by size)
     bool use_graph = !(getenv("EMG3D_GRAPH") && getenv("EMG3D_GRAPH")[0] == '0');    // replay captured cycles (0: eager launches)
     // verb = 5 of the reference (solver.py:502-578): the residual norm after every smoothing call of every level.  With
     // `trace` on the cycles run eagerly; each smoothing call is followed by a norm-only residual into trace_norms and a
@@ -302,19 +305,6 @@ struct MG : emg3d_mg {
     std::map<int, std::pair<int, int>> graph_home;      // per captured cycle: Level::e_home of level 0 on entry / on exit
     std::map<int, int> graph_seen;
     bool dry = false;           // dry run: allocate/prepare only, launch nothing
-    bool use_twist = LAB_ENV("EMG3D_TWIST", 1) != 0;                    // two-sided factorisation below twist_max_lines
-    i64 twist_max_lines_env = LAB_ENV("EMG3D_TWIST_MAX", 0);            // 0: q_min_lines()
-    i64 twist_max_lines() const { return twist_max_lines_env > 0 ? twist_max_lines_env : q_min_lines(); }
-    // ---- launch-shape thresholds in units of the DEVICE (256 CUs = 1024 SIMDs on MI355X; the literals of rounds 2-5 in brackets) ----
-    // A colour launch of the chain kernels is made of waves that all last the same time: W waves on S SIMDs take ceil(W / S) rounds
-    // (HISTORY R5.19), so every "how many lines" threshold is a number of waves per SIMD:
-    //   q_min_lines      8 S  [8192]  lines per colour from which the quad kernel serves: one wave per SIMD at 8 lines per wave
-    //   qpl_few_lines      S  [1024]  up to here the scan kernel serves lines of any length: one single-line wave per SIMD
-    //   tha_min_lines  1.07 S [1100]  measured crossover of the affine kernel against the scan kernel on 33..64-block lines
-    //   tha_big_lines   8 CUs [2048]  65..128-block lines in the affine kernel: one workgroup of 8 lines per CU, ONE round
-    //   qdesc_max      8.8 S  [9000]  threads of a colour launch up to which the descriptor table is cheaper than the arithmetic
-    i64 simds() const { return (i64)simd_count(); }
-    int tw_stages = (int)LAB_ENV("EMG3D_TW_STAGES", 0);                 // register prefetch depth of the two-sided kernels (0: 3)
     bool log_launches = getenv("EMG3D_LOG") != nullptr;                 // one line per sweep launch on stderr
     int xcd_map = (int)LAB_ENV("EMG3D_XCD", 1);                         // XCD-aware workgroup -> line map
     // k_residual: block map and node planes per thread (stencil.hpp; every setting gives identical results): levels of
@@ -355,45 +345,8 @@ struct MG : emg3d_mg {
         if (e && strlen(e) == 8) for (int k = 0; k < 8; ++k) point_perm_b[k] = (e[k] - '0') & 7;
     }
 #endif
-    // sweeps on parity-split working copies (the lines of one colour contiguous in memory): 0 never, 1 every level and
-    // ordering, 2 (default) colour-ordered levels of >= split_min_cells
-    int use_split = (int)LAB_ENV("EMG3D_SPLIT", 2);
-    i64 split_min_cells = LAB_ENV("EMG3D_SPLIT_MIN_CELLS", 2000000);
-    // quad-per-line chain kernel (smooth_qc.hpp): 1 (default) on launches of >= q_min_lines lines per colour (bandwidth
-    // bound: 256^3 level 0), 2 wherever a lane-group kernel would serve, 0 never
-    int use_q = (int)LAB_ENV("EMG3D_Q", 1);
-    i64 q_min_lines_env = LAB_ENV("EMG3D_Q_MIN_LINES", 0);              // 0: 8 lines per wave on every SIMD
-    i64 q_min_lines() const { return q_min_lines_env > 0 ? q_min_lines_env : 8 * simds(); }
-    // register prefetch depth of k_line_sweep_qc: 0 = by the launch -- 2 stages at 16 lines per wave and at most one wave per SIMD (210 registers; the 3-stage
-    // instantiation there is 322 registers with 84 / 310 AGPR writes / reads in its loop bodies, i.e. prefetched values that are
-    // waited for when they are parked), 3 stages below (level 1 of a 256^3 cycle: 8 lines per wave); lab: 2 | 3 force one.
-    // 256^3, same box, alternating (profiles/r05_qstages_ab.txt): launch 731 -> 713 us dense, 650 -> 637 dipole, V-cycle 30.88 -> 30.57 ms;
-    // 2 stages everywhere: the launch the same, the cycle +0.15 ms (level 1).
-    int q_stages = (int)LAB_ENV("EMG3D_Q_STAGES", 0);
-    // (384^3, 36.9 k lines per colour = 2.2 waves per SIMD: 3 stages again, 119.7 / 121.3 against 123.0 / 122.3 ms per V-cycle,
-    // profiles/r05_qstages_ab.txt: the two-stage instantiation pays where a launch is ONE wave per SIMD)
-    int q_stages_for(int lpw, i64 nmax) const {
-        return q_stages == 2 || q_stages == 3 ? q_stages : ((lpw == 16 && nmax * nsys > 15 * simds() && nmax * nsys <= 16 * simds()) ? 2 : 3);
-    }
     int use_zsep = (int)LAB_ENV("EMG3D_ZSEP", 1);                       // lab: 0 = always read zeta
     int q_tile = (int)LAB_ENV("EMG3D_Q_TILE", 0);                       // lab: switches of in-kernel instrumentation (LineArgs::tile; 256: timestamps of k_line_sweep_tha)
-    int q_lpw = (int)LAB_ENV("EMG3D_Q_LPW", 0);                         // lines per wave 16|8|4|2 (0: by launch size)
-    // quad-per-block scan kernel (smooth_qpl.hpp): direction mask; lines of qpl_min_nl .. qpl_max_nl blocks (any length
-    // <= 256 when a colour has <= qpl_few_lines lines, and in lexicographic order); two blocks per quad from qpl_m2_min on
-    int use_qpl = (int)LAB_ENV("EMG3D_QPL", 7);
-    i64 qpl_min_nl = LAB_ENV("EMG3D_QPL_MIN", 2);
-    i64 qpl_max_nl = LAB_ENV("EMG3D_QPL_MAX_NL", 64);
-    // (32 since round 4: with the launch prologues trimmed, the 32-block levels of a 128^3 F-cycle -- ~1000 lines per colour -- do
-    // better with one wave per SIMD and two blocks per quad than with two waves per SIMD: cycle 8.75 / 8.72 -> 8.63 / 8.65 ms;
-    // from 16 blocks on: 8.78 / 8.76; profiles/r04_qpl_m2_ab.txt)
-    i64 qpl_m2_min = LAB_ENV("EMG3D_QPL_M2", 32);
-    // chain form of the scan kernel (smooth_qpl.hpp CH) on lines of at most this many quads (0: never).  4-block lines: the 168 such
-    // launches of a 128^3 F-cycle 5.27 -> 4.86 us (three DPP-fed steps against two Kogge-Stone steps through LDS); 8-block lines
-    // (seven steps, lane shuffles across the row boundary) 5.78 -> 6.16 us: 4 (HISTORY R6.3, profiles/r06_qpl_chain_ab.txt)
-    int qpl_chain_seg = (int)LAB_ENV("EMG3D_QPL_CHAIN", 4);
-    i64 qpl_few_lines_env = LAB_ENV("EMG3D_QPL_FEW", 0);                // 0: one single-line wave per SIMD
-    i64 qpl_few_lines() const { return qpl_few_lines_env > 0 ? qpl_few_lines_env : simds(); }
-    i64 qpl_max_lines = LAB_ENV("EMG3D_QPL_MAX", (i64)1 << 40);
 
 #ifdef EMG3D_LAB
     MG() { read_colour_perm(); }
@@ -402,7 +355,6 @@ struct MG : emg3d_mg {
 #endif
 
     ~MG() override {
-        if (!stream && !side && allocs.empty() && !stage) return;       // (a shape-only object, emg3d_sweep_plan: no HIP call)
         hipSetDevice(device);
         if (stream) hipStreamSynchronize(stream);
         if (side) hipStreamSynchronize(side);
@@ -975,42 +927,7 @@ struct MG : emg3d_mg {
         else transpose_xy(L.zetaW[w], (const double*)L.zeta, L.nC[0], L.nC[1], L.nC[2], true, 1);
         L.sW_valid[w] = false;
     }
-    // does the row-parallel kernel (32-bit offsets) apply to this level?
-    // The lane-group kernels address with a uniform base and 32-bit per-lane byte offsets: (i) the field arrays, (ii) a plane of
-    // the factor, (iii) zeta must each stay below 4 GiB.  wide_fits: (ii) and (iii) only.
-    bool wide_fits(const Level<T>& L) const {
-        const i64 lim = (i64)1 << 32;
-        i64 mx = 0;
-        for (int d = 0; d < 3; ++d) {
-            const int P = (d == 0) ? 1 : 0, Q = (d == 2) ? 1 : 2;
-            mx = std::max(mx, (L.nC[P] - 1) * (L.nC[Q] - 1));
-        }
-        return sweep_kernel == 0 && mx * 15 * (i64)sizeof(T) < lim && L.nCells * 8 < lim;
-    }
-    bool rp_fits(const Level<T>& L) const {
-        return wide_fits(L) && L.nE * (i64)sizeof(T) < ((i64)1 << 32) && !q_big_force(L);
-    }
-    // Fields of 4 GiB and more (complex: from ~445^3 cells on; 512^3 = 6.4 GB per field): the quad-per-line kernel with 64-bit
-    // field offsets (k_line_sweep_qc<..., BIG>) serves, on the split working copies like every other large level, where all
-    // three line directions have the lines for it (>= q_min_lines() per colour, i.e. 8 per wave on every SIMD: the 16-line instantiation
-    // at the balanced number of lines per wave); everything else of the cycle
-    // (residual, transfers, conversions) is 64-bit throughout.  Other shapes keep the thread-per-line kernel.
-    // EMG3D_Q_BIG=1 (lab): the 64-bit variant on levels that would fit 32 bits (parity tests at small sizes).
-    int q_big_lab = (int)LAB_ENV("EMG3D_Q_BIG", 0);
-    bool q_big_lines(const Level<T>& L) const {
-        for (int d = 0; d < 3; ++d) {
-            const int P = (d == 0) ? 1 : 0, Q = (d == 2) ? 1 : 2;
-            if ((L.nC[P] / 2) * (L.nC[Q] / 2) < std::max<i64>(q_min_lines(), 1)) return false;
-        }
-        return order == 1 && use_q >= 1;
-    }
-    bool q_big_force(const Level<T>& L) const { return q_big_lab && q_big_lines(L) && wide_fits(L); }
-    bool q_big(const Level<T>& L) const {
-        return wide_fits(L) && q_big_lines(L) && (q_big_lab || L.nE * (i64)sizeof(T) >= ((i64)1 << 32));
-    }
-    bool split_on(const Level<T>& L) const {
-        return (use_split == 1 || (use_split == 2 && order == 1 && L.nCells >= split_min_cells)) && (rp_fits(L) || q_big(L));
-    }
+    bool split_on(Level<T>& L) { return plan(L, 0).split; }     // (a property of the level: the same for every direction)
     // Level 0 with split working copies: the field STAYS in the x-split copy eW[1] between the sweeps -- the residual and
     // the prolongation address it there (ResidualArgs::xs, ProlongArgs::fxs), the x-line sweeps convert eW[1] <-> eW[0]
     // -- and returns to the reference layout only when something outside the cycle asks for it (sel_e).  Saves the
@@ -1018,8 +935,8 @@ struct MG : emg3d_mg {
     // The coarse levels with split copies never see the reference layout at all: restriction and prolongation address
     // eW[1] / sW[1] directly (RestrictArgs::cxs, ProlongArgs::cxs).
     int use_home = (int)LAB_ENV("EMG3D_HOME", 1);
-    bool home_on(const Level<T>& L) const { return use_home && &L == lv0.get() && split_on(L); }
-    bool home_lvl(const Level<T>& L) const { return use_home && &L != lv0.get() && split_on(L); }
+    bool home_on(Level<T>& L) { return use_home && &L == lv0.get() && split_on(L); }
+    bool home_lvl(Level<T>& L) { return use_home && &L != lv0.get() && split_on(L); }
     void e_to_ref(Level<T>& L) {
         if (L.e_home != 1) return;
         convert_field(L, L.e, L.eW[1], 1, false, true);
@@ -1032,112 +949,18 @@ struct MG : emg3d_mg {
         L.e_home = 1;
     }
 
-    // dir 0 (x-lines) runs on the transposed copies when `use_xt`.
-    // Small levels: the 6-9 transposition launches cost more than strided access.
-    bool xt(const Level<T>& L, int dir) const {
-        return dir == 0 && use_xt && L.nCells >= xt_min_cells && !qpl(L, dir);
-    }
-    // Which sweep kernel serves (level, direction) -- decided when the factor is built, because the
-    // kernels differ in the factor layout:
-    //   k_line_sweep_qpl (scan along the line, smooth_qpl.hpp)  wherever the dependent chain of the lane-group
-    //       kernels would leave SIMDs idle: lines of <= qpl_max_nl (64) blocks; lines of any length <= 256
-    //       blocks when a colour has <= qpl_few_lines (1024) lines; every launch of the lexicographic order
-    //       (a hyperplane holds at most min(nP, nQ)/2 lines: 128-block lines 20 instead of 96 us per launch);
-    //   k_line_sweep_thm (two-sided chain on the mirrored factorisation, halves of 8 lines in a pair of waves, smooth_thm.hpp)
-    //                                                             colours of < 8192 longer lines (128^3 level 0);
-    //   k_line_sweep_qc  (quad per line, compact factor, smooth_qc.hpp)   colours of >= 8192 lines (256^3 levels 0, 1);
-    //   k_line_sweep_rp  (one-sided chain, lane per row)         where neither applies (factor beyond 4 GiB, EMG3D_TWIST=0);
-    //   k_line_sweep_qc<..., BIG> (the same with 64-bit field offsets)      levels whose field arrays reach 4 GiB (q_big);
-    //   k_line_sweep     (thread per line, 64-bit offsets)       such levels in the lexicographic order or with fewer lines, EMG3D_SWEEP=tpl.
-    // EMG3D_QPL=<direction bit mask> (0: off), EMG3D_QPL_MAX_NL, EMG3D_QPL_FEW, EMG3D_QPL_M2 tune the first rule.
-    // EMG3D_BATCH_TUNE=1 (default 0): with batched systems, choose between the scan kernel and the chain kernels by the
-    // lines a LAUNCH carries (lines x systems) instead of the lines of one system -- the scan kernel does 4 x the
-    // arithmetic and only pays while the chain kernels leave SIMDs idle.  8 systems at 128^3: 50.3 -> 46.4 ms per cycle.
-    // Off by default because the kernel choice then depends on the batch size: a system's result agrees with its
-    // stand-alone solve to rounding (1e-12) instead of bit for bit.
-    int batch_tune = getenv("EMG3D_BATCH_TUNE") ? atoi(getenv("EMG3D_BATCH_TUNE")) : 0;
     // lexicographic order, lines of <= 16 blocks: hyperplane loop inside one workgroup instead of a launch per hyperplane
     int lex_loop = (int)LAB_ENV("EMG3D_LEX_LOOP", 1);
-    // k_line_sweep_tha (smooth_tha.hpp: the two-sided solve in affine form, helper waves) on the mid levels the scan kernel served:
-    // colour order, no split copies, lines of tha_min_nl .. tha_mid_nl (33..64) blocks, at least tha_min_lines lines per colour.
-    // Returns the helper waves per half (0: another kernel serves).  Measured per launch (profiles/r04_rs_shapes.txt, r04_tha_ab.txt):
-    // the launch is as long as its chain wave's work (~7 us + 0.6 us per step: 25 us at 64 blocks, 19 us at 40) whatever the
-    // number of lines up to 2048 (one workgroup per CU at 8 lines each); the scan kernel grows with the lines (64-block lines:
-    // 16 / 22 / 41 us at 512 / 1024 / 2048 lines per colour) and wins below ~1100; lines of <= 32 blocks stay with the scan kernel.
-    // Batched handles take the same kernel: the choice must not depend on the batch size (a system stays bit for bit its own solve).
-    int use_tha = (int)LAB_ENV("EMG3D_THA", 3);     // helper waves per half: 3 (lab: 2; 0: off, the scan kernel serves)
-    i64 tha_min_nl = LAB_ENV("EMG3D_THA_MIN", 33), tha_mid_nl = LAB_ENV("EMG3D_THA_MID", 64), tha_min_lines_env = LAB_ENV("EMG3D_THA_MIN_LINES", 0);
-    i64 tha_min_lines() const { return tha_min_lines_env > 0 ? tha_min_lines_env : (1100 * simds() + 1023) / 1024; }
-    // It also serves lines of 65..128 blocks (tha_max_nl) when a colour has at most 2048 lines (tha_big_max_lines), i.e. ONE round
-    // of workgroups at one per CU (142 KB of LDS at 128 blocks): 128 x 128 x 64, x- / y-lines: 74 -> 53 us per launch against
-    // k_line_sweep_thm, the grid's F-cycle 6.71 -> 6.25 ms (profiles/r04_tha_long_lines.txt).  Level 0 of 128^3 (4032 lines per
-    // colour = two rounds, each as long as its helper-bound forward pass) loses 103-105 to 86 us and keeps k_line_sweep_thm<8, ZS>
-    // (lab: EMG3D_THA_BIG_LINES=8192; HISTORY R4.8).
-    i64 tha_max_nl = LAB_ENV("EMG3D_THA_MAX", 128);
-    i64 tha_big_max_lines_env = LAB_ENV("EMG3D_THA_BIG_LINES", 0);
-    i64 tha_big_max_lines() const { return tha_big_max_lines_env > 0 ? tha_big_max_lines_env : (i64)THA_LPW * (simds() / 4); }
-    int tha_split = (int)LAB_ENV("EMG3D_THA_SPLIT", 0);     // lab: also on mid levels that have split copies (EMG3D_SPLIT_MIN_CELLS)
-    // LDS of a k_line_sweep_tha workgroup: up to 135 680 B dynamic (c128, 128-block lines) + THA_STATIC_LDS static.  Asked for once
-    // per handle; a device or runtime that refuses it (or has less LDS per workgroup) gets the other kernels (tha_helpers -> 0)
-    // instead of failing launches.
-    mutable int tha_lds_state = -1;     // -1: not asked yet, 0: refused, 1: granted
-    mutable i64 tha_lds_limit = 0;      // the device's LDS bytes per workgroup
-    bool tha_lds_ok(i64 nL) const {
-        if (tha_lds_state < 0) {
-            int lim = 0;
-            if (hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) { (void)hipGetLastError(); lim = 0; }
-            tha_lds_limit = lim;
-            const bool ok = lim >= THA_MAX_DYN_LDS + THA_STATIC_LDS && tha_attrs<T>(THA_MAX_DYN_LDS);
-            tha_lds_state = ok ? 1 : 0;
-        }
-        return tha_lds_state == 1 && (i64)tha_lds_bytes<T, 3>((int)nL) <= (i64)THA_MAX_DYN_LDS &&
-               (i64)tha_lds_bytes<T, 3>((int)nL) + THA_STATIC_LDS <= tha_lds_limit;
-    }
-    int tha_helpers(const Level<T>& L, int dir) const {
-        if ((use_tha != 3 && use_tha != 2) || order != 1 || sweep_kernel != 0 || !use_twist || !rp_fits(L)) return 0;
-        const i64 nL = L.nC[dir];
-        if (nL < tha_min_nl || nL > tha_max_nl || !tha_lds_ok(nL)) return 0;
-        const bool mid = nL >= tha_min_nl && nL <= tha_mid_nl && (!split_on(L) || tha_split);
-        const bool big = nL > tha_mid_nl && nL <= tha_max_nl;
-        if (!mid && !big) return 0;
-        const int P = (dir == 0) ? 1 : 0, Q = (dir == 2) ? 1 : 2;
-        const i64 lines = (L.nC[P] / 2) * (L.nC[Q] / 2);                // largest colour
-        if (lines < tha_min_lines() || lines >= q_min_lines()) return 0;
-        if (big && lines > tha_big_max_lines()) return 0;                 // (more than one round of workgroups at one per CU)
-        return use_tha;
-    }
-    bool qpl(const Level<T>& L, int dir) const {
-        if (!((use_qpl >> dir) & 1) || split_on(L) || sweep_kernel != 0 || tha_helpers(L, dir)) return false;
-        const i64 cap = (L.nC[dir] >= qpl_m2_min) ? 256 : 128;     // 8 waves x 16 quads x M blocks per line
-        const int P = (dir == 0) ? 1 : 0, Q = (dir == 2) ? 1 : 2;
-        i64 lines = (L.nC[P] / 2) * (L.nC[Q] / 2);                  // per colour
-        i64 max_nl = qpl_max_nl;
-        if (batch_tune && nsys > 1 && order == 1) {                 // a launch carries nsys x the lines (see batch_tune)
-            lines *= nsys;
-            max_nl = std::max<i64>(4, qpl_max_nl / nsys);
-        }
-        const i64 maxnl = (order == 0 || lines <= qpl_few_lines()) ? cap : std::min<i64>(max_nl, cap);
-        if (L.nC[dir] < qpl_min_nl || L.nC[dir] > maxnl || !rp_fits(L)) return false;
-        return lines <= qpl_max_lines;
-    }
-    // (lines that fit ONE wave -- seg <= 16 -- get single-wave workgroups: fewer, fatter workgroups were measured slower, 8.54 -> 8.8 /
-    // 9.1 / 10.5 ms per 128^3 F-cycle at 2 / 4 / 8 waves, HISTORY R5.13)
-    // workgroup waves NW, blocks per quad M, quads per line seg (power of two, M * seg >= nL)
-    void qpl_shape(i64 nL, int& NW, int& M, int& seg) const {
-        M = (nL >= qpl_m2_min) ? 2 : 1;
-        const i64 nch = (nL + M - 1) / M;
-        seg = 4; while (seg < nch) seg *= 2;
-        NW = seg <= 16 ? 1 : seg / 16;
-    }
     // sweep = false: arguments for k_line_factor (un-split model arrays);
     // sweep = true : arguments for the sweep kernels (working copies).
     void line_args(Level<T>& L, int dir, LineArgs<T>& a, bool sweep) {
         if (dir == 0) { a.L = 0; a.P = 1; a.Q = 2; }
         else if (dir == 1) { a.L = 1; a.P = 0; a.Q = 2; }
         else { a.L = 2; a.P = 0; a.Q = 1; }
-        const bool sp = sweep && split_on(L);
+        const SweepPlan& P = plan(L, dir);
+        const bool sp = sweep && P.split;
         // the split working copy of the x direction is always the transposed one
-        const bool t = (sp && dir == 0) ? true : xt(L, dir);
+        const bool t = (sp && dir == 0) ? true : P.xt;
         const int w = (dir == 0) ? 0 : 1;
         for (int q = 0; q < 3; ++q) {
             a.nC[q] = L.nC[q]; a.eta[q] = t ? L.etaT[q] : L.eta[q]; a.h[q] = L.h[q]; a.ih[q] = L.ih[q];
@@ -1174,102 +997,22 @@ struct MG : emg3d_mg {
             }
         }
         a.qd = nullptr; a.qdn = 0;
-        a.qpl = 0; a.qM = 0; a.seg = 0; a.qlpw = 0;
-        if (qpl(L, dir)) { int NW, M, seg; qpl_shape(L.nC[a.L], NW, M, seg); a.qpl = NW; a.qM = M; a.seg = seg; }
-        a.tha = tha_helpers(L, dir);
+        a.qpl = P.NW; a.qM = P.M; a.seg = P.seg; a.qlpw = 0;
+        a.tha = P.helpers;
         a.mode = 0; a.cP = a.cQ = 0; a.cntA = a.cntB = 0; a.t = a.jQ0 = a.cnt = 0;
         a.bt = sweep ? batch(L) : Batch();
     }
 
-    // Two-sided factorisation + k_line_sweep_thm for latency-bound launches: fewer than 8192 lines per colour (beyond that the
-    // sweep is HBM bound and the quad-per-line kernel on the compact factor moves fewer bytes), strides within the 24-bit
-    // multiplies of the kernel (twist_ok).
-    // quad-per-line chain kernel for this (level, direction)?  Decided by the level's largest colour.
-    bool q_on(const LineArgs<T>& a) const {
-        return use_q >= 2 || (use_q == 1 && a.nA[0] * a.nB2[0] >= q_min_lines());
-    }
-    // Two-sided sweeps on the MIRRORED factorisation (k_line_sweep_thm: left blocks [l_i; T_i] upwards, right blocks
-    // [l_j; T_{j-1}] downwards: the reference's accuracy; round 1's plain two-sided grouping was 1e-8 on ill-conditioned lines).
-    bool thm_on(const Level<T>& L, const LineArgs<T>& a) const { return twist_ok(L, a); }
-    bool twist_ok(const Level<T>& L, const LineArgs<T>& a) const {
-        if (q_on(a)) return false;                    // the quad-per-line kernel has its own (compact, one-sided) factorisation
-        if (!use_twist || !rp_fits(L) || L.nC[a.L] < 3) return false;
-        const i64 nQ = L.nC[a.Q];
-        const i64 maxlines = a.nA[0] * ((nQ - 0) / 2);
-        if (maxlines >= twist_max_lines()) return false;
-        const i64 lim24 = (i64)1 << 24;
-        i64 mxs = 15 * a.nLinesTot * (i64)sizeof(T);
-        for (int c = 0; c < 3; ++c) mxs = std::max(mxs, a.fl.st[c][a.L] * (i64)sizeof(T));
-        mxs = std::max(mxs, a.cl.st[a.L] * 8);
-        // the two-sided kernels form the factor offset block * stride + entry in 32 bits: the whole factor of
-        // the direction must stay below 4 GiB (160 x 160 x 768 complex would wrap silently otherwise)
-        const i64 fac_bytes = 15 * a.nLinesTot * L.nC[a.L] * (i64)sizeof(T);
-        return mxs < lim24 && L.nC[a.L] < lim24 && fac_bytes < ((i64)1 << 32);
-    }
-
-    // Layout of the cached factorisation of (level, direction), i.e. which kernel family will sweep it (Level::fac_kind): 4 = compact
-    // (G and r: 11 numbers per block) wherever the quad-per-line kernel serves (smooth_qc.hpp), 3 = mirrored two-sided
-    // (k_line_sweep_thm / _tha), 0 = one-sided, 15 numbers per block (scan kernel, k_line_sweep_rp, thread per line).  a: line_args(L, dir, a, false).
-    int factor_kind(const Level<T>& L, const LineArgs<T>& a) const {
-        if (!a.qpl && thm_on(L, a)) return 3;
-        return (!a.qpl && (rp_fits(L) || q_big(L)) && q_on(a) && sweep_kernel == 0) ? 4 : 0;
-    }
-    // The kernel instantiation the colour launches of (level, direction) select, by name as `rocprofv3 --kernel-trace` and
-    // emg3d_mg_last_sweep_kernel show it, from the level's SHAPE alone -- the same predicates ensure_factor / launch_sweep use, no
-    // device memory, no launch (emg3d_sweep_plan: host-side tests of the selection on devices of other sizes).  info: [0] lines of
-    // the largest colour, [1] lines per wave (qc, rp: per wave; thm: per pair of waves; tha: per workgroup; qpl: lines per workgroup),
-    // [2] rounds of waves / workgroups of the largest colour's launch, [3] factor layout (factor_kind), [4] sweeps run on
-    // parity-split working copies, [5] 64-bit field offsets.
-    void plan_sweep(Level<T>& L, int dir, char* name, i64 info[6]) {
-        LineArgs<T> a;
-        line_args(L, dir, a, false);
-        const int kind = factor_kind(L, a);
-        const bool big = q_big(L) && !rp_fits(L), rp = rp_fits(L) || big;
-        const i64 nmax = a.nA[0] * a.nB2[0], S = simds();
-        const char* tn = sizeof(T) == 16 ? "c128" : "f64";
-        i64 lpw = 0, rounds = 0;
-        if (kind == 3 && a.tha) {
-            snprintf(name, 64, "k_line_sweep_tha<%s,%d>", tn, a.tha);
-            lpw = THA_LPW; rounds = (((nmax + THA_LPW - 1) / THA_LPW) * nsys + S / 4 - 1) / (S / 4);
-        } else if (kind == 3) {
-            lpw = th_lines_per_pair(a);
-            snprintf(name, 64, "k_line_sweep_thm<%s,%d,%d>", tn, tw_stages ? tw_stages : 3, (int)lpw);
-            rounds = (2 * ((nmax + lpw - 1) / lpw) * nsys + S - 1) / S;
-        } else if (a.qpl) {
-            snprintf(name, 64, "%s<%s,%d,%d>", (a.qpl == 1 && a.qM == 1 && order == 1 && a.seg <= qpl_chain_seg) ? "k_line_sweep_qpl_chain" : "k_line_sweep_qpl",
-                     tn, a.qpl, a.qM);
-            lpw = (16 * a.qpl) / a.seg;
-            rounds = (((nmax + lpw - 1) / lpw) * a.qpl * nsys + S - 1) / S;
-        } else if (rp && kind == 4) {
-            const int inst = big ? 16 : q_lpw ? q_lpw : (nmax >= q_min_lines() ? 16 : 4);
-            snprintf(name, 64, "%s<%s,%d,%d>", big ? "k_line_sweep_qc_big" : "k_line_sweep_qc", tn, q_stages_for(inst, nmax), inst);
-            lpw = inst == 16 ? q_balanced_lpw(nmax * nsys) : inst;
-            rounds = (((nmax + lpw - 1) / lpw) * nsys + S - 1) / S;
-        } else if (rp) {
-            lpw = force_lpw ? force_lpw : (nmax >= 8 * S ? 8 : 4);
-            snprintf(name, 64, "k_line_sweep_rp<%s,%d>", tn, (lpw == 8 || lpw == 12) ? (int)lpw : 4);
-            rounds = (((nmax + lpw - 1) / lpw) * nsys + S - 1) / S;
-        } else {
-            snprintf(name, 64, "k_line_sweep<%s>", tn);
-            lpw = 64; rounds = (((nmax + 63) / 64) * nsys + S - 1) / S;
-        }
-        info[0] = nmax; info[1] = lpw; info[2] = rounds; info[3] = kind; info[4] = split_on(L) ? 1 : 0; info[5] = big ? 1 : 0;
-    }
+    // The cached factorisation of (level, direction), in the layout of the kernel family that will sweep it (SweepPlan::fac_kind).
     void ensure_factor(Level<T>& L, int dir) {
-        if (xt(L, dir)) ensure_transposed_model(L);
+        const SweepPlan& P = plan(L, dir);
+        if (P.xt) ensure_transposed_model(L);
         if (L.fac[dir]) return;
-        LineArgs<T> a;
-        line_args(L, dir, a, false);
-        const i64 per_line = a.qpl ? (i64)a.qM * a.seg : L.nC[a.L];
-        const int kind = factor_kind(L, a);
-        L.fac[dir] = dalloc<T>(a.nLinesTot * per_line * (kind == 4 ? 11 : 15));
-        L.fac_lines[dir] = a.nLinesTot;
-        L.fac_mid[dir] = L.nC[a.L] - 1;     // one-sided, unless ...
-        L.fac_kind[dir] = kind;
-        if (kind == 3) {                    // ... the mirrored two-sided factorisation serves
-            L.fac_mid[dir] = qm_mid(L.nC[a.L]);
-            thm_attrs();
-        }
+        L.fac_lines[dir] = (L.nC[dir == 0 ? 1 : 0] - 1) * (L.nC[dir == 2 ? 1 : 2] - 1);
+        L.fac[dir] = dalloc<T>(L.fac_lines[dir] * P.fac_entries);
+        L.fac_mid[dir] = P.mid;
+        L.fac_kind[dir] = P.fac_kind;
+        if (P.fac_kind == 3) thm_attrs();
         compute_factor(L, dir);
     }
     // (re)compute the cached factorisation of (level, direction) into its buffer: the model may have changed (set_smu0)
@@ -1317,65 +1060,30 @@ struct MG : emg3d_mg {
         check_launch();
     }
 
-    // n independent lines: row-parallel kernel (8 lanes per line) by default;
-    // EMG3D_SWEEP=tpl selects the thread-per-line kernel (A/B + debugging).
-    // Lines per wave: with few lines the recurrence is latency bound and more
-    // waves win (4 lines/wave); with many lines the sweep is HBM bound and
-    // fewer, fuller waves move fewer bytes (8 lines/wave).  Measured on MI355X:
-    // 128^3 (4032 lines/colour) 0.67 vs 0.75 ms, 256^3 (16129) 5.6 vs 4.6 ms.
-    // workgroups of a row-parallel launch (a multiple of the 8 XCDs when the XCD-aware map is on:
-    // the kernels drop the workgroups past the last line)
-    unsigned rp_grid(i64 nt) const {
-        const i64 nb = (nt + EMG_RP_BLOCK - 1) / EMG_RP_BLOCK;
-        return (unsigned)(xcd_map ? ((nb + 7) / 8) * 8 : nb);
-    }
-    template <int LPW>
-    void launch_rp(const LineArgs<T>& a, i64 n) {
-        const i64 nwaves = (n + LPW - 1) / LPW;
-        const i64 nt = nwaves * 64;
-        MG_LAUNCH((k_line_sweep_rp<T, LPW>), bgrid(rp_grid(nt)), dim3(EMG_RP_BLOCK), 0, stream, a);
-    }
-    void launch_qpl(const LineArgs<T>& a, i64 n) {
-        const int NW = a.qpl;
-        const i64 lpg = (16 * NW) / a.seg;              // lines per workgroup
-        const i64 nb = (n + lpg - 1) / lpg;
-        if (broken) return;
-        // (single-wave workgroups in colour order: with the descriptors written when the factor was built, ensure_qdesc)
-        const bool chain = NW == 1 && a.qM == 1 && a.mode == 0 && a.seg <= qpl_chain_seg;
-        qpl_launch<T>(NW, a.qM, false, (NW == 1 && a.qd) ? 2 : 0, chain, bgrid(qpl_grid(nb)), stream, a);
-        if (chain) note_kernel("k_line_sweep_qpl_chain", NW, a.qM);
-    }
-    unsigned qpl_grid(i64 nb) const { return (unsigned)(xcd_map ? ((nb + 7) / 8) * 8 : nb); }
+    // workgroups of a lane-group launch (a multiple of the 8 XCDs when the XCD-aware map is on: the kernels drop the workgroups
+    // past the last line)
+    unsigned xcd_grid(i64 nb) const { return (unsigned)(xcd_map ? ((nb + 7) / 8) * 8 : nb); }
+    unsigned rp_grid(i64 nt) const { return xcd_grid((nt + EMG_RP_BLOCK - 1) / EMG_RP_BLOCK); }
     // Descriptors of the scan kernel's colour launches on levels of short lines (one wave per workgroup): everything of the
     // prologue that depends on grid and model only -- 11 element offsets / flags and 15 coefficient products per lane and block --
     // is computed ONCE, by the kernel's own prologue in generating mode, and loaded by the 7 launches of every smoothing call
-    // thereafter (HISTORY R5.12).  176 B per thread: only where a colour launch has at most qdesc_max_threads threads and the factor
-    // has fewer than 2^32 entries.  Measured (profiles/r05_qdesc_ab.txt, 128^3 F-cycle, three alternating repetitions): off 8.57 /
-    // 8.54 / 8.50 ms; launches of <= 9000 threads (308 of the 420 on <= 16-block lines) 8.456 / 8.458 / 8.451; <= 40 000 threads (all
-    // 420) 8.495 / 8.468 / 8.48; the 32-block level too (two blocks per quad, 65 k threads) 8.72: beyond ~8 k threads the table costs
-    // more to read than the arithmetic it replaces.  In-kernel stamps at 128 x 4 x 4: 8330 -> 7500 cycles.
-    int use_qdesc = (int)LAB_ENV("EMG3D_QDESC", 1);
-    i64 qdesc_max_threads_env = LAB_ENV("EMG3D_QDESC_MAX", 0);
-    i64 qdesc_max_threads() const { return qdesc_max_threads_env > 0 ? qdesc_max_threads_env : (9000 * simds() + 1023) / 1024; }
+    // thereafter (HISTORY R5.12).  Where: SweepPlan::qdesc.
     void ensure_qdesc(Level<T>& L, int dir) {
-        if (!use_qdesc || order != 1 || L.qd[dir][0] || L.qdn[dir][0] == ~0u) return;
+        const SweepPlan& P = plan(L, dir);
+        if (!P.qdesc || L.qd[dir][0] || L.qdn[dir][0] == ~0u) return;
+        L.qdn[dir][0] = ~0u;                                    // (asked once)
+        if (!L.fac[dir]) return;
         LineArgs<T> a;
         line_args(L, dir, a, true);
-        L.qdn[dir][0] = ~0u;                                    // (asked once)
-        if (a.qpl != 1 || !L.fac[dir]) return;
-        const i64 nQ = L.nC[a.Q];
-        const i64 nB[2] = {(nQ - 0) / 2, (nQ - 1) / 2};
-        const i64 lpg = 16 / a.seg, per = (i64)a.qM * a.seg;
-        if (a.nLinesTot * 15 * per >= ((i64)1 << 32)) return;
-        if (((a.nA[0] * nB[0] + lpg - 1) / lpg) * 64 > qdesc_max_threads()) return;
+        const i64 lpg = 16 / a.seg;
         a.bt = Batch();                                         // (the descriptors do not depend on the system)
         for (int c = 0; c < 4; ++c) {
             a.mode = 0; a.cP = c & 1; a.cQ = c >> 1;
-            a.cntA = a.nA[a.cP]; a.cntB = nB[a.cQ];
+            a.cntA = a.nA[a.cP]; a.cntB = a.nB2[a.cQ];
             a.rs.slot0 = (unsigned)a.base[c];
             const i64 n = a.cntA * a.cntB;
             if (n <= 0) continue;
-            const unsigned grid = qpl_grid((n + lpg - 1) / lpg);
+            const unsigned grid = xcd_grid((n + lpg - 1) / lpg);
             const i64 nthreads = (i64)grid * 64;
             void* tab = try_alloc<char>(nthreads * a.qM * (3 * 16 + 8 * 16));     // (pure optimisation data: without it the kernel computes)
             if (!tab) return;
@@ -1389,36 +1097,6 @@ struct MG : emg3d_mg {
     // sweep-level parity tests report it instead of guessing from the grid size)
     char sweep_name[64] = "";
     char res_name[64] = "";            // the same for the most recent residual launch
-    void note_kernel(const char* base, int p1, int p2) {
-        const char* tn = sizeof(T) == 16 ? "c128" : "f64";
-        if (p2 >= 0) snprintf(sweep_name, sizeof sweep_name, "%s<%s,%d,%d>", base, tn, p1, p2);
-        else if (p1 >= 0) snprintf(sweep_name, sizeof sweep_name, "%s<%s,%d>", base, tn, p1);
-        else snprintf(sweep_name, sizeof sweep_name, "%s<%s>", base, tn);
-    }
-    // A launch of the quad kernel at 16 lines per wave is ONE wave per SIMD (three prefetch stages: 322+ registers; with two stages a
-    // second wave fits, but one full wave per SIMD is the faster form -- 256^3: 9 lines per wave on two waves per SIMD 0.90 against
-    // 0.73 ms).  Its waves all last the same time, so a launch of W waves on C = SIMDs wave slots lasts ceil(W / C) rounds: 448^3 --
-    // 3136 waves = 3.06 rounds of 1024 -- pays four (12.9 % of the roofline where 512^3, exactly four rounds, reaches 16 %).  Deal the
-    // lines evenly instead: the fewest rounds r that 16 lines per wave allow, then ceil(lines / (C r)) lines per wave (>= 8: levels of
-    // 8192 ... 16383 lines per colour take the same path, launch_sweep).  Measured by size (profiles/r05_balanced_lpw.txt, dense source, % of the
-    // algorithmic roofline): 288^3 11.6 -> 13.9, 320^3 14.8 -> 15.8, 368^3 12.5 -> 14.9, 384^3 13.4 -> 15.1, 448^3 12.9 -> 14.4, 480^3
-    // 14.1 -> 14.5; 256^3, 352^3, 512^3 (whole rounds already) unchanged.  Bit-identical (a line's arithmetic does not know its
-    // wave).
-    int q_balanced_lpw(i64 lines) const {
-        const i64 cap = simd_count();
-        const i64 rounds = std::max<i64>(1, (lines + 16 * cap - 1) / (16 * cap));
-        const i64 lpw = (lines + cap * rounds - 1) / (cap * rounds);
-        return (int)std::min<i64>(16, std::max<i64>(lpw, 8));
-    }
-    // lpw: the instantiation (16 | 8 | 4 | 2 lines per wave; big: the 16-line one with 64-bit field offsets); the 16-line
-    // instantiation runs at the balanced number of lines per wave
-    void launch_qc(const LineArgs<T>& a0, i64 n, int lpw, bool big) {
-        LineArgs<T> a = a0;
-        if (big) lpw = 16;
-        a.qlpw = (lpw == 16) ? q_balanced_lpw(n * nsys) : lpw;
-        const i64 nt = ((n + a.qlpw - 1) / a.qlpw) * 64;
-        if (!broken) qc_launch<T>(q_stages_for(lpw, a.nA[0] * a.nB2[0]), lpw, a.zsep != 0, big, bgrid(rp_grid(nt)), stream, a);
-    }
     // lab: k_line_sweep_thm can keep the last KL forward steps of a half in LDS (smooth_thm.hpp; KL by lines per pair of waves
     // so that the workgroup stays within the CU's 160 KB).  Measured at 128^3: counted traffic 491 -> 453 MB per launch,
     // launch 102.3 -> 103.7 us (profiles/HISTORY.md) -- the saving sits in steps during which every wave of the launch is
@@ -1426,7 +1104,7 @@ struct MG : emg3d_mg {
     int thm_lifo = (int)LAB_ENV("EMG3D_THM_LIFO", 0);
     // More than 64 KB of LDS per workgroup must be asked for, per kernel instantiation and device; done when the factor of
     // a two-sided level is built, i.e. before the launches are captured into a graph.  (Only the lab build's LIFO variants need
-    // it; k_line_sweep_tha's dynamic LDS is asked for where the kernel is selected: tha_lds_ok.)
+    // it; k_line_sweep_tha's dynamic LDS is asked for with the device's size: sweep_device_knobs.)
     void thm_attrs() {
 #ifdef EMG3D_LAB
         static bool done[64] = {false};
@@ -1435,61 +1113,48 @@ struct MG : emg3d_mg {
         thm_lifo_attrs<T>();
 #endif
     }
-    void launch_thm_l(const LineArgs<T>& a, i64 n, int LPW) {
-        const i64 npairs = (n + LPW - 1) / LPW;
-        const i64 nb = (npairs * 128 + EMG_RP_BLOCK - 1) / EMG_RP_BLOCK;
-        const unsigned grid = (unsigned)(xcd_map ? ((nb + 7) / 8) * 8 : nb);
-        const int stages = tw_stages ? tw_stages : 3;
-        note_kernel("k_line_sweep_thm", stages, LPW);
-        if (!broken) thm_launch<T>(stages, LPW, thm_lifo != 0, a.zsep != 0, bgrid(grid), stream, a);
-    }
-    void launch_tha(const LineArgs<T>& a, i64 n, int NH) {
-        const i64 nb = (n + THA_LPW - 1) / THA_LPW;
-        const unsigned grid = (unsigned)(xcd_map ? ((nb + 7) / 8) * 8 : nb);
-        snprintf(sweep_name, sizeof sweep_name, "k_line_sweep_tha<%s,%d>", sizeof(T) == 16 ? "c128" : "f64", NH);
-        const size_t dyn = NH == 2 ? tha_lds_bytes<T, 2>((int)a.nC[a.L]) : tha_lds_bytes<T, 3>((int)a.nC[a.L]);
-        if (!broken) tha_launch<T>(NH, a.zsep != 0, bgrid(grid), dyn, stream, a);
-    }
-    void launch_thm(const LineArgs<T>& a, i64 n) {
-        if (a.tha) {                    // mid levels: the affine kernel with three helper waves per half (HISTORY R4.6-R4.7)
-#ifdef EMG3D_LAB
-            if (a.tha == 2) { launch_tha(a, n, 2); return; }
-#endif
-            launch_tha(a, n, 3);
-            return;
-        }
-        const int lpw = th_lines_per_pair(a);
-        launch_thm_l(a, n, (lpw == 4 || lpw == 12) ? lpw : 8);
-    }
-    void launch_sweep(const LineArgs<T>& a, i64 n, bool rp, bool big = false) {
+    // One launch of n lines (a colour, or a hyperplane of the lexicographic order) with the kernel the plan names: the grid, and the
+    // instantiation through sweep_launch.hpp.
+    void launch_sweep(const SweepPlan& P, const LineArgs<T>& a, i64 n) {
         if (log_launches) fprintf(stderr, "[sweep] nC %lld %lld %lld L %d lines %lld kernel %s split %d\n", (long long)a.nC[0], (long long)a.nC[1], (long long)a.nC[2], a.L, (long long)n,
-                                  a.qm == 2 ? "thm" : a.qpl ? "qpl" : (rp && a.fcomp) ? "qc" : rp ? "rp" : "tpl", a.split);
-        if (a.qm == 2) {
-            launch_thm(a, n);
-        } else if (a.qpl) {
-            note_kernel("k_line_sweep_qpl", a.qpl, a.qM);
-            launch_qpl(a, n);
-        } else if (rp && a.fcomp) {
-            // lines per wave by the level's largest colour: aim at >= ~1000 waves (one per SIMD) before filling lanes
-            const i64 nmax = a.nA[0] * a.nB2[0];
-            // (8192 ... 16383 lines: the 16-line instantiation at ceil(lines / SIMDs) = 8 ... 16 lines per wave -- ONE round of waves --
-            // instead of 8 lines per wave in up to two, q_balanced_lpw)
-            const int lpw = big ? 16 : q_lpw ? q_lpw : (nmax >= q_min_lines() ? 16 : 4);
-            note_kernel(big ? "k_line_sweep_qc_big" : "k_line_sweep_qc", q_stages_for(lpw, nmax), lpw);
-            launch_qc(a, n, lpw, big);
-        } else if (rp) {
-            // by the level's largest colour, not by this colour's own count: the colours of one level
-            // must not straddle the threshold (256 x 128 x 128: 8192 / 8128 / 8064 / 8001 lines; 8 lines per
-            // wave 0.20 ms per launch, 4 lines per wave 0.30 ms)
-            const int lpw = force_lpw ? force_lpw : (a.nA[0] * a.nB2[0] >= 8 * simds() ? 8 : 4);
-            note_kernel("k_line_sweep_rp", (lpw == 8 || lpw == 12) ? lpw : 4, -1);
-            if (lpw == 8) launch_rp<8>(a, n);
-            else if (lpw == 12) launch_rp<12>(a, n);
-            else launch_rp<4>(a, n);
-        } else {
-            note_kernel("k_line_sweep", -1, -1);
-            MG_LAUNCH(k_line_sweep<T>, bgrid_y((unsigned)((n + EMG_LINE_BLOCK - 1) / EMG_LINE_BLOCK)),
-                               dim3(EMG_LINE_BLOCK), 0, stream, a);
+                                  P.name, a.split);
+        memcpy(sweep_name, P.name, sizeof sweep_name);
+        if (broken) return;
+        switch (P.family) {
+        case SweepFamily::tha: {        // one workgroup per THA_LPW lines
+            const size_t dyn = P.helpers == 2 ? tha_lds_bytes<T, 2>((int)a.nC[a.L]) : tha_lds_bytes<T, 3>((int)a.nC[a.L]);
+            tha_launch<T>(P.helpers, a.zsep != 0, bgrid(xcd_grid((n + THA_LPW - 1) / THA_LPW)), dyn, stream, a);
+            break;
+        }
+        case SweepFamily::thm: {        // a pair of waves per inst_lpw lines
+            const i64 npairs = (n + P.inst_lpw - 1) / P.inst_lpw;
+            thm_launch<T>(P.stages, P.inst_lpw, thm_lifo != 0, a.zsep != 0, bgrid(rp_grid(npairs * 128)), stream, a);
+            break;
+        }
+        case SweepFamily::qpl:
+        case SweepFamily::qpl_chain: {  // (16 NW) / seg lines per workgroup; single-wave workgroups load the descriptors of ensure_qdesc
+            const i64 lpg = (16 * P.NW) / P.seg;
+            qpl_launch<T>(P.NW, P.M, false, (P.NW == 1 && a.qd) ? 2 : 0, P.family == SweepFamily::qpl_chain,
+                          bgrid(xcd_grid((n + lpg - 1) / lpg)), stream, a);
+            break;
+        }
+        case SweepFamily::qc:
+        case SweepFamily::qc_big: {     // the 16-line instantiation runs at the balanced number of lines per wave of THIS launch
+            LineArgs<T> b = a;
+            b.qlpw = P.inst_lpw == 16 ? sweep_balanced_lpw(knobs, n * nsys) : P.inst_lpw;
+            qc_launch<T>(P.stages, P.inst_lpw, a.zsep != 0, P.big, bgrid(rp_grid(((n + b.qlpw - 1) / b.qlpw) * 64)), stream, b);
+            break;
+        }
+        case SweepFamily::rp: {
+            const unsigned g = rp_grid(((n + P.inst_lpw - 1) / P.inst_lpw) * 64);
+            if (P.inst_lpw == 8) hipLaunchKernelGGL((k_line_sweep_rp<T, 8>), bgrid(g), dim3(EMG_RP_BLOCK), 0, stream, a);
+            else if (P.inst_lpw == 12) hipLaunchKernelGGL((k_line_sweep_rp<T, 12>), bgrid(g), dim3(EMG_RP_BLOCK), 0, stream, a);
+            else hipLaunchKernelGGL((k_line_sweep_rp<T, 4>), bgrid(g), dim3(EMG_RP_BLOCK), 0, stream, a);
+            break;
+        }
+        case SweepFamily::tpl:
+            hipLaunchKernelGGL(k_line_sweep<T>, bgrid_y((unsigned)((n + EMG_LINE_BLOCK - 1) / EMG_LINE_BLOCK)), dim3(EMG_LINE_BLOCK), 0, stream, a);
+            break;
         }
     }
 
@@ -1500,7 +1165,7 @@ struct MG : emg3d_mg {
         ensure_sflags(L, dir);          // (dry: allocation only)
         if (home_on(L) || home_lvl(L)) ensure_work(L, 1);
         if (split_on(L)) ensure_work(L, (dir == 0) ? 0 : 1);
-        else if (xt(L, dir)) ensure_transposed_model(L);
+        else if (plan(L, dir).xt) ensure_transposed_model(L);
     }
     void to_work(Level<T>& L, int dir) {
         ensure_sflags(L, dir);
@@ -1520,7 +1185,7 @@ struct MG : emg3d_mg {
                 e_to_w1(L);
                 if (w == 0) convert_field(L, L.eW[0], L.eW[1], 2, true);
             }
-        } else if (xt(L, dir)) {
+        } else if (plan(L, dir).xt) {
             if (!L.sT_valid) { convert_field(L, L.sT, L.s, -1, true); L.sT_valid = true; }
             convert_field(L, L.eT, L.e, -1, true);
         }
@@ -1529,9 +1194,9 @@ struct MG : emg3d_mg {
         if (home_on(L) || home_lvl(L)) {       // the field stays in (x-lines: goes to) the x-split copy
             if (dir == 0) convert_field(L, L.eW[1], L.eW[0], 2, false);
         } else if (split_on(L)) convert_field(L, L.e, L.eW[(dir == 0) ? 0 : 1], (dir == 0) ? 0 : 1, false);
-        else if (xt(L, dir)) convert_field(L, L.e, L.eT, -1, false);
+        else if (plan(L, dir).xt) convert_field(L, L.e, L.eT, -1, false);
     }
-    int work_id(Level<T>& L, int dir) { return split_on(L) ? ((dir == 0) ? 0 : 1) : (xt(L, dir) ? 2 : 3 + dir); }
+    int work_id(Level<T>& L, int dir) { return plan(L, dir).work_id; }
 
     // ---- placement of level 0's WRITTEN working copies (HISTORY R5.18, R6.1) -----------------------------------------------
     // A level-0 colour launch at 256^3 lasts 0.62 ... 0.73 ms depending on which piece of physical memory the working copy it
@@ -1556,12 +1221,12 @@ struct MG : emg3d_mg {
         return dir == 0 ? (lr == 1 || lr == 5 || lr == 6 || lr == 7) : dir == 1 ? (lr == 2 || lr == 4 || lr == 6 || lr == 7)
                                                                               : (lr == 3 || lr == 4 || lr == 5 || lr == 7);
     }
-    bool place_applies(const Level<T>& L) const {
-        return place_tries > 1 && order == 1 && sweep_kernel == 0 && !trace && split_on(L) &&
+    bool place_applies(Level<T>& L) {
+        return place_tries > 1 && order == 1 && !trace && split_on(L) &&
                (i64)nsys * L.nE * (i64)sizeof(T) >= place_min_bytes;
     }
-    bool placement_pending(int lr_dir) const {
-        const Level<T>& L = *lv0;
+    bool placement_pending(int lr_dir) {
+        Level<T>& L = *lv0;
         if (!place_applies(L)) return false;
         const int lr = current_lr_dir(lr_dir, L.nC);
         return (lr_has(lr, 0) && !placed[0]) || ((lr_has(lr, 1) || lr_has(lr, 2)) && !placed[1]);
@@ -1655,8 +1320,7 @@ struct MG : emg3d_mg {
         ensure_sflags(L, dir);          // (valid already inside a captured sequence: refresh_level0_source)
         LineArgs<T> a;
         line_args(L, dir, a, true);
-        const bool big = q_big(L) && !rp_fits(L);          // 64-bit field offsets (a.fcomp is set: ensure_factor)
-        const bool rp = rp_fits(L) || big;
+        const SweepPlan& P = plan(L, dir);
         const i64 nP = L.nC[a.P], nQ = L.nC[a.Q];
         const i64 nB[2] = {(nQ - 0) / 2, (nQ - 1) / 2};
         int iback = 0;
@@ -1680,7 +1344,7 @@ struct MG : emg3d_mg {
                     a.qd = L.qd[dir][c]; a.qdn = (L.qd[dir][c] ? L.qdn[dir][c] : 0u);
                     const i64 n = a.cntA * a.cntB;
                     if (n <= 0) continue;
-                    launch_sweep(a, n, rp, big);
+                    launch_sweep(P, a, n);
                 }
             } else {
                 const i64 tmin = 3, tmax = (nP - 1) + 2 * (nQ - 1);
@@ -1692,7 +1356,7 @@ struct MG : emg3d_mg {
                     const i64 maxn = std::min<i64>(nQ - 1, (nP - 1) / 2 + 1), quads = maxn * a.seg;
                     const int lnw = quads <= 16 ? 1 : quads <= 32 ? 2 : quads <= 64 ? 4 : 8;
                     if (!broken) qpl_launch<T>(lnw, 1, true, 0, false, bgrid(1), stream, b);
-                    note_kernel("k_line_sweep_qpl", lnw, 1);
+                    sweep_kernel_name(sweep_name, sizeof sweep_name, SweepFamily::qpl, (int)sizeof(T), lnw, 1);
                     continue;
                 }
                 for (i64 th = tmin; th <= tmax; ++th) {
@@ -1705,7 +1369,7 @@ struct MG : emg3d_mg {
                     const i64 n = jQ1 - jQ0 + 1;
                     if (n <= 0) continue;
                     a.mode = 1; a.t = tt; a.jQ0 = jQ0; a.cnt = n;
-                    launch_sweep(a, n, rp);
+                    launch_sweep(P, a, n);
                 }
             }
         }
@@ -2008,7 +1672,7 @@ struct MG : emg3d_mg {
         // (the launch descriptors carry factor offsets of the layout they were generated for: they go with the factor)
         auto clear = [](Level<T>& L) {
             for (int d = 0; d < 3; ++d) {
-                L.fac[d] = nullptr; L.fac_kind[d] = 0;
+                L.fac[d] = nullptr; L.fac_kind[d] = 0; L.plan_key[d] = -1;
                 for (int c = 0; c < 4; ++c) { L.qd[d][c] = nullptr; L.qdn[d][c] = 0; }
             }
         };

@@ -111,7 +111,8 @@ int emg3d_restrict_model(int is_complex, int64_t nx, int64_t ny, int64_t nz, voi
 /* Which line-sweep kernel the library selects for the colour launches (order 1; order 0: the hyperplane launches) of a level of
  * nx x ny x nz cells along dir (1, 2, 3 = x, y, z) on a device of cu_count compute units (<= 0: the current device) with nsys
  * batched systems -- the launch selection of the handle (reference: the one loop of core.gauss_seidel_x/_y/_z, emg3d/core.py:477-1316,
- * has no such choice) evaluated on the shape alone: no device memory, no launch, callable without a GPU when cu_count > 0.
+ * has no such choice) evaluated on the shape alone: no device memory, no launch, callable without a GPU when cu_count > 0.  The
+ * selection lives in csrc/sweep_plan.hpp (plan_sweep): this call and the handle's launches read the same SweepPlan.
  * name (>= 64 bytes): the instantiation as emg3d_mg_last_sweep_kernel reports it; info[6]: lines of the largest colour, lines per
  * wave (thm: per pair of waves, tha / qpl: per workgroup), rounds of waves of that colour's launch, factor layout (0 one-sided 15
  * numbers per block, 3 mirrored two-sided, 4 compact 11 numbers), parity-split working copies (0 / 1), 64-bit field offsets (0 / 1). */

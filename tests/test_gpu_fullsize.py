@@ -348,8 +348,8 @@ def test_384_one_sweep_vs_oracle(oracle):
 @pytest.mark.parametrize("shape", [(256, 128, 64), (96, 160, 48), (320, 32, 40), (64, 72, 264), (136, 136, 136)])
 def test_sweep_plan_matches_the_launches_and_the_oracle(oracle, shape):
     """Non-cubic grids, where every line direction lands in another kernel family: (a) the instantiation a handle launches on level 0 is
-    the one `emg3d_sweep_plan` predicts from the shape and THIS device's CU count (the host-side planning function and the launch path
-    evaluate the same predicates); (b) one colour-ordered sweep per direction against the strict oracle, element-wise."""
+    the one `emg3d_sweep_plan` predicts from the shape and THIS device's CU count (plan and launch come from the same value,
+    csrc/sweep_plan.hpp); (b) one colour-ordered sweep per direction against the strict oracle, element-wise."""
     import emg3d_amd as em
     from types import SimpleNamespace
     from emg3d_amd import _lib
@@ -650,7 +650,7 @@ def test_512_one_sweep_vs_oracle(oracle):
 @pytest.mark.parametrize("nz,expect", [(704, "k_line_sweep_thm"), (768, "k_line_sweep_rp")])
 def test_factor_offset_boundary_selects_the_right_kernel(oracle, nz, expect):
     """The two-sided kernel forms its factor offsets in 32 bits: the whole factor of a direction must stay below 4 GiB
-    (MG::twist_ok).  160 x 160 x 704 (z-lines: 25 281 lines x 704 blocks x 240 B = 4.27e9 B) is just inside, 160 x 160 x 768
+    (sweep_twist_ok, csrc/sweep_plan.hpp).  160 x 160 x 704 (z-lines: 25 281 lines x 704 blocks x 240 B = 4.27e9 B) is just inside, 160 x 160 x 768
     (4.66e9 B) beyond -- there the one-sided k_line_sweep_rp (64-bit block pointer, 32-bit offsets within a block record)
     must serve.  Selected kernel by name, and the z-line sweep against the strict oracle on both sides."""
     import emg3d_amd as em

@@ -697,3 +697,43 @@ def test_sweep_plan_thresholds_follow_the_device():
         assert a["kernel"].split("<")[0] == b["kernel"].split("<")[0] and a["factor_kind"] == b["factor_kind"]
     # ... the rounds do
     assert plan((128,) * 3, nsys=8)["rounds"] > plan((128,) * 3)["rounds"]
+
+
+def test_sweep_plan_replays_the_recorded_selection(monkeypatch):
+    """The launch selection is ONE function (csrc/sweep_plan.hpp) that the handle and `emg3d_sweep_plan` share; what it answers is
+    pinned by a table recorded before that function was factored out of the cycle driver (tests/golden/make_sweep_plans.py: a
+    seeded sample of a few hundred of its 1.87 M plans -- every kernel family and every lines-per-wave value it runs at in f64 and
+    c128, each with every direction, ordering, batch size and device size (256 / 128 CUs) it occurs with; for each of the lab
+    build's knobs rows that the knob changes): every field of every row, product and lab library.  The generator's --dump writes the
+    whole table for comparing two builds."""
+    import json
+    import os
+    from conftest import GOLDEN
+    from emg3d_amd import _lib
+    with open(os.path.join(GOLDEN, "sweep_plans.json")) as fh:
+        fix = json.load(fh)
+    assert fix["columns"] == ["nx", "ny", "nz", "direction", "dtype", "ordering", "nsys", "cu_count", "kernel", "lines_per_colour",
+                              "lines_per_wave", "rounds", "factor_kind", "split", "big_offsets"]
+    for k in [k for k in os.environ if k.startswith("EMG3D_") and k != "EMG3D_HIP_LIB"]:
+        monkeypatch.delenv(k)
+    prev = _lib.use(None)
+    n, kernels = 0, set()
+    try:
+        for group in fix["groups"]:
+            _lib.use(_lib.LAB_PATH if group["library"] == "lab" else None)
+            with monkeypatch.context() as mp:
+                for k, v in group["env"].items():
+                    mp.setenv(k, v)       # (read per call)
+                for nx, ny, nz, d, dt, ordering, nsys, cu, *want in group["rows"]:
+                    p = _lib.sweep_plan((nx, ny, nz), d, dtype=np.complex128 if dt == "c128" else np.float64, ordering=ordering,
+                                        nsys=nsys, cu_count=cu)
+                    got = [p["kernel"], p["lines_per_colour"], p["lines_per_wave"], p["rounds"], p["factor_kind"], int(p["split"]),
+                           int(p["big_offsets"])]
+                    assert got == want, (group["library"], group["env"], (nx, ny, nz), d, dt, ordering, nsys, cu, got, want)
+                    n += 1
+                    kernels.add(p["kernel"].split("<")[0])
+    finally:
+        _lib.use(prev)
+    assert n >= 400
+    assert kernels == {"k_line_sweep", "k_line_sweep_rp", "k_line_sweep_qc", "k_line_sweep_qc_big", "k_line_sweep_thm", "k_line_sweep_tha",
+                       "k_line_sweep_qpl", "k_line_sweep_qpl_chain"}
