@@ -539,6 +539,99 @@ static int sweep_plan_impl(i64 nx, i64 ny, i64 nz, int dir, int order, int nsys,
     return 0;
 }
 
+template <class T>
+static int jvec_source_impl(MG<T>* m, int efield_vec, double smu0_re, double smu0_im, const double* vx, const double* vy,
+                            const double* vz) {
+    if (sizeof(T) == 8 && smu0_im != 0.0) return -2;
+    HIP_TRY(hipSetDevice(m->device));
+    Level<T>& L = *m->lv0;
+    const T* fwd = m->vec(efield_vec);
+    if (!fwd || efield_vec < 0) return -2;             // a workspace vector: the source of the selected system is written
+    // the perturbations (up to 3 nC doubles) are staged in the residual buffer (3 nC * 8 < nE * sizeof(T)); the same host
+    // array for several directions is uploaded once
+    double* stage = reinterpret_cast<double*>(L.r);
+    const double* hv[3] = {vx, vy, vz};
+    const double* dv[3] = {nullptr, nullptr, nullptr};
+    const i64 n = L.nCells;
+    int used = 0;
+    for (int c = 0; c < 3; ++c) {
+        if (!hv[c]) continue;
+        for (int q = 0; q < c; ++q) if (hv[q] == hv[c]) dv[c] = dv[q];
+        if (dv[c]) continue;
+        double* d = stage + (i64)used++ * n;
+        HIP_TRY(hipMemcpyAsync(d, hv[c], (size_t)n * sizeof(double), hipMemcpyHostToDevice, m->stream));
+        dv[c] = d;
+    }
+    T* s = m->sel_s();
+    if (m->broken) return (int)hipErrorOutOfMemory;
+    hipLaunchKernelGGL(k_jvec_source<T>, dim3((unsigned)((L.nE + 255) / 256)), dim3(256), 0, m->stream, L.nC[0], L.nC[1], L.nC[2],
+                       L.fl, fwd, smu0_re, smu0_im, dv[0], dv[1], dv[2], (const double*)L.h[0], (const double*)L.h[1],
+                       (const double*)L.h[2], s, L.nE);
+    m->source_changed();
+    m->lv0->s_dense = true;         // (every line carries a source: no point in scanning it for zeros)
+    m->check_launch();
+    return finish(m);               // (synchronises: the host arrays have been read)
+}
+
+// one output (gy == gz == NULL: grad = (g_x + g_y) + g_z) or the three components
+static int gradient_impl(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, double* gx, double* gy, double* gz) {
+    const bool split = gy != nullptr;
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        Level<T>& L = *m->lv0;
+        const T* fwd = m->vec(efield_vec);
+        if (!fwd || efield_vec == -2) return -2;           // the forward field must be a saved copy, not the live field
+        // the gradient (nC doubles, or 3 nC) is staged in the residual buffer (3 nC * 8 < nE * sizeof(T))
+        double* dg = reinterpret_cast<double*>(L.r);
+        const i64 n = L.nCells;
+        const unsigned blocks = (unsigned)((n + 255) / 256);
+        const T* bwd = m->sel_e();
+        if (m->broken) return (int)hipErrorOutOfMemory;
+        if (split)
+            hipLaunchKernelGGL((k_gradient<T, true>), dim3(blocks), dim3(256), 0, m->stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd, bwd,
+                               smu0_re, smu0_im, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], dg, dg + n, dg + 2 * n);
+        else
+            hipLaunchKernelGGL((k_gradient<T, false>), dim3(blocks), dim3(256), 0, m->stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd, bwd,
+                               smu0_re, smu0_im, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], dg, (double*)nullptr,
+                               (double*)nullptr);
+        m->check_launch();
+        HIP_TRY(m->d2h(gx, dg, (size_t)n * sizeof(double)));
+        if (split) {
+            HIP_TRY(m->d2h(gy, dg + n, (size_t)n * sizeof(double)));
+            HIP_TRY(m->d2h(gz, dg + 2 * n, (size_t)n * sizeof(double)));
+        }
+        return finish(m);
+    });
+}
+
+template <class T>
+static int cells2edges_impl(const i64 nC[3], const void* const v[3], const double* vol, void* const out[3]) {
+    const i64 nE = n_edges(nC), n = nC[0] * nC[1] * nC[2];
+    const FieldLayout fl = ref_field_layout(nC);
+    char* base = nullptr;
+    DEV_ALLOC(base, (size_t)(nE + 3 * n) * sizeof(T) + (size_t)n * 8);
+    T* df = (T*)base; T* dv = df + nE; double* dvol = (double*)(dv + 3 * n);
+    i64 len[3];
+    for (int c = 0; c < 3; ++c) len[c] = (c < 2 ? fl.off[c + 1] : nE) - fl.off[c];
+    C2EArgs<T> a;
+    for (int c = 0; c < 3; ++c) {
+        a.nC[c] = nC[c];
+        a.v[c] = nullptr;
+        if (!v[c]) continue;
+        HIP_TRY(hipMemcpy(dv + (size_t)c * n, v[c], (size_t)n * sizeof(T), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(df + fl.off[c], out[c], (size_t)len[c] * sizeof(T), hipMemcpyHostToDevice));
+        a.v[c] = dv + (size_t)c * n;
+    }
+    HIP_TRY(hipMemcpy(dvol, vol, (size_t)n * 8, hipMemcpyHostToDevice));
+    a.fl = fl; a.vol = dvol; a.out = df;
+    hipLaunchKernelGGL(k_cells2edges<T>, dim3((unsigned)((nE + 255) / 256)), dim3(256), 0, 0, a, nE);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    for (int c = 0; c < 3; ++c)
+        if (v[c]) HIP_TRY(hipMemcpy(out[c], df + fl.off[c], (size_t)len[c] * sizeof(T), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" {
 
 int emg3d_hip_version(void) { return EMG3D_HIP_VERSION; }
@@ -839,20 +932,61 @@ int emg3d_interp3d_grid(int dtype, int64_t nx, int64_t ny, int64_t nz, const dou
 
 int emg3d_mg_gradient(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, double* grad) {
     if (!mg || !grad) return -2;
+    return gradient_impl(mg, efield_vec, smu0_re, smu0_im, grad, nullptr, nullptr);
+}
+
+int emg3d_mg_gradient3(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, double* grad_x, double* grad_y,
+                       double* grad_z) {
+    if (!mg || !grad_x || !grad_y || !grad_z) return -2;
+    return gradient_impl(mg, efield_vec, smu0_re, smu0_im, grad_x, grad_y, grad_z);
+}
+
+int emg3d_mg_jvec_source(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, const double* vx, const double* vy,
+                         const double* vz) {
+    if (!mg) return -2;
+    DISPATCH(mg, return jvec_source_impl<T>(m, efield_vec, smu0_re, smu0_im, vx, vy, vz));
+}
+
+int emg3d_mg_set_receiver_adjoint(emg3d_mg_t* mg, int64_t n, const double* xyz, const double* factors, const void* w,
+                                  int accumulate) {
+    if (!mg || n < 1 || !xyz || !factors || !w) return -2;
     DISPATCH(mg, {
         HIP_TRY(hipSetDevice(m->device));
-        Level<T>& L = *m->lv0;
-        const T* fwd = m->vec(efield_vec);
-        if (!fwd || efield_vec == -2) return -2;           // the forward field must be a saved copy, not the live field
-        // the gradient (nC doubles) is staged in the residual buffer (nC * 8 < nE * sizeof(T))
-        double* dg = reinterpret_cast<double*>(L.r);
-        const unsigned blocks = (unsigned)((L.nCells + 255) / 256);
-        hipLaunchKernelGGL(k_gradient<T>, dim3(blocks), dim3(256), 0, m->stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd,
-                           (const T*)m->sel_e(), smu0_re, smu0_im, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], dg);
-        m->check_launch();
-        HIP_TRY(m->d2h(grad, dg, (size_t)L.nCells * sizeof(double)));
-        return finish(m);
+        auto& L = *m->lv0;
+        if (L.nC[0] < 3 || L.nC[1] < 3 || L.nC[2] < 3) return -2;
+        if (!accumulate) HIP_TRY(hipMemsetAsync(m->sel_s(), 0, (size_t)L.nE * sizeof(T), m->stream));
+        m->source_changed();
+        RcvComp<T> comp[3];
+        receiver_components<T>(L.nodes, L.centers, L.nC, true, m->sel_s(), comp);
+        const int rc = receiver_adjoint_device<T>(m->stream, comp, L.fl, n, xyz, factors, (const T*)w, m->sel_s());
+        const int st = finish(m);
+        return rc ? rc : st;
     });
+}
+
+int emg3d_mg_get_receiver_response_linear(emg3d_mg_t* mg, int64_t n, const double* xyz, const double* factors, void* resp) {
+    if (!mg || n < 1 || !xyz || !factors || !resp) return -2;
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        auto& L = *m->lv0;
+        if (L.nC[0] < 3 || L.nC[1] < 3 || L.nC[2] < 3) return -2;
+        const T* fdev = m->sel_e();
+        if (m->broken) return (int)hipErrorOutOfMemory;
+        RcvComp<T> comp[3];
+        receiver_components<T>(L.nodes, L.centers, L.nC, true, fdev, comp);
+        const int rc = receiver_response_device<T>(m->stream, comp, n, xyz, factors, (T*)nullptr, (T*)resp, 0);
+        const int st = finish(m);
+        return rc ? rc : st;
+    });
+}
+
+int emg3d_cells2edges(int dtype, int64_t nx, int64_t ny, int64_t nz, const void* vx, const void* vy, const void* vz,
+                      const double* vol, void* out_x, void* out_y, void* out_z) {
+    if (nx < 1 || ny < 1 || nz < 1 || !vol || (vx && !out_x) || (vy && !out_y) || (vz && !out_z)) return -2;
+    const i64 nC[3] = {nx, ny, nz};
+    const void* const v[3] = {vx, vy, vz};
+    void* const out[3] = {out_x, out_y, out_z};
+    return dtype ? cells2edges_impl<c128>(nC, v, vol, out) : cells2edges_impl<double>(nC, v, vol, out);
 }
 
 int emg3d_mg_set_sfield_dipole(emg3d_mg_t* mg, const double* src6, const double* scale6, int decimals, int accumulate,

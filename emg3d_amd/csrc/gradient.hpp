@@ -63,10 +63,11 @@ __device__ __forceinline__ double grad_prod(c128 b, c128 e, double sr, double si
     return -(be.re * sr - be.im * si);
 }
 
-// grad[cell] = sum_c edges2cellaverages_c( -Re(b * e * smu0) ), vol = (hx*hy)*hz (meshes cell_volumes)
-template <class T>
+// grad[cell] = sum_c edges2cellaverages_c( -Re(b * e * smu0) ), vol = (hx*hy)*hz (meshes cell_volumes).
+// SPLIT: the three components go to g0, g1, g2 instead (emg3d_mg_gradient3); their sum (g0 + g1) + g2 is the one-output result.
+template <class T, bool SPLIT>
 __global__ void k_gradient(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* e, const T* b, double sr, double si,
-                           const double* h0, const double* h1, const double* h2, double* grad) {
+                           const double* h0, const double* h1, const double* h2, double* g0, double* g1, double* g2) {
     const i64 nC[3] = {n0, n1, n2};
     const i64 n = n0 * n1 * n2;
     const i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -84,5 +85,95 @@ __global__ void k_gradient(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* e, c
             return grad_prod(bc[o], ec[o], sr, si);
         });
     }
-    grad[idx] = (g[0] + g[1]) + g[2];          // grad_x + grad_y + grad_z, optimize.py:199
+    if (SPLIT) { g0[idx] = g[0]; g1[idx] = g[1]; g2[idx] = g[2]; }
+    else g0[idx] = (g[0] + g[1]) + g[2];          // grad_x + grad_y + grad_z, optimize.py:199
+}
+
+// ---- the transpose: cells -> edges (J v of optimize.Jacobian) ---------------------------------------------------------------
+// Gather form again: one thread per EDGE sums the (up to) four cells around it, in ascending cell order -- deterministic, no atomics,
+// and never a scatter from the cells.  e2c_component above adds edge (e1, e2) (transverse indices) of component c into the cells
+// (m1 | p1, m2 | p2), m = max(e - 1, 0), p = min(e, n - 1): the four statements of the reference, which hit the SAME cell twice (four
+// times on a grid corner line) for a boundary edge.  Its transpose therefore gives a boundary edge its cell two / four times.
+// W(j0, j1, j2) returns the cell's weight (vol * v); the result is sum W / 4.
+template <class V, class W>
+__device__ __forceinline__ V c2e_gather(int c, const i64 e[3], const i64 nC[3], W w) {
+    const int t1 = (c == 0) ? 1 : 0, t2 = (c == 2) ? 1 : 2;
+    const i64 e1 = e[t1], e2 = e[t2];
+    const i64 a1[2] = {e1 > 0 ? e1 - 1 : 0, e1 < nC[t1] - 1 ? e1 : nC[t1] - 1};        // m1, p1
+    const i64 a2[2] = {e2 > 0 ? e2 - 1 : 0, e2 < nC[t2] - 1 ? e2 : nC[t2] - 1};        // m2, p2
+    V acc = V();
+#pragma unroll
+    for (int q2 = 0; q2 < 2; ++q2)
+#pragma unroll
+        for (int q1 = 0; q1 < 2; ++q1) {          // (m1, m2), (p1, m2), (m1, p2), (p1, p2)
+            i64 j[3];
+            j[c] = e[c]; j[t1] = a1[q1]; j[t2] = a2[q2];
+            acc += w(j[0], j[1], j[2]) / 4.0;
+        }
+    return acc;
+}
+
+// Edge `idx` of [fx|fy|fz] in the reference numbering (x fastest inside a component): component and (i0, i1, i2).
+__device__ __forceinline__ int edge_of(i64 idx, const i64 nC[3], i64 e[3]) {
+    const i64 nx = nC[0] * (nC[1] + 1) * (nC[2] + 1), ny = (nC[0] + 1) * nC[1] * (nC[2] + 1);
+    const int c = idx < nx ? 0 : (idx < nx + ny ? 1 : 2);
+    const i64 lin = idx - (c == 0 ? 0 : (c == 1 ? nx : nx + ny));
+    const i64 d0 = (c == 0) ? nC[0] : nC[0] + 1, d1 = (c == 1) ? nC[1] : nC[1] + 1, d2 = (c == 2) ? nC[2] : nC[2] + 1;
+    unlin3(lin, d0, d1, d2, e[0], e[1], e[2]);
+    return c;
+}
+
+// maps.cellaverages2edges: out_c[edge] += sum over the statements of edges2cellaverages that read this edge of vol * v_c / 4 --
+// the exact transpose of k_edges2cell (boundary multiplicities included).  v[c] == nullptr: that component is left alone.
+template <class T>
+struct C2EArgs {
+    i64 nC[3];
+    FieldLayout fl;
+    const T* v[3];           // F-ordered (nx, ny, nz) cell arrays
+    const double* vol;
+    T* out;                  // [fx|fy|fz] (+=)
+};
+
+template <class T>
+__global__ void k_cells2edges(C2EArgs<T> a, i64 nE) {
+    const i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= nE) return;
+    i64 e[3];
+    const int c = edge_of(idx, a.nC, e);
+    const T* v = a.v[c];
+    if (!v) return;
+    const double* vol = a.vol;
+    const i64 n0 = a.nC[0], n01 = a.nC[0] * a.nC[1];
+    const i64 o = a.fl.off[c] + e[0] * a.fl.st[c][0] + e[1] * a.fl.st[c][1] + e[2] * a.fl.st[c][2];
+    a.out[o] += c2e_gather<T>(c, e, a.nC, [&](i64 j0, i64 j1, i64 j2) {
+        const i64 q = j0 + j1 * n0 + j2 * n01;
+        return vol[q] * v[q];
+    });
+}
+
+__device__ __forceinline__ double jvec_prod(double cv, double e, double sr, double) { return (sr * cv) * e; }
+__device__ __forceinline__ c128 jvec_prod(double cv, c128 e, double sr, double si) { return mk(sr * cv, si * cv) * e; }
+
+// Right-hand side of the J v solve: s[edge] = s mu_0 * C(v)[edge] * E[edge], C(v) = 1/4 sum of V_c v_c over the four cells around
+// the edge with that component's perturbation (v[c] == nullptr: none, the component's source is zero); PEC boundary edges are written
+// as exact zeros.  V = (hx*hy)*hz as in k_gradient.  Per edge 16 B of E are read and 16 B written (c128); the cell reads hit the cache.
+template <class T>
+__global__ void k_jvec_source(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* efield, double sr, double si, const double* v0,
+                              const double* v1, const double* v2, const double* h0, const double* h1, const double* h2, T* s, i64 nE) {
+    const i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= nE) return;
+    const i64 nC[3] = {n0, n1, n2};
+    i64 e[3];
+    const int c = edge_of(idx, nC, e);
+    const int t1 = (c == 0) ? 1 : 0, t2 = (c == 2) ? 1 : 2;
+    const i64 o = fl.off[c] + e[0] * fl.st[c][0] + e[1] * fl.st[c][1] + e[2] * fl.st[c][2];
+    const double* v = c == 0 ? v0 : (c == 1 ? v1 : v2);
+    T val = Zero<T>::v();
+    if (v && e[t1] > 0 && e[t1] < nC[t1] && e[t2] > 0 && e[t2] < nC[t2]) {
+        const double cv = c2e_gather<double>(c, e, nC, [&](i64 j0, i64 j1, i64 j2) {
+            return ((h0[j0] * h1[j1]) * h2[j2]) * v[j0 + n0 * (j1 + n1 * j2)];
+        });
+        val = jvec_prod(cv, efield[o], sr, si);
+    }
+    s[o] = val;
 }

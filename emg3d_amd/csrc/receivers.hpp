@@ -372,10 +372,11 @@ int interp3d_device(hipStream_t st, const T* values, const i64 n[3], i64 off, i6
 
 // fields.get_receiver_response (fields.py:733-817) of three device-resident components: resp_host[n] =
 // sum_c fac[c][r] * interp3d(points_c[1:-1], comp_c[1:-1,1:-1,1:-1], xyz, 'cubic', 0.0, 'constant', nan); a component
-// whose factors are all <= 1e-10 in magnitude is skipped (fields.py:810).
+// whose factors are all <= 1e-10 in magnitude is skipped (fields.py:810).  method 0: trilinear interpolation on the same trimmed
+// points, NaN outside (the receiver operator whose transpose receiver_adjoint_device applies); scratch is not used then.
 template <class T>
 int receiver_response_device(hipStream_t st, const RcvComp<T> comp[3], i64 npts, const double* xyz, const double* fac,
-                             T* scratch, T* resp_host) {
+                             T* scratch, T* resp_host, int method = 1) {
     if (npts < 1) return -2;
     T* dresp = nullptr;
     DEV_ALLOC(dresp, (size_t)npts * sizeof(T));
@@ -395,7 +396,7 @@ int receiver_response_device(hipStream_t st, const RcvComp<T> comp[3], i64 npts,
         }
         if (rc) break;
         const i64 off = 1 + C.n[0] + C.n[0] * C.n[1];
-        rc = interp3d_device<T>(st, C.dev, m, off, 1, C.n[0], C.n[0] * C.n[1], p, npts, xyz, 1, true, 0.0, NAN,
+        rc = interp3d_device<T>(st, C.dev, m, off, 1, C.n[0], C.n[0] * C.n[1], p, npts, xyz, method, true, method ? 0.0 : NAN, NAN,
                                 fac + c * npts, scratch, dresp);
     }
     if (rc == 0) {
@@ -404,4 +405,98 @@ int receiver_response_device(hipStream_t st, const RcvComp<T> comp[3], i64 npts,
         if (e != hipSuccess) rc = (int)e;
     }
         return rc;
+}
+
+// ---- transpose of the linear receiver operator -------------------------------------------------------------------------------
+// s[edge] (+)= sum over the receivers r that touch the edge of weight * w[r]: thread per TOUCHED edge, contributions in the fixed
+// order of the host's table (receiver, then corner) -- deterministic although receivers share edges, no atomics.
+template <class T>
+__global__ void k_receiver_adjoint(T* s, const i64* edges, const int* ptr, const int* rcv, const double* wgt, const T* w, i64 nedges) {
+    const i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nedges) return;
+    T acc = Zero<T>::v();
+    for (int q = ptr[k]; q < ptr[k + 1]; ++q) acc += w[rcv[q]] * wgt[q];
+    s[edges[k]] += acc;
+}
+
+// s (+)= P^T w, P the operator of receiver_response_device(method 0) on the electric components comp (only n / pts are used),
+// fl the layout of s.  Host: 8 weights per receiver and active component, O(npts log npts); CSR by edge.  A receiver outside the
+// trimmed points of an active component (its datum is NaN) contributes nothing.
+template <class T>
+int receiver_adjoint_device(hipStream_t st, const RcvComp<T> comp[3], const FieldLayout& fl, i64 npts, const double* xyz,
+                            const double* fac, const T* w_host, T* s) {
+    if (npts < 1) return -2;
+    struct Entry { i64 edge; int r; double w; };
+    std::vector<Entry> ent;
+    std::vector<char> inside((size_t)npts, 1);
+    bool active[3];
+    for (int c = 0; c < 3; ++c) {
+        active[c] = false;
+        for (i64 r = 0; r < npts; ++r) if (std::fabs(fac[c * npts + r]) > 1e-10) { active[c] = true; break; }
+        if (!active[c]) continue;
+        for (int a = 0; a < 3; ++a) {
+            if (comp[c].n[a] < 3) return -2;
+            const double* g = comp[c].pts[a].data() + 1;
+            const i64 m = comp[c].n[a] - 2;
+            for (i64 r = 0; r < npts; ++r) if (!(xyz[a * npts + r] >= g[0] && xyz[a * npts + r] <= g[m - 1])) inside[r] = 0;
+        }
+    }
+    for (int c = 0; c < 3; ++c) {
+        if (!active[c]) continue;
+        for (i64 r = 0; r < npts; ++r) {
+            if (!inside[r]) continue;
+            i64 ii[3];
+            double tt[3];
+            for (int a = 0; a < 3; ++a) {           // as interp3d_device, method 0
+                const double* g = comp[c].pts[a].data() + 1;
+                const i64 m = comp[c].n[a] - 2;
+                const double v = xyz[a * npts + r];
+                i64 i = (i64)(std::lower_bound(g, g + m, v) - g) - 1;
+                if (i < 0) i = 0;
+                if (i > m - 2) i = m - 2;
+                if (m == 1) { ii[a] = 1; tt[a] = 0.0; continue; }
+                ii[a] = i + 1;
+                tt[a] = (v - g[i]) / (g[i + 1] - g[i]);
+            }
+            for (int a0 = 0; a0 < 2; ++a0)
+                for (int a1 = 0; a1 < 2; ++a1)
+                    for (int a2 = 0; a2 < 2; ++a2) {
+                        const double wg = (a0 ? tt[0] : 1 - tt[0]) * (a1 ? tt[1] : 1 - tt[1]) * (a2 ? tt[2] : 1 - tt[2]);
+                        // (an axis with one trimmed point: both corners are that point, weights 1 and 0)
+                        const i64 i0 = ii[0] + (comp[c].n[0] == 3 ? 0 : a0), i1 = ii[1] + (comp[c].n[1] == 3 ? 0 : a1),
+                                  i2 = ii[2] + (comp[c].n[2] == 3 ? 0 : a2);
+                        ent.push_back({fl.off[c] + i0 * fl.st[c][0] + i1 * fl.st[c][1] + i2 * fl.st[c][2], (int)r,
+                                       fac[c * npts + r] * wg});
+                    }
+        }
+    }
+    if (ent.empty()) return 0;
+    std::stable_sort(ent.begin(), ent.end(), [](const Entry& a, const Entry& b) { return a.edge < b.edge; });
+    std::vector<i64> edges;
+    std::vector<int> ptr, rcv(ent.size());
+    std::vector<double> wgt(ent.size());
+    for (size_t q = 0; q < ent.size(); ++q) {
+        if (q == 0 || ent[q].edge != ent[q - 1].edge) { edges.push_back(ent[q].edge); ptr.push_back((int)q); }
+        rcv[q] = ent[q].r; wgt[q] = ent[q].w;
+    }
+    ptr.push_back((int)ent.size());
+    const size_t ne = edges.size(), nq = ent.size();
+    char* base = nullptr;
+    DEV_ALLOC(base, ne * 8 + nq * 8 + (size_t)npts * sizeof(T) + (ne + 1 + nq) * 4 + 64);
+    i64* dedges = (i64*)base;
+    double* dwgt = (double*)(dedges + ne);
+    T* dw = (T*)(dwgt + nq);
+    int* dptr = (int*)(dw + npts);
+    int* drcv = dptr + ne + 1;
+    HIP_TRY(hipMemcpyAsync(dedges, edges.data(), ne * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dwgt, wgt.data(), nq * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dw, w_host, (size_t)npts * sizeof(T), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dptr, ptr.data(), (ne + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(drcv, rcv.data(), nq * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_receiver_adjoint<T>, dim3((unsigned)((ne + EMG_RCV_BLOCK - 1) / EMG_RCV_BLOCK)), dim3(EMG_RCV_BLOCK), 0, st, s,
+                       (const i64*)dedges, (const int*)dptr, (const int*)drcv, (const double*)dwgt, (const T*)dw, (i64)ne);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);             // (the host tables and the device block go out of scope)
+    if (e != hipSuccess) { fprintf(stderr, "[emg3d_hip] receiver adjoint: %s\n", hipGetErrorString(e)); return (int)e; }
+    return 0;
 }

@@ -456,12 +456,39 @@ def get_receiver(grid, values, coordinates, method='cubic', extrapolate=False):
     return out if values.size == grid.nC else EMArray(out)
 
 
-def get_receiver_response(grid, field, rec):
+def _linear_receiver_response(grid, f, electric, dtype, n, xyz, fac):
+    """``get_receiver_response(method='linear')``: ``maps.interp3d(..., 'linear', nan, ...)`` of every active component on its
+    trimmed points (on the device), weighted with the rotation factors."""
+    from . import maps
+    nx, ny, nz = (int(v) for v in grid.vnC)
+    nodes = (grid.nodes_x, grid.nodes_y, grid.nodes_z)
+    centers = (grid.cell_centers_x, grid.cell_centers_y, grid.cell_centers_z)
+    out = np.zeros(n, dtype=dtype)
+    o = 0
+    for c in range(3):
+        cell = [(a == c) if electric else (a != c) for a in range(3)]
+        shp = tuple((nx, ny, nz)[a] + (0 if cell[a] else 1) for a in range(3))
+        size = int(np.prod(shp))
+        comp = f[o:o + size].reshape(shp, order='F')
+        o += size
+        if not np.any(np.abs(fac[c]) > 1e-10):
+            continue
+        pts = tuple((centers[a] if cell[a] else nodes[a])[1:-1] for a in range(3))
+        out += fac[c] * maps.interp3d(pts, comp[1:-1, 1:-1, 1:-1], tuple(xyz), 'linear', np.nan, 'constant', np.nan)
+    return out
+
+
+def get_receiver_response(grid, field, rec, method='cubic'):
     """Field (response) at point receivers ``rec = (x, y, z, azimuth, dip)`` -- the interface of the reference's
     ``fields.get_receiver_response`` (emg3d/fields.py:733-817): cubic-spline interpolation of every component
     on its trimmed staggered grid (first and last value per direction dropped), NaN outside, components
     weighted with the rotation factors.  Evaluated on the device (``emg3d_get_receiver_response``); for a
-    field that already lives in HBM use ``DeviceMG.get_receiver_response`` (no field transfer)."""
+    field that already lives in HBM use ``DeviceMG.get_receiver_response`` (no field transfer).
+
+    ``method='linear'`` (not in the reference v0.17.0, which always interpolates with cubic splines): trilinear interpolation on
+    the same trimmed points, NaN outside -- the receiver operator whose exact transpose ``optimize.Jacobian`` applies."""
+    if method not in ('cubic', 'linear'):
+        raise ValueError(f"`method` must be 'cubic' or 'linear'; provided: {method!r}.")
     from . import _lib
     if np.ndim(np.asarray(field)) == 3:
         raise ValueError("`field` must be a `Field`-instance, not a\n"
@@ -472,6 +499,8 @@ def get_receiver_response(grid, field, rec):
     f = np.ascontiguousarray(np.asarray(field), dtype=dtype)
     nx, ny, nz = (int(v) for v in grid.vnC)
     electric = bool(getattr(field, 'is_electric', f.size == grid.nE))
+    if method == 'linear':
+        return _linear_receiver_response(grid, f, electric, dtype, n, xyz, fac)
     hx, hy, hz = (np.ascontiguousarray(h, dtype=np.float64) for h in grid.h)
     origin = np.ascontiguousarray(grid.origin, dtype=np.float64)
     out = np.empty(n, dtype=dtype)

@@ -243,3 +243,36 @@ def edges2cellaverages(ex, ey, ez, vol, out_x, out_y, out_z):
                                             *(_lib.ptr(o) for o in outs)), "emg3d_edges2cellaverages")
     for o, r in zip((out_x, out_y, out_z), outs):
         o[...] = r.reshape((nx, ny, nz), order='F') if np.iscomplexobj(o) or dtype == np.float64 else r.reshape((nx, ny, nz), order='F').real
+
+
+def cellaverages2edges(vx, vy, vz, vol, out_x, out_y, out_z):
+    """The exact transpose of :func:`edges2cellaverages`: cell values ``vx, vy, vz`` (shape ``vol.shape``; ``None`` skips a
+    component) to the edges, ``out_c[edge] += sum vol * v_c / 4`` over the statements of ``edges2cellaverages`` that read the
+    edge -- an interior edge takes its four cells once, a boundary edge its cells two or four times, as the reference's kernel
+    (emg3d/maps.py:578-630) counts them.  ADDED into ``out_x/y/z`` (the components of a field: ``fx, fy, fz`` views) in place;
+    ``sum(e2c(f) * v) == sum(f * c2e(v))``.  Evaluated on the device (``emg3d_cells2edges``: one thread per edge gathers its
+    cells).  The reference has no such function (its adjoint does not need one); ``optimize.Jacobian.jvec`` builds its
+    right-hand side with the same gather."""
+    lib = _lib.load()
+    arrs = [a for a in (vx, vy, vz, out_x, out_y, out_z) if a is not None]
+    dtype = np.dtype(np.complex128 if any(np.iscomplexobj(a) for a in arrs) else np.float64)
+    nx, ny, nz = (int(v) for v in np.shape(vol))
+    shapes = ((nx, ny + 1, nz + 1), (nx + 1, ny, nz + 1), (nx + 1, ny + 1, nz))
+    vl = np.ascontiguousarray(np.asarray(vol, dtype=np.float64).ravel(order='F'))
+    vs, outs = [], []
+    for v, o, shp in zip((vx, vy, vz), (out_x, out_y, out_z), shapes):
+        if v is None:
+            vs.append(None); outs.append(None)
+            continue
+        if np.shape(v) != (nx, ny, nz) or o is None or np.shape(o) != shp:
+            raise ValueError(f"cellaverages2edges: cell arrays must have shape {(nx, ny, nz)}, the outputs {shapes}.")
+        if dtype.kind == 'c' and not np.iscomplexobj(o):
+            raise TypeError("cellaverages2edges: complex cell values need complex outputs.")
+        vs.append(np.ascontiguousarray(np.asarray(v, dtype=dtype).ravel(order='F')))
+        outs.append(np.ascontiguousarray(np.asarray(o, dtype=dtype).ravel(order='F')))
+    none = ctypes.c_void_p(None)
+    _lib.check(lib.emg3d_cells2edges(_lib.dtype_code(dtype), nx, ny, nz, *(none if v is None else _lib.ptr(v) for v in vs),
+                                     _lib.ptr(vl), *(none if o is None else _lib.ptr(o) for o in outs)), "emg3d_cells2edges")
+    for o, r, shp in zip((out_x, out_y, out_z), outs, shapes):
+        if r is not None:
+            o[...] = r.reshape(shp, order='F')

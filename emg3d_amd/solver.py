@@ -172,12 +172,21 @@ class DeviceMG:
                    "emg3d_mg_get_hfield")
         return fields._h_from_vector(out, shapes)
 
-    def get_receiver_response(self, rec, magnetic=False, smu0=None, mu_r=False):
+    def get_receiver_response(self, rec, magnetic=False, smu0=None, mu_r=False, method='cubic'):
         """``fields.get_receiver_response`` (reference fields.py:733-817) of the DEVICE-RESIDENT electric field
         (``magnetic=True``: of ``H = get_h_field(E)``, formed on the device; needs ``smu0``): spline
-        prefilter and evaluation run on the device, 16 bytes per receiver cross PCIe."""
+        prefilter and evaluation run on the device, 16 bytes per receiver cross PCIe.  ``method='linear'`` (electric only):
+        trilinear interpolation on the same trimmed points, NaN outside (``emg3d_mg_get_receiver_response_linear``)."""
+        if method not in ('cubic', 'linear'):
+            raise ValueError(f"`method` must be 'cubic' or 'linear'; provided: {method!r}.")
         n, xyz, fac = fields._receiver_args(rec)
         out = np.empty(n, dtype=self.dtype)
+        if method == 'linear':
+            if magnetic:
+                raise NotImplementedError("Linear receivers are implemented for the electric field only.")
+            _lib.check(self._lib.emg3d_mg_get_receiver_response_linear(self._h, n, _lib.ptr(xyz), _lib.ptr(fac), _lib.ptr(out)),
+                       "emg3d_mg_get_receiver_response_linear")
+            return out
         a = complex(smu0) if smu0 is not None else 0j
         if magnetic and smu0 is None:
             raise ValueError("magnetic receivers need `smu0` (field.smu0).")
@@ -186,14 +195,45 @@ class DeviceMG:
                    "emg3d_mg_get_receiver_response")
         return out
 
-    def gradient(self, efield_vec, smu0):
+    def gradient(self, efield_vec, smu0, components=False):
         """Adjoint-state gradient of one (source, frequency) pair on this grid (reference optimize.py:176-199):
-        the handle's field = back-propagated field, workspace vector ``efield_vec`` = forward field."""
-        out = np.empty(self.nC, dtype=np.float64)
+        the handle's field = back-propagated field, workspace vector ``efield_vec`` = forward field.  ``components=True``:
+        the three terms ``(grad_x, grad_y, grad_z)`` whose sum ``(grad_x + grad_y) + grad_z`` is the default result."""
         a = complex(smu0)
+        if components:
+            outs = [np.empty(self.nC, dtype=np.float64) for _ in range(3)]
+            _lib.check(self._lib.emg3d_mg_gradient3(self._h, int(efield_vec), a.real, a.imag, *(_lib.ptr(o) for o in outs)),
+                       "emg3d_mg_gradient3")
+            return tuple(outs)
+        out = np.empty(self.nC, dtype=np.float64)
         _lib.check(self._lib.emg3d_mg_gradient(self._h, int(efield_vec), a.real, a.imag, _lib.ptr(out)),
                    "emg3d_mg_gradient")
         return out
+
+    def jvec_source(self, efield_vec, smu0, vx, vy, vz):
+        """Source of the selected system <- ``s mu_0 C(v) E`` (``emg3d_mg_jvec_source``): ``E`` = workspace vector
+        ``efield_vec``, ``vx, vy, vz`` conductivity perturbations per direction (``nC`` values, F-ordered; ``None``: none)."""
+        a = complex(smu0)
+        held, ptrs = [], []
+        for v in (vx, vy, vz):
+            if v is None:
+                ptrs.append(ctypes.c_void_p(None))
+                continue
+            same = [h for src, h in held if src is v]
+            arr = same[0] if same else np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel(order='F'))
+            if arr.size != self.nC:
+                raise ValueError(f"jvec_source: {arr.size} values for {self.nC} cells.")
+            held.append((v, arr))
+            ptrs.append(_lib.ptr(arr))
+        _lib.check(self._lib.emg3d_mg_jvec_source(self._h, int(efield_vec), a.real, a.imag, *ptrs), "emg3d_mg_jvec_source")
+
+    def set_receiver_adjoint(self, rec, w, accumulate=False):
+        """Source of the selected system (+)= ``P^T w``, ``P`` the linear receiver operator of
+        ``get_receiver_response(rec, method='linear')`` (``emg3d_mg_set_receiver_adjoint``); ``w``: one value per receiver."""
+        n, xyz, fac = fields._receiver_args(rec)
+        wv = np.ascontiguousarray(np.broadcast_to(np.asarray(w), (n,)), dtype=self.dtype)
+        _lib.check(self._lib.emg3d_mg_set_receiver_adjoint(self._h, n, _lib.ptr(xyz), _lib.ptr(fac), _lib.ptr(wv),
+                                                           int(bool(accumulate))), "emg3d_mg_set_receiver_adjoint")
 
     def set_source(self, src, smu0, strength=0, length=1.0, decimals=6, accumulate=False, electric=True):
         """Build the source field ``s mu_0 J_s`` of an electric source IN HBM (``fields.get_source_field``,
@@ -641,7 +681,7 @@ def _exact_parts(grid, model, smu0):
 
 
 def solve_sources(grid, model, sources, frequency, strength=0, cycle='F', semicoarsening=False,
-                  linerelaxation=False, verb=1, rec=None, download=True, electric=True, **kwargs):
+                  linerelaxation=False, verb=1, rec=None, download=True, electric=True, resident=None, **kwargs):
     """``[solve(grid, model, get_source_field(grid, src, frequency, strength), ...) for src in sources]`` as ONE
     batched multigrid iteration: the sources of a survey share grid, model and frequency (the reference loops over
     them one solve at a time, simulations.py:916-1015), hence the operator, the coarse models and the cached
@@ -653,12 +693,20 @@ def solve_sources(grid, model, sources, frequency, strength=0, cycle='F', semico
     of frequency ``frequency`` (uploaded).  Multigrid only (``sslsolver`` is not batched).  ``rec``: receivers
     ``(x, y, z, azimuth, dip)`` -- the responses are extracted on the device.  ``download=False``: no fields
     returned.  Returns ``(efields | None, info_dicts)`` and the responses ``(n_sources, n_rec)`` if ``rec``.
+
+    ``resident=n`` (with ``handle``; ``sources`` is ignored and may be None): the sources already sit in systems ``0 .. n-1`` of
+    the handle (``DeviceMG.select`` + ``set_source`` / ``jvec_source`` / ``set_receiver_adjoint``); nothing is uploaded.  The
+    handle may carry more systems than ``n``: the others are frozen for the call and keep their fields.
     """
     if kwargs.get('sslsolver'):
         raise ValueError("solve_sources batches multigrid cycles; use solve() per source with a Krylov solver.")
     kwargs.pop('sslsolver', None)
     device = kwargs.pop('device', 0)
     handle = kwargs.pop('handle', None)       # an existing DeviceMG of this grid / model / frequency: used, not closed
+    if resident is not None:
+        if handle is None:
+            raise ValueError("solve_sources: `resident` sources live on a `handle`.")
+        sources = [None] * int(resident)
     n = len(sources)
     if n < 1:
         raise ValueError("solve_sources: no sources.")
@@ -683,16 +731,21 @@ def solve_sources(grid, model, sources, frequency, strength=0, cycle='F', semico
             dev = DeviceMG(grid, models.VolumeModel(grid, model, proto), proto.dtype, device=device)
     try:
         dev.set_params(v0)
-        if dev.nsys != n:
+        if resident is not None and n > dev.nsys:
+            raise ValueError(f"solve_sources: {n} resident sources on a handle of {dev.nsys} systems.")
+        if resident is None and dev.nsys != n:
             dev.set_batch(n)
-        active = np.ones(n, dtype=np.int32)
+        active = np.ones(dev.nsys, dtype=np.int32)
+        active[n:] = 0                  # (resident sources on a wider handle: the other systems stay frozen)
         if handle is not None:
             dev.set_mask(active)
         for b, (src, var) in enumerate(zip(sources, vars_)):
             dev.select(b)
             if handle is not None:
                 dev.set_efield(None)
-            if host_fields[b] is not None:
+            if resident is not None:            # the system holds its source already
+                pass
+            elif host_fields[b] is not None:
                 dev.set_sfield(host_fields[b])
             else:
                 dev.set_source(src, proto.smu0, strength=strength, electric=electric)

@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 104
+#define EMG3D_HIP_ABI_VERSION 105
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -231,6 +231,38 @@ int emg3d_edges2cellaverages(int dtype, int64_t nx, int64_t ny, int64_t nz, cons
  * doubles, F-ordered.  (The reference then maps -grad to the model grid: emg3d_interp3d_grid, optimize.model_gradient.)
  * Overwrites the residual buffer.                                                                                */
 int emg3d_mg_gradient(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, double* grad);
+/* The same with the three components kept apart: grad_x, grad_y, grad_z (nC doubles each); (grad_x + grad_y) + grad_z is
+ * emg3d_mg_gradient's result bit for bit.                                                                               */
+int emg3d_mg_gradient3(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, double* grad_x, double* grad_y,
+                       double* grad_z);
+
+/* ---- sensitivity products (optimize.Jacobian) --------------------------------------------------------------------
+ * The reference (v0.17.0) has the gradient only; these are the pieces of J v and J^T w with J = d(data) / d(conductivity) for
+ * one (source, frequency) pair.  With A e = s the system of core.amat_x (the sigma-term of an edge is -1/4 (eta of its four
+ * cells) e, eta = s mu_0 sigma V; reference emg3d/core.py:149-177) and E the forward field:
+ *   J v   = P de,   A de = s mu_0 C(v) o E,   C(v)[edge] = 1/4 sum of V_c v_c over the four cells around the edge;
+ *   J^T w = -sum_c edges2cellaverages_c(-Re(s mu_0 lambda E)) = -emg3d_mg_gradient,   A lambda = P^T conj(w).
+ * maps.cellaverages2edges: the exact transpose of emg3d_edges2cellaverages (boundary edges count their cell two or four times,
+ * as there): out_c[edge] += sum vol v_c / 4; v_* F-ordered (nx,ny,nz) of dtype, out_* the components of a field of dtype (host);
+ * a NULL v_c leaves out_c alone.                                                                                       */
+int emg3d_cells2edges(int dtype, int64_t nx, int64_t ny, int64_t nz, const void* vx, const void* vy, const void* vz,
+                      const double* vol, void* out_x, void* out_y, void* out_z);
+/* Source of the selected system <- s mu_0 C(v) o E, E = workspace vector `efield_vec` (>= 0), per component with that
+ * component's perturbation vx / vy / vz (host, nC doubles, F-ordered; NULL: the component's source is zero; the same pointer
+ * for several directions is uploaded once); PEC boundary edges are written as exact zeros.  One thread per edge gathers its
+ * four cells: deterministic.  Overwrites the residual buffer.                                                          */
+int emg3d_mg_jvec_source(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, const double* vx, const double* vy,
+                         const double* vz);
+/* Linear receivers: resp[r] = sum_c factors[c][r] * (trilinear interpolation of component c of the selected system's field on
+ * the trimmed points of emg3d_get_receiver_response), NaN outside them; xyz / factors as there.  This is the receiver
+ * operator P whose transpose the next call applies.                                                                    */
+int emg3d_mg_get_receiver_response_linear(emg3d_mg_t* mg, int64_t n, const double* xyz, const double* factors, void* resp);
+/* Source of the selected system (+)= P^T w: w[n] of the handle's dtype (host); the buffer is zeroed first unless
+ * accumulate != 0.  Receivers whose datum is NaN (outside the trimmed points) contribute nothing.  Receivers may share
+ * edges: the host builds the edge -> contributions table (O(n log n)), the device gathers per touched edge in a fixed
+ * order -- results repeat bit for bit.                                                                                 */
+int emg3d_mg_set_receiver_adjoint(emg3d_mg_t* mg, int64_t n, const double* xyz, const double* factors, const void* w,
+                                  int accumulate);
 
 /* ---- regridding ---------------------------------------------------------------------------------------------------
  * maps._volume_average_weights(x1, x2), reference emg3d/maps.py:526-576, for one axis: x1 (n1 >= 2 edges, old grid) and
