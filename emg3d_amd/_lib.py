@@ -22,7 +22,7 @@ c_double = ctypes.c_double
 c_dp = ctypes.POINTER(ctypes.c_double)
 
 # include/emg3d_hip.h: EMG3D_HIP_ABI_VERSION -- a library built from another header version is refused at load
-ABI_VERSION = 105
+ABI_VERSION = 106
 
 # name -> (restype, argtypes); mirrors include/emg3d_hip.h one to one.
 SIGNATURES = {
@@ -116,6 +116,15 @@ SIGNATURES = {
     "emg3d_mg_vec_scale": (c_int, [c_vp, c_int, c_double, c_double]),
     "emg3d_mg_vec_dot": (c_int, [c_vp, c_int, c_int, c_dp]),
     "emg3d_mg_vec_amatvec": (c_int, [c_vp, c_int, c_int]),
+    "emg3d_mg_bvec_alloc": (c_int, [c_vp, c_int]),
+    "emg3d_mg_bvec_copy": (c_int, [c_vp, c_int, c_int]),
+    "emg3d_mg_bvec_zero": (c_int, [c_vp, c_int]),
+    "emg3d_mg_bvec_axpy": (c_int, [c_vp, c_int, c_vp, c_int]),
+    "emg3d_mg_bvec_scale": (c_int, [c_vp, c_int, c_vp]),
+    "emg3d_mg_bvec_dot": (c_int, [c_vp, c_int, c_int, c_vp]),
+    "emg3d_mg_bvec_amatvec": (c_int, [c_vp, c_int, c_int]),
+    "emg3d_mg_bvec_get": (c_int, [c_vp, c_int, c_int, c_vp]),
+    "emg3d_mg_bvec_set": (c_int, [c_vp, c_int, c_int, c_vp]),
 }
 
 _lib = None

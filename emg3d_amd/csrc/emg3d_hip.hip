@@ -1371,4 +1371,58 @@ int emg3d_mg_vec_amatvec(emg3d_mg_t* mg, int dst, int src) {
     DISPATCH(mg, { HIP_TRY(hipSetDevice(m->device)); return m->vec_amatvec(dst, src); });
 }
 
+// ---- batched Krylov vector workspace: vectors [nsys][nE], every primitive on all systems that are not frozen ----
+}  // extern "C"
+template <class T>
+static BatchCoef<T> batch_coef(int nsys, const double* alpha) {      // alpha: [nsys][2] (Re, Im)
+    BatchCoef<T> c;
+    for (int b = 0; b < EMG_MAX_BATCH; ++b) c.v[b] = b < nsys ? scalar_of<T>(alpha[2 * b], alpha[2 * b + 1]) : Zero<T>::v();
+    return c;
+}
+extern "C" {
+
+int emg3d_mg_bvec_alloc(emg3d_mg_t* mg, int n) {
+    if (n < 0 || n > 256) return -2;
+    DISPATCH(mg, { HIP_TRY(hipSetDevice(m->device)); return m->bvec_alloc(n); });
+}
+int emg3d_mg_bvec_copy(emg3d_mg_t* mg, int dst, int src) {
+    DISPATCH(mg, { HIP_TRY(hipSetDevice(m->device)); return m->bvec_copy(dst, src); });
+}
+int emg3d_mg_bvec_zero(emg3d_mg_t* mg, int id) {
+    DISPATCH(mg, { HIP_TRY(hipSetDevice(m->device)); return m->bvec_zero(id); });
+}
+int emg3d_mg_bvec_axpy(emg3d_mg_t* mg, int y, const double* alpha, int x) {
+    if (!alpha) return -2;
+    DISPATCH(mg, { HIP_TRY(hipSetDevice(m->device)); return m->bvec_axpy(y, batch_coef<T>(m->nsys, alpha), x); });
+}
+int emg3d_mg_bvec_scale(emg3d_mg_t* mg, int y, const double* alpha) {
+    if (!alpha) return -2;
+    DISPATCH(mg, { HIP_TRY(hipSetDevice(m->device)); return m->bvec_scale(y, batch_coef<T>(m->nsys, alpha)); });
+}
+int emg3d_mg_bvec_dot(emg3d_mg_t* mg, int a, int b, double* out) {
+    if (!out) return -2;
+    DISPATCH(mg, { HIP_TRY(hipSetDevice(m->device)); return m->bvec_dot(a, b, out); });
+}
+int emg3d_mg_bvec_amatvec(emg3d_mg_t* mg, int dst, int src) {
+    DISPATCH(mg, { HIP_TRY(hipSetDevice(m->device)); return m->bvec_amatvec(dst, src); });
+}
+int emg3d_mg_bvec_get(emg3d_mg_t* mg, int id, int b, void* host) {
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        T* v = m->bvec(id);
+        if (!v || !host || b < 0 || b >= m->nsys) return -2;
+        return get_field(m, v + (i64)b * m->lv0->nE, host);
+    });
+}
+int emg3d_mg_bvec_set(emg3d_mg_t* mg, int id, int b, const void* host) {
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        T* v = m->bvec(id);
+        if (!v || !host || b < 0 || b >= m->nsys) return -2;
+        HIP_TRY(m->h2d(v + (i64)b * m->lv0->nE, host, (size_t)m->lv0->nE * sizeof(T)));
+        m->touched(id);
+        return finish(m);
+    });
+}
+
 }  // extern "C"

@@ -773,6 +773,115 @@ struct MG : emg3d_mg {
         return err;
     }
 
+    // ------------------------------------------- batched Krylov vector workspace (emg3d_mg_bvec_*)
+    // Beside the single-system workspace above (whose vectors stay nE-sized and address the SELECTED system): vectors
+    // [nsys][nE] addressed by index, -1 = the whole level-0 source array, -2 = the whole level-0 field array.  Every
+    // primitive acts on the systems that are not frozen (set_mask) and gives each of them bit for bit what the
+    // single-system primitive gives on that system's vectors: same kernels' bodies, per system the same launch geometry.
+    std::vector<T*> bvecs;
+    double* bdot_partials = nullptr;    // [nsys][2 DOT_BLOCKS]
+    double* bdot_out = nullptr;         // [nsys][2]
+    std::vector<double> bdot_host;
+    std::vector<int> hmask;             // host mirror of bmask (empty: every system is active)
+    bool sys_on(int b) const { return hmask.empty() || hmask[(size_t)b] != 0; }
+    int bvec_alloc(int n) {
+        while ((int)bvecs.size() < n) {
+            T* v = try_alloc<T>((i64)nsys * lv0->nE);      // (optional memory, as vec_alloc: the handle stays usable)
+            if (!v) return (int)hipErrorOutOfMemory;
+            hipMemsetAsync(v, 0, (size_t)nsys * (size_t)lv0->nE * sizeof(T), stream);
+            bvecs.push_back(v);
+        }
+        if (!bdot_partials) {
+            bdot_partials = dalloc<double>((i64)nsys * 2 * DOT_BLOCKS); bdot_out = dalloc<double>(2 * (i64)nsys);
+            bdot_host.assign((size_t)(2 * nsys), 0.0);
+        }
+        return broken ? (int)hipErrorOutOfMemory : err;
+    }
+    T* bvec(int id) {
+        if (id == -1) return lv0->s;
+        if (id == -2) { e_to_ref(*lv0); return lv0->e; }
+        if (id < 0 || id >= (int)bvecs.size()) return nullptr;
+        return bvecs[(size_t)id];
+    }
+    // fn(first, count) for every run of consecutive active systems
+    template <class F>
+    void active_runs(F fn) {
+        for (int b = 0; b < nsys;) {
+            if (!sys_on(b)) { ++b; continue; }
+            int e = b;
+            while (e < nsys && sys_on(e)) ++e;
+            fn(b, e - b);
+            b = e;
+        }
+    }
+    int bvec_copy(int dst, int src) {
+        T *d = bvec(dst), *s_ = bvec(src);
+        if (!d || !s_) return -2;
+        const i64 nE = lv0->nE;
+        if (d != s_) active_runs([&](int b, int k) {
+            hipMemcpyAsync(d + (i64)b * nE, s_ + (i64)b * nE, (size_t)k * (size_t)nE * sizeof(T), hipMemcpyDeviceToDevice, stream);
+        });
+        touched(dst);
+        return 0;
+    }
+    int bvec_zero(int id) {
+        // the whole field array is overwritten: whatever layout it was in needs no conversion (as emg3d_mg_set_efield)
+        bool all_on = true;
+        for (int b = 0; b < nsys; ++b) all_on = all_on && sys_on(b);
+        if (id == -2 && all_on) lv0->e_home = 0;
+        T* d = bvec(id);
+        if (!d) return -2;
+        const i64 nE = lv0->nE;
+        active_runs([&](int b, int k) { hipMemsetAsync(d + (i64)b * nE, 0, (size_t)k * (size_t)nE * sizeof(T), stream); });
+        touched(id);
+        return 0;
+    }
+    int bvec_axpy(int y, const BatchCoef<T>& alpha, int x) {
+        T *py = bvec(y), *px = bvec(x);
+        if (!py || !px || py == px) return -2;
+        MG_LAUNCH(k_axpy_b<T>, bgrid_y(vec_grid()), dim3(EMG_BLOCK), 0, stream, py, (const T*)px, alpha, lv0->nE, batch(*lv0));
+        touched(y);
+        return 0;
+    }
+    int bvec_scale(int y, const BatchCoef<T>& alpha) {
+        T* py = bvec(y);
+        if (!py) return -2;
+        MG_LAUNCH(k_scale_b<T>, bgrid_y(vec_grid()), dim3(EMG_BLOCK), 0, stream, py, alpha, lv0->nE, batch(*lv0));
+        touched(y);
+        return 0;
+    }
+    int bvec_dot(int a, int b, double* out) {       // out[2 b], out[2 b + 1] = <a_b, b_b>, a conjugated; frozen systems: untouched
+        T *pa = bvec(a), *pb = bvec(b);
+        if (!pa || !pb || !bdot_partials) return -2;
+        const Batch bt = batch(*lv0);
+        MG_LAUNCH(k_dot_partials_b<T>, bgrid_y(DOT_BLOCKS), dim3(EMG_BLOCK), 0, stream, (const T*)pa, (const T*)pb, lv0->nE,
+                  bdot_partials, bt);
+        MG_LAUNCH(k_sum_pairs_b, bgrid_y(1), dim3(EMG_BLOCK), 0, stream, (const double*)bdot_partials, (i64)DOT_BLOCKS, bdot_out, bt);
+        hipError_t st = hipMemcpyAsync(bdot_host.data(), bdot_out, (size_t)(2 * nsys) * sizeof(double), hipMemcpyDeviceToHost, stream);
+        if (st == hipSuccess) st = hipStreamSynchronize(stream);
+        if (st != hipSuccess) return (int)st;
+        for (int s_ = 0; s_ < nsys; ++s_)
+            if (sys_on(s_)) { out[2 * s_] = bdot_host[(size_t)(2 * s_)]; out[2 * s_ + 1] = bdot_host[(size_t)(2 * s_ + 1)]; }
+        return 0;
+    }
+    // dst_b = A src_b: the residual launch of vec_amatvec over all systems, then the negate
+    int bvec_amatvec(int dst, int src) {
+        T *pd = bvec(dst), *ps = bvec(src);
+        if (!pd || !ps || pd == ps) return -2;
+        Level<T>& L = *lv0;
+        active_runs([&](int b, int k) { hipMemsetAsync(pd + (i64)b * L.nE, 0, (size_t)k * (size_t)L.nE * sizeof(T), stream); });
+        ResidualArgs<T> a;
+        for (int q = 0; q < 3; ++q) { a.nC[q] = L.nC[q]; a.eta[q] = L.eta[q]; a.h[q] = L.h[q]; a.ih[q] = L.ih[q]; }
+        a.fl = L.fl; a.r = pd; a.s = pd; a.e = ps; a.zeta = L.zeta; a.partials = nullptr; a.bt = batch(L);
+        const i64 plane = (L.nC[0] + 1) * (L.nC[1] + 1);
+        dim3 grid((unsigned)((plane + EMG_BLOCK - 1) / EMG_BLOCK), (unsigned)(L.nC[2] + 1), (unsigned)nsys);
+        if (!broken) residual_launch<T>(0, 1, grid, stream, a);   // pd = 0 - A ps
+        MG_LAUNCH(k_negate_b<T>, bgrid_y(vec_grid()), dim3(EMG_BLOCK), 0, stream, pd, L.nE, a.bt);
+        touched(dst);
+        check_launch();
+        return err;
+    }
+
     // ------------------------------------------------------------ smoothers
     // ---- working copies: x<->y transpose and parity split ------------------
     // bt: the batch of a FIELD array (model arrays are shared by the systems: Batch())
@@ -841,7 +950,7 @@ struct MG : emg3d_mg {
     // arrays are re-allocated as [n][nE]; the model and everything derived from it is shared.
     int set_batch(int n) {
         if (n < 1 || n > 64) return -2;
-        if (!hier.empty() || !graphs.empty() || lv0->eT || lv0->eW[0] || lv0->eW[1] || !vecs.empty()) return -6;
+        if (!hier.empty() || !graphs.empty() || lv0->eT || lv0->eW[0] || lv0->eW[1] || !vecs.empty() || !bvecs.empty()) return -6;
         if (n == nsys) return 0;
         Level<T>& L = *lv0;
         hipStreamSynchronize(stream);
@@ -853,6 +962,7 @@ struct MG : emg3d_mg {
         hipMemsetAsync(L.e, 0, (size_t)(nsys * L.nE) * sizeof(T), stream);
         hipMemsetAsync(L.r, 0, (size_t)(nsys * L.nE) * sizeof(T), stream);
         bmask = nullptr; n_partials = 0;
+        hmask.clear();
         if (nsys > 1) {
             bmask = dalloc<int>(nsys);
             std::vector<int> ones((size_t)nsys, 1);
@@ -864,6 +974,7 @@ struct MG : emg3d_mg {
     }
     int set_mask(const int* host) {
         if (nsys == 1) return 0;
+        hmask.assign(host, host + nsys);
         hipError_t st = hipMemcpyAsync(bmask, host, (size_t)nsys * sizeof(int), hipMemcpyHostToDevice, stream);
         if (st == hipSuccess) st = hipStreamSynchronize(stream);
         source_changed();       // a system that was frozen while a working copy of the source was refreshed

@@ -580,9 +580,17 @@ __global__ __launch_bounds__(EMG_BLOCK) void k_prolong(ProlongArgs<T> a) {
 
 // y = -y  (amatvec sign, solver.py:660) / generic scale.
 template <class T>
-__global__ __launch_bounds__(EMG_BLOCK) void k_negate(T* v, i64 n) {
+__device__ __forceinline__ void negate_body(T* v, i64 n) {
     for (i64 i = (i64)blockIdx.x * EMG_BLOCK + threadIdx.x; i < n; i += (i64)gridDim.x * EMG_BLOCK)
         v[i] = -v[i];
+}
+template <class T>
+__global__ __launch_bounds__(EMG_BLOCK) void k_negate(T* v, i64 n) { negate_body(v, n); }
+// batched vectors [system][n]: the system from blockIdx.y, per system the launch geometry of k_negate
+template <class T>
+__global__ __launch_bounds__(EMG_BLOCK) void k_negate_b(T* v, i64 n, Batch bt) {
+    EMG_BATCH(y, bt);
+    negate_body(v + boff_, n);
 }
 
 // ---------------------------------------------------------------------------
@@ -595,25 +603,31 @@ HD double conj_mul(double a, double b) { return a * b; }
 HD double imag_of(double) { return 0.0; }
 HD double imag_of(c128 a) { return a.im; }
 
-template <class T>
-__global__ __launch_bounds__(EMG_BLOCK) void k_axpy(T* __restrict__ y, const T* __restrict__ x, T alpha, i64 n) {
-    for (i64 i = (i64)blockIdx.x * EMG_BLOCK + threadIdx.x; i < n; i += (i64)gridDim.x * EMG_BLOCK)
-        y[i] = y[i] + alpha * x[i];
+// The element update, the per-element product and the two reduction stages live in __forceinline__ helpers that the
+// single-system and the batched kernels share: both see the same expressions (contracted the same way), the same loop
+// and the same summation order, so a system of a batch gets bit for bit what the single-system kernel gives on its vectors.
+template <class T> __device__ __forceinline__ T axpy_elem(T y, T alpha, T x) { return y + alpha * x; }
+template <class T> __device__ __forceinline__ T scale_elem(T alpha, T y) { return alpha * y; }
+template <class T> __device__ __forceinline__ void dot_elem(T a, T b, double& re, double& im) {
+    const T t = conj_mul(a, b);
+    re += real_of(t); im += imag_of(t);
 }
 template <class T>
-__global__ __launch_bounds__(EMG_BLOCK) void k_scale(T* __restrict__ y, T alpha, i64 n) {
+__device__ __forceinline__ void axpy_body(T* __restrict__ y, const T* __restrict__ x, T alpha, i64 n) {
     for (i64 i = (i64)blockIdx.x * EMG_BLOCK + threadIdx.x; i < n; i += (i64)gridDim.x * EMG_BLOCK)
-        y[i] = alpha * y[i];
+        y[i] = axpy_elem(y[i], alpha, x[i]);
+}
+template <class T>
+__device__ __forceinline__ void scale_body(T* __restrict__ y, T alpha, i64 n) {
+    for (i64 i = (i64)blockIdx.x * EMG_BLOCK + threadIdx.x; i < n; i += (i64)gridDim.x * EMG_BLOCK)
+        y[i] = scale_elem(alpha, y[i]);
 }
 // partials[2 b], partials[2 b + 1] = real / imaginary part of block b's share of <a, b>
 template <class T>
-__global__ __launch_bounds__(EMG_BLOCK) void k_dot_partials(const T* __restrict__ a, const T* __restrict__ b, i64 n,
-                                                            double* partials) {
+__device__ __forceinline__ void dot_partials_body(const T* __restrict__ a, const T* __restrict__ b, i64 n, double* partials) {
     double re = 0.0, im = 0.0;
-    for (i64 i = (i64)blockIdx.x * EMG_BLOCK + threadIdx.x; i < n; i += (i64)gridDim.x * EMG_BLOCK) {
-        const T t = conj_mul(a[i], b[i]);
-        re += real_of(t); im += imag_of(t);
-    }
+    for (i64 i = (i64)blockIdx.x * EMG_BLOCK + threadIdx.x; i < n; i += (i64)gridDim.x * EMG_BLOCK)
+        dot_elem(a[i], b[i], re, im);
     __shared__ double red[2][EMG_BLOCK / 64];
     for (int o = 32; o > 0; o >>= 1) { re += __shfl_down(re, o, 64); im += __shfl_down(im, o, 64); }
     if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = re; red[1][threadIdx.x >> 6] = im; }
@@ -625,7 +639,7 @@ __global__ __launch_bounds__(EMG_BLOCK) void k_dot_partials(const T* __restrict_
     }
 }
 // out[0], out[1] = sum of the nb (re, im) partial pairs, fixed order
-static __global__ __launch_bounds__(EMG_BLOCK) void k_sum_pairs(const double* partials, i64 nb, double* out) {
+__device__ __forceinline__ void sum_pairs_body(const double* partials, i64 nb, double* out) {
     __shared__ double red[2][EMG_BLOCK];
     double tr = 0.0, ti = 0.0;
     for (i64 i = threadIdx.x; i < nb; i += EMG_BLOCK) { tr += partials[2 * i]; ti += partials[2 * i + 1]; }
@@ -636,6 +650,50 @@ static __global__ __launch_bounds__(EMG_BLOCK) void k_sum_pairs(const double* pa
         __syncthreads();
     }
     if (threadIdx.x == 0) { out[0] = red[0][0]; out[1] = red[1][0]; }
+}
+
+template <class T>
+__global__ __launch_bounds__(EMG_BLOCK) void k_axpy(T* __restrict__ y, const T* __restrict__ x, T alpha, i64 n) {
+    axpy_body(y, x, alpha, n);
+}
+template <class T>
+__global__ __launch_bounds__(EMG_BLOCK) void k_scale(T* __restrict__ y, T alpha, i64 n) { scale_body(y, alpha, n); }
+template <class T>
+__global__ __launch_bounds__(EMG_BLOCK) void k_dot_partials(const T* __restrict__ a, const T* __restrict__ b, i64 n,
+                                                            double* partials) {
+    dot_partials_body(a, b, n, partials);
+}
+static __global__ __launch_bounds__(EMG_BLOCK) void k_sum_pairs(const double* partials, i64 nb, double* out) {
+    sum_pairs_body(partials, nb, out);
+}
+
+// ---- the same primitives on batched vectors [system][n] (emg3d_mg_bvec_*) ----
+// The system comes from blockIdx.y (a frozen system's workgroups return at once); gridDim.x is, per system, the grid of
+// the single-system kernel.  The per-system coefficients travel by value in the kernel-argument segment (set_batch
+// caps the batch at EMG_MAX_BATCH systems): no upload, no synchronisation per call.
+#define EMG_MAX_BATCH 64
+template <class T> struct BatchCoef { T v[EMG_MAX_BATCH]; };
+template <class T>
+__global__ __launch_bounds__(EMG_BLOCK) void k_axpy_b(T* __restrict__ y, const T* __restrict__ x, BatchCoef<T> alpha, i64 n, Batch bt) {
+    EMG_BATCH(y, bt);
+    axpy_body(y + boff_, x + boff_, alpha.v[b_], n);
+}
+template <class T>
+__global__ __launch_bounds__(EMG_BLOCK) void k_scale_b(T* __restrict__ y, BatchCoef<T> alpha, i64 n, Batch bt) {
+    EMG_BATCH(y, bt);
+    scale_body(y + boff_, alpha.v[b_], n);
+}
+// partials: [system][2 gridDim.x]
+template <class T>
+__global__ __launch_bounds__(EMG_BLOCK) void k_dot_partials_b(const T* __restrict__ a, const T* __restrict__ b, i64 n,
+                                                              double* partials, Batch bt) {
+    EMG_BATCH(y, bt);
+    dot_partials_body(a + boff_, b + boff_, n, partials + (i64)b_ * 2 * gridDim.x);
+}
+// out: [system][2]
+static __global__ __launch_bounds__(EMG_BLOCK) void k_sum_pairs_b(const double* partials, i64 nb, double* out, Batch bt) {
+    EMG_BATCH(y, bt);
+    sum_pairs_body(partials + (i64)b_ * 2 * nb, nb, out + 2 * b_);
 }
 
 // ---------------------------------------------------------------------------

@@ -357,7 +357,7 @@ class DeviceMG:
         cycle.  Before the first cycle only; zeroes the fields."""
         st = self._lib.emg3d_mg_set_batch(self._h, int(n))
         if st == -6:
-            raise RuntimeError("set_batch: the handle has already run or prepared a cycle.")
+            raise RuntimeError("set_batch: the handle has already run or prepared a cycle, or holds workspace vectors.")
         _lib.check(st, "emg3d_mg_set_batch")
 
     def select(self, b):
@@ -457,6 +457,58 @@ class DeviceMG:
 
     def vec_amatvec(self, dst, src):
         _lib.check(self._lib.emg3d_mg_vec_amatvec(self._h, int(dst), int(src)), "emg3d_mg_vec_amatvec")
+
+    # ---- batched vector workspace: vectors [nsys][nE]; every primitive acts on the systems that are not frozen ----
+    # (ids 0..n-1; SFIELD / EFIELD = the whole level-0 source / field array; per system bit for bit the vec_* result)
+    def bvec_alloc(self, n):
+        _lib.check(self._lib.emg3d_mg_bvec_alloc(self._h, int(n)), "emg3d_mg_bvec_alloc")
+
+    def _bcoef(self, alpha):
+        c = np.broadcast_to(np.asarray(alpha, dtype=np.complex128), (self.nsys,))
+        return np.ascontiguousarray(np.stack([c.real, c.imag], axis=1))
+
+    def bvec_copy(self, dst, src):
+        _lib.check(self._lib.emg3d_mg_bvec_copy(self._h, int(dst), int(src)), "emg3d_mg_bvec_copy")
+
+    def bvec_zero(self, i):
+        _lib.check(self._lib.emg3d_mg_bvec_zero(self._h, int(i)), "emg3d_mg_bvec_zero")
+
+    def bvec_axpy(self, y, alpha, x):
+        """y_b += alpha_b * x_b; ``alpha``: one value per system (or one for all)."""
+        a = self._bcoef(alpha)
+        _lib.check(self._lib.emg3d_mg_bvec_axpy(self._h, int(y), _lib.ptr(a), int(x)), "emg3d_mg_bvec_axpy")
+
+    def bvec_scale(self, y, alpha):
+        a = self._bcoef(alpha)
+        _lib.check(self._lib.emg3d_mg_bvec_scale(self._h, int(y), _lib.ptr(a)), "emg3d_mg_bvec_scale")
+
+    def bvec_dot(self, a, b, out=None):
+        """``vec_dot`` per system in one call (one device-to-host copy); the entries of frozen systems keep what ``out``
+        held (zero without ``out``)."""
+        n = self.nsys
+        if out is None:
+            out = np.zeros(n, dtype=self.dtype)
+        raw = np.zeros((n, 2))
+        raw[:, 0] = out.real
+        if self.dtype.kind == 'c':
+            raw[:, 1] = out.imag
+        _lib.check(self._lib.emg3d_mg_bvec_dot(self._h, int(a), int(b), _lib.ptr(raw)), "emg3d_mg_bvec_dot")
+        out[...] = raw[:, 0] + 1j * raw[:, 1] if self.dtype.kind == 'c' else raw[:, 0]
+        return out
+
+    def bvec_amatvec(self, dst, src):
+        _lib.check(self._lib.emg3d_mg_bvec_amatvec(self._h, int(dst), int(src)), "emg3d_mg_bvec_amatvec")
+
+    def bvec_get(self, i, b):
+        y = np.empty(self.nE, dtype=self.dtype)
+        _lib.check(self._lib.emg3d_mg_bvec_get(self._h, int(i), int(b), _lib.ptr(y)), "emg3d_mg_bvec_get")
+        return y
+
+    def bvec_set(self, i, b, x):
+        x = self._field(x)
+        if x.size != self.nE:
+            raise ValueError(f"bvec_set: {x.size} values for {self.nE} edges.")
+        _lib.check(self._lib.emg3d_mg_bvec_set(self._h, int(i), int(b), _lib.ptr(x)), "emg3d_mg_bvec_set")
 
     def time_sweep(self, direction, reps=3):
         v = ctypes.c_float()
@@ -680,6 +732,141 @@ def _exact_parts(grid, model, smu0):
     return models.model_parts(grid, model, raw=True)
 
 
+def _rotation_state(var):
+    """Where ``var`` stands in the rotation of the semicoarsening / line-relaxation directions: the positions in the two
+    lists (they advance by one per cycle the system has run) and the directions of the next cycle."""
+    return (int(var.sc_dir), int(var.lr_dir), var.it % len(var._raw_sc_cycle) if var.sc_cycle else 0,
+            var.it % len(var._raw_lr_cycle) if var.lr_cycle else 0)
+
+
+def _rotation_partitions(states, active):
+    """Groups of active systems (``active[b]`` != 0) with equal rotation ``states[b]``, in the order of their first members.
+    The systems of a group can go through the same launches of a cycle; the groups run one after the other."""
+    groups = {}
+    for b, st in enumerate(states):
+        if b < len(active) and active[b]:
+            groups.setdefault(st, []).append(b)
+    return list(groups.values())
+
+
+def _batched_multigrid(dev, vars_, active):
+    """Level-0 loop of ``multigrid`` for the systems ``active[b]`` != 0 of a batched handle (mask already on the device), which
+    stand at the same point of the direction rotation and start together: initial norm, optional initial smoothing, then
+    cycles until every system has met one of its own termination tests (a finished system is frozen).  Returns the
+    systems for which ``_terminate`` raised ``_ConvergenceError`` (a failing preconditioner) and the mask the device holds at
+    the end."""
+    active = np.array(active, dtype=np.int32)
+    on_device = active.copy()
+    idx = [b for b in range(len(vars_)) if active[b]]
+    failed = []
+    if not idx:
+        return failed, on_device
+    lead = vars_[idx[0]]
+    maxc = lead._maxcycle
+    dev.begin(lead.sc_dir)
+    l2_last = np.atleast_1d(dev.residual_norm()).copy()
+    l2_stag = {b: np.ones(maxc) * l2_last[b] for b in idx}
+    if lead.nu_init > 0:
+        dev.smooth(lead.nu_init, lead.lr_dir)
+    it = 0
+    while active.any():
+        live = [b for b in idx if active[b]]
+        l2_prev = l2_last.copy()
+        for b in idx:
+            l2_stag[b][(it - 1) % maxc] = l2_last[b]
+        # the rotation of the directions depends on the cycle count only: one state for the systems of the group, each
+        # of which advances its own iterators (it may enter a later call in another group)
+        cur = (vars_[live[0]].sc_dir, vars_[live[0]].lr_dir)
+        for b in live:
+            v = vars_[b]
+            nxt = (next(v.sc_cycle) if v.sc_cycle else v.sc_dir, next(v.lr_cycle) if v.lr_cycle else v.lr_dir)
+        ahead = PREPARE_AHEAD and nxt != cur and it + 1 < lead.maxit
+        norms = np.atleast_1d(dev.cycle(cur[0], cur[1], nxt=nxt if ahead else None))
+        it += 1
+        changed = False
+        for b in live:
+            var = vars_[b]
+            l2_last[b] = norms[b]
+            var.it += 1
+            _print_cycle_info(var, l2_last[b], l2_prev[b])
+            var.sc_dir, var.lr_dir = nxt
+            try:
+                done = _terminate(var, l2_last[b], l2_stag[b][(it - 1) % maxc], it)
+            except _ConvergenceError:
+                failed.append(b)
+                active[b] = 0
+                changed = True
+                continue
+            if done:
+                var.l2 = l2_last[b]
+                active[b] = 0
+                changed = True
+        if changed and active.any():
+            dev.set_mask(active)
+            on_device = active.copy()
+    return failed, on_device
+
+
+def _krylov_sources(dev, vars_, active):
+    """The Krylov part of ``solve_sources``: ``krylov`` for the systems ``active[b]`` != 0 of the batched handle ``dev`` (sources
+    in place), all in lockstep (``_bicgstab_device_batched`` / ``_cgs_device_batched``), preconditioned -- if ``cycle`` -- by
+    batched multigrid cycles.  The solutions end up in the level-0 field array of the handle."""
+    n = len(vars_)
+    nsys = dev.nsys
+    live = [b for b in range(n) if active[b]]
+    if not live:                    # zero sources only: zero fields
+        return
+    v0 = vars_[live[0]]
+    name = v0.sslsolver
+    if not _krylov_fits_device(dev, name, nsys=nsys):
+        mi = _lib.mem_info(dev.device)
+        raise _lib.HipLibraryError(
+            f"solve_sources: the {name} workspace of {nsys} systems needs {_krylov_workspace_bytes(dev, name, nsys=nsys)} "
+            f"bytes of device memory, {mi['free'] + mi['pooled_on_device']} bytes are free; use a smaller batch "
+            f"(fewer sources per call, shard.solve_survey(batch=...)).")
+
+    def psolve(src, dst, mask):
+        """dst_b = M src_b for the systems of ``mask``: per system what ``mg_on_device`` + ``multigrid`` run for a single solve.
+        The systems may stand at different points of the direction rotation (an inner call ends early for a system
+        whose norm falls below tol * l2_refe): one batched pass per group of equal state, the others frozen.  The
+        device's mask is ``mask`` on entry and on return."""
+        dev.bvec_copy(dev.SFIELD, src)
+        dev.bvec_zero(dev.EFIELD)
+        failed, on_device = [], mask
+        for group in _rotation_partitions([_rotation_state(v) for v in vars_], mask):
+            gmask = np.zeros(nsys, dtype=np.int32)
+            gmask[group] = 1
+            if not np.array_equal(gmask, on_device):
+                dev.set_mask(gmask)
+            bad, on_device = _batched_multigrid(dev, vars_, gmask)
+            failed += bad
+        if not np.array_equal(mask, on_device):
+            dev.set_mask(mask)
+        dev.bvec_copy(dst, dev.EFIELD)
+        return failed
+
+    def callback(var):
+        def cb(l2):
+            _count_krylov_step(var)
+            var.l2 = l2
+            _log_krylov_step(var)
+        return cb
+
+    drive = {'bicgstab': _bicgstab_device_batched, 'cgs': _cgs_device_batched}[name]
+    failed = []
+    codes = drive(dev, n, rtol=v0.tol, maxiter=v0.ssl_maxit, atol=1e-30, psolve=psolve if v0.cycle else None,
+                  callbacks=[callback(var) for var in vars_], active=active, failed=failed)
+    for b, var in enumerate(vars_):
+        if active[b]:
+            _krylov_exit_message(var, codes[b], b in failed)
+    mask = np.zeros(nsys, dtype=np.int32)
+    mask[:n] = active[:n]           # (a zero source's field was zeroed when it was set up)
+    dev.set_mask(mask)
+    dev.bvec_copy(dev.EFIELD, 0)    # the iterates (batched vector 0) -> the level-0 fields: receivers, download, reuse
+    mask[:n] = 1
+    dev.set_mask(mask)
+
+
 def solve_sources(grid, model, sources, frequency, strength=0, cycle='F', semicoarsening=False,
                   linerelaxation=False, verb=1, rec=None, download=True, electric=True, resident=None, **kwargs):
     """``[solve(grid, model, get_source_field(grid, src, frequency, strength), ...) for src in sources]`` as ONE
@@ -690,17 +877,24 @@ def solve_sources(grid, model, sources, frequency, strength=0, cycle='F', semico
     (a finished system is frozen, ``DeviceMG.set_mask``): fields and ``info_dict`` equal those of separate solves.
 
     ``sources``: electric sources as ``DeviceMG.set_source`` takes them (built in HBM), or ``SourceField`` objects
-    of frequency ``frequency`` (uploaded).  Multigrid only (``sslsolver`` is not batched).  ``rec``: receivers
+    of frequency ``frequency`` (uploaded).  ``sslsolver=True | 'bicgstab' | 'cgs'``: the Krylov iteration of ``solve`` for all
+    sources in lockstep on batched device vectors (``DeviceMG.bvec_*``), preconditioned by the batched cycles; every system
+    keeps its own coefficients and stops by its own tests, as above.  The workspace (12 vectors per system) must fit
+    in device memory (``HipLibraryError`` otherwise: use a smaller batch); ``'gcrotmk'`` is not batched.  ``rec``: receivers
     ``(x, y, z, azimuth, dip)`` -- the responses are extracted on the device.  ``download=False``: no fields
     returned.  Returns ``(efields | None, info_dicts)`` and the responses ``(n_sources, n_rec)`` if ``rec``.
 
     ``resident=n`` (with ``handle``; ``sources`` is ignored and may be None): the sources already sit in systems ``0 .. n-1`` of
     the handle (``DeviceMG.select`` + ``set_source`` / ``jvec_source`` / ``set_receiver_adjoint``); nothing is uploaded.  The
-    handle may carry more systems than ``n``: the others are frozen for the call and keep their fields.
+    handle may carry more systems than ``n``: the others are frozen for the call and keep their fields.  Multigrid only.
     """
-    if kwargs.get('sslsolver'):
-        raise ValueError("solve_sources batches multigrid cycles; use solve() per source with a Krylov solver.")
-    kwargs.pop('sslsolver', None)
+    sslsolver = kwargs.pop('sslsolver', False)
+    if sslsolver not in (False, None, True, 'bicgstab', 'cgs'):
+        raise ValueError("solve_sources batches the Krylov solvers 'bicgstab' and 'cgs' (sslsolver=True: 'bicgstab'); "
+                         f"use solve() per source for sslsolver={sslsolver!r}.")
+    sslsolver = sslsolver or False
+    if sslsolver and resident is not None:
+        raise ValueError("solve_sources: `resident` sources are solved by multigrid only (sslsolver=False).")
     device = kwargs.pop('device', 0)
     handle = kwargs.pop('handle', None)       # an existing DeviceMG of this grid / model / frequency: used, not closed
     if resident is not None:
@@ -715,7 +909,7 @@ def solve_sources(grid, model, sources, frequency, strength=0, cycle='F', semico
     for sf in host_fields:
         if sf is not None and (sf.freq is None or sf._freq != proto._freq):
             raise ValueError("solve_sources: every source field must carry the frequency of the batch.")
-    vars_ = [MGParameters(cycle=cycle, sslsolver=False, semicoarsening=semicoarsening,
+    vars_ = [MGParameters(cycle=cycle, sslsolver=sslsolver, semicoarsening=semicoarsening,
                           linerelaxation=linerelaxation, vnC=grid.vnC, verb=verb, **kwargs) for _ in range(n)]
     v0 = vars_[0]
     if handle is not None:
@@ -755,39 +949,18 @@ def solve_sources(grid, model, sources, frequency, strength=0, cycle='F', semico
             if var.l2_refe < 100 * np.finfo(float).tiny:        # zero source: zero field (solver.py:330-337)
                 var.l2_refe = np.nan
                 var.exit_message = "CONVERGED"
-                var.l2 = 0.0
+                if sslsolver:           # (as solve(): neither solver runs, the error keeps its initial value)
+                    var.sslsolver = None
+                    var.cycle = None
+                else:
+                    var.l2 = 0.0
                 active[b] = 0
-        if not active.all():
-            dev.set_mask(active)
-        dev.begin(v0.sc_dir)
-        l2_last = np.atleast_1d(dev.residual_norm()).copy()
-        l2_stag = [np.ones(v0._maxcycle) * l2_last[b] for b in range(n)]
-        if v0.nu_init > 0 and active.any():
-            dev.smooth(v0.nu_init, v0.lr_dir)
-        it = 0
-        while active.any():
-            l2_prev = l2_last.copy()
-            for b in range(n):
-                l2_stag[b][(it - 1) % v0._maxcycle] = l2_last[b]
-            nxt = (next(v0.sc_cycle) if v0.sc_cycle else v0.sc_dir, next(v0.lr_cycle) if v0.lr_cycle else v0.lr_dir)
-            ahead = PREPARE_AHEAD and nxt != (v0.sc_dir, v0.lr_dir) and it + 1 < v0.maxit
-            norms = np.atleast_1d(dev.cycle(v0.sc_dir, v0.lr_dir, nxt=nxt if ahead else None))
-            it += 1
-            changed = False
-            for b, var in enumerate(vars_):
-                if not active[b]:
-                    continue
-                l2_last[b] = norms[b]
-                var.it += 1
-                _print_cycle_info(var, l2_last[b], l2_prev[b])
-                if _terminate(var, l2_last[b], l2_stag[b][(it - 1) % v0._maxcycle], it):
-                    var.l2 = l2_last[b]
-                    active[b] = 0
-                    changed = True
-            # the rotation of the directions depends on the cycle count only: one state for all systems
-            v0.sc_dir, v0.lr_dir = nxt
-            if changed and active.any():
+        if sslsolver:
+            _krylov_sources(dev, vars_, active)
+        else:
+            if not active.all():
                 dev.set_mask(active)
+            _batched_multigrid(dev, vars_, active)
         efields = [] if download else None
         resp = [] if rec is not None else None
         for b in range(n):
@@ -1044,13 +1217,281 @@ def _cgs_device(dev, b, x0, rtol, maxiter, atol, psolve, callback):
     return dev.vec_get(X), maxiter
 
 
-def _krylov_fits_device(dev, name, m=20):
+class _Lockstep:
+    """Bookkeeping of the batched Krylov drivers: which systems of the handle still iterate, their return codes, and the
+    per-system views of the batched reductions.  All active systems execute iteration k together; a system that returns
+    is frozen (``set_mask``) and its vectors stay as they are from then on."""
+
+    def __init__(self, dev, n, active=None):
+        self.dev = dev
+        self.nsys = dev.nsys
+        self.active = np.zeros(self.nsys, dtype=np.int32)
+        self.active[:n] = 1 if active is None else np.asarray(active)[:n]
+        self.codes = [0] * n
+        self.failed = []            # systems whose preconditioner failed (code -1, as krylov() sets it)
+        self.cplx = np.dtype(dev.dtype).kind == 'c'
+        self._on_device = None
+
+    def live(self):
+        return [b for b in range(len(self.codes)) if self.active[b]]
+
+    def sync(self, mask=None):
+        """The device's mask <- ``mask`` (default: the active systems), if it is another one."""
+        mask = self.active if mask is None else mask
+        if self._on_device is None or not np.array_equal(mask, self._on_device):
+            self.dev.set_mask(mask)
+            self._on_device = np.array(mask, dtype=np.int32)
+
+    def only(self, systems):
+        mask = np.zeros(self.nsys, dtype=np.int32)
+        mask[list(systems)] = 1
+        return mask
+
+    def finish(self, b, code):
+        self.active[b] = 0
+        self.codes[b] = code
+
+    def dot(self, a, b):
+        """[vec_dot(a_b, b_b)] as Python scalars (the arithmetic of the single-system driver), None for frozen systems."""
+        d = self.dev.bvec_dot(a, b)
+        return [(complex(d[k]) if self.cplx else float(d[k])) if k < len(self.codes) and self.active[k] else None
+                for k in range(self.nsys)]
+
+    def norm(self, a):
+        return [None if v is None else float(np.sqrt(abs(v))) for v in self.dot(a, a)]
+
+    def coef(self, values, sign=1):
+        """Per-system coefficients for bvec_axpy / bvec_scale (0 for frozen systems, which the kernels skip); sign -1: -v."""
+        return [0.0 if (v is None or not self.active[k]) else (-v if sign < 0 else v) for k, v in enumerate(values)]
+
+
+def _bicgstab_device_batched(dev, n, rtol, maxiter, atol, psolve, callbacks, active=None, failed=None):
+    """``_bicgstab_device`` for the first ``n`` systems of a batched handle in lockstep, restated on ``bvec_*``: same order
+    of operations, same breakdown tests and, per system, the same exit codes (0, maxiter, -10, -11; -1: the
+    preconditioner failed for that system and its iterate is zero).  Every system keeps its own rho, alpha, omega and
+    atol and goes through exactly the operations of an iteration of its own.  The right-hand sides are the level-0
+    sources in the handle, the start vector is zero; the iterates are left in batched vector 0.  ``psolve(src, dst,
+    mask)`` applies the preconditioner to the systems of ``mask`` (the device's mask on entry, and again on return) and
+    returns those for which it failed; ``callbacks[b]`` gets || s_b - A x_b || after every iteration of system b;
+    ``active``: flags, 0 leaves a system out from the start.  Returns the list of exit codes; the systems whose
+    preconditioner failed are appended to ``failed`` (a code of -1 alone may also be ``maxiter``)."""
+    X, R, RT, P, V, S, T, PH, SH, B, TMP, RES = range(12)
+    ls = _Lockstep(dev, n, active)
+    dev.bvec_alloc(12)
+    ls.sync(ls.only(range(n)))
+    dev.bvec_zero(X)
+    ls.sync()
+    dev.bvec_copy(B, dev.SFIELD)
+    bnrm2 = ls.norm(B)
+    tol = [None if v is None else max(float(atol), float(rtol) * float(v)) for v in bnrm2]
+    for b in ls.live():
+        if bnrm2[b] == 0:
+            ls.finish(b, 0)
+    rhotol = np.finfo(np.dtype(dev.dtype).char).eps ** 2
+    omegatol = rhotol
+    rho_prev, omega, alpha = [None] * ls.nsys, [None] * ls.nsys, [None] * ls.nsys
+
+    def apply_psolve(src, dst):
+        if psolve is None:
+            dev.bvec_copy(dst, src)
+            return
+        failed = psolve(src, dst, ls.active.copy())      # (the device's mask on return: the one it got)
+        for b in failed:             # as a single solve ends there: the returned field is zero
+            ls.sync(ls.only([b]))
+            dev.bvec_zero(X)
+            ls.finish(b, -1)
+            ls.failed.append(b)
+        ls.sync()
+
+    ls.sync()
+    dev.bvec_copy(R, B)
+    dev.bvec_copy(RT, R)
+    for iteration in range(maxiter):
+        if not ls.live():
+            break
+        nr = ls.norm(R)
+        for b in ls.live():
+            if nr[b] < tol[b]:
+                ls.finish(b, 0)
+        ls.sync()
+        if not ls.live():
+            break
+        rho = ls.dot(RT, R)
+        for b in ls.live():
+            if abs(rho[b]) < rhotol:
+                ls.finish(b, -10)
+        if iteration > 0:
+            for b in ls.live():
+                if abs(omega[b]) < omegatol:
+                    ls.finish(b, -11)
+            ls.sync()
+            if not ls.live():
+                break
+            beta = [None] * ls.nsys
+            for b in ls.live():
+                beta[b] = (rho[b] / rho_prev[b]) * (alpha[b] / omega[b])
+            dev.bvec_axpy(P, ls.coef(omega, -1), V)     # p -= omega*v
+            dev.bvec_scale(P, ls.coef(beta))            # p *= beta
+            dev.bvec_axpy(P, 1.0, R)                    # p += r
+        else:
+            ls.sync()
+            if not ls.live():
+                break
+            dev.bvec_copy(P, R)
+        apply_psolve(P, PH)
+        if not ls.live():
+            break
+        dev.bvec_amatvec(V, PH)
+        rv = ls.dot(RT, V)
+        for b in ls.live():
+            if rv[b] == 0:
+                ls.finish(b, -11)
+        ls.sync()
+        if not ls.live():
+            break
+        for b in ls.live():
+            alpha[b] = rho[b] / rv[b]
+        dev.bvec_axpy(R, ls.coef(alpha, -1), V)         # r -= alpha*v
+        dev.bvec_copy(S, R)                             # s = r
+        ns = ls.norm(S)
+        # x += alpha*phat: the update of a system that converges here and the first of the two updates of the others
+        # (nothing reads x in between: the same two operations on x in the same order either way)
+        dev.bvec_axpy(X, ls.coef(alpha), PH)
+        for b in ls.live():
+            if ns[b] < tol[b]:
+                ls.finish(b, 0)
+        ls.sync()
+        if not ls.live():
+            break
+        apply_psolve(S, SH)
+        if not ls.live():
+            break
+        dev.bvec_amatvec(T, SH)
+        ts, tt = ls.dot(T, S), ls.dot(T, T)
+        for b in ls.live():
+            omega[b] = ts[b] / tt[b]
+            rho_prev[b] = rho[b]
+        dev.bvec_axpy(X, ls.coef(omega), SH)
+        dev.bvec_axpy(R, ls.coef(omega, -1), T)
+        if callbacks:
+            dev.bvec_amatvec(TMP, X)                    # the reference's callback: || sfield - A x ||
+            dev.bvec_copy(RES, B)
+            dev.bvec_axpy(RES, -1.0, TMP)
+            res = ls.norm(RES)
+            for b in ls.live():
+                callbacks[b](res[b])
+    for b in ls.live():
+        ls.finish(b, maxiter)
+    if failed is not None:
+        failed.extend(ls.failed)
+    return ls.codes
+
+
+def _cgs_device_batched(dev, n, rtol, maxiter, atol, psolve, callbacks, active=None, failed=None):
+    """``_cgs_device`` for the first ``n`` systems of a batched handle in lockstep (see ``_bicgstab_device_batched``)."""
+    X, R, RT, P, U, Q, PH, VH, UQ, UH, B, TMP = range(12)
+    ls = _Lockstep(dev, n, active)
+    dev.bvec_alloc(12)
+    ls.sync(ls.only(range(n)))
+    dev.bvec_zero(X)
+    ls.sync()
+    dev.bvec_copy(B, dev.SFIELD)
+    bnrm2 = ls.norm(B)
+    tol = [None if v is None else max(float(atol), float(rtol) * float(v)) for v in bnrm2]
+    for b in ls.live():
+        if bnrm2[b] == 0:
+            ls.finish(b, 0)
+    rhotol = np.finfo(np.dtype(dev.dtype).char).eps ** 2
+    rho_prev = [None] * ls.nsys
+
+    def apply_psolve(src, dst):
+        if psolve is None:
+            dev.bvec_copy(dst, src)
+            return
+        failed = psolve(src, dst, ls.active.copy())      # (the device's mask on return: the one it got)
+        for b in failed:             # as a single solve ends there: the returned field is zero
+            ls.sync(ls.only([b]))
+            dev.bvec_zero(X)
+            ls.finish(b, -1)
+            ls.failed.append(b)
+        ls.sync()
+
+    ls.sync()
+    dev.bvec_copy(R, B)
+    dev.bvec_copy(RT, R)
+    for iteration in range(maxiter):
+        if not ls.live():
+            break
+        nr = ls.norm(R)
+        for b in ls.live():
+            if nr[b] < tol[b]:
+                ls.finish(b, 0)
+        ls.sync()
+        if not ls.live():
+            break
+        rho = ls.dot(RT, R)
+        for b in ls.live():
+            if abs(rho[b]) < rhotol:
+                ls.finish(b, -10)
+        ls.sync()
+        if not ls.live():
+            break
+        if iteration > 0:
+            beta = [None] * ls.nsys
+            for b in ls.live():
+                beta[b] = rho[b] / rho_prev[b]
+            dev.bvec_copy(U, R)                         # u = r + beta q
+            dev.bvec_axpy(U, ls.coef(beta), Q)
+            dev.bvec_scale(P, ls.coef(beta))            # p = u + beta (q + beta p)
+            dev.bvec_axpy(P, 1.0, Q)
+            dev.bvec_scale(P, ls.coef(beta))
+            dev.bvec_axpy(P, 1.0, U)
+        else:
+            dev.bvec_copy(P, R)
+            dev.bvec_copy(U, R)
+        apply_psolve(P, PH)
+        if not ls.live():
+            break
+        dev.bvec_amatvec(VH, PH)
+        rv = ls.dot(RT, VH)
+        for b in ls.live():
+            if rv[b] == 0:
+                ls.finish(b, -11)
+        ls.sync()
+        if not ls.live():
+            break
+        alpha = [None] * ls.nsys
+        for b in ls.live():
+            alpha[b] = rho[b] / rv[b]
+            rho_prev[b] = rho[b]
+        dev.bvec_copy(Q, U)                             # q = u - alpha vhat
+        dev.bvec_axpy(Q, ls.coef(alpha, -1), VH)
+        dev.bvec_copy(UQ, U)                            # uhat = M (u + q)
+        dev.bvec_axpy(UQ, 1.0, Q)
+        apply_psolve(UQ, UH)
+        if not ls.live():
+            break
+        dev.bvec_axpy(X, ls.coef(alpha), UH)
+        dev.bvec_amatvec(TMP, X)                        # r = b - A x: the true residual, as SciPy computes it
+        dev.bvec_copy(R, B)
+        dev.bvec_axpy(R, -1.0, TMP)
+        if callbacks:
+            res = ls.norm(R)                            # the reference's callback: || sfield - A x ||
+            for b in ls.live():
+                callbacks[b](res[b])
+    for b in ls.live():
+        ls.finish(b, maxiter)
+    if failed is not None:
+        failed.extend(ls.failed)
+    return ls.codes
+
+
+def _krylov_fits_device(dev, name, m=20, nsys=1):
     """Do the Krylov vectors of the device-resident iteration fit next to the handle?  GCROT(m, k = m) keeps up to about
     5 + 2 (m + 1) + 2 m + 2 nE-sized vectors in HBM (~1.5 GB each at 256^3: ~130 GB), bicgstab / cgs 9 / 10.  When
     they do not fit, the caller runs SciPy's host iteration around the device preconditioner instead of failing in
-    ``emg3d_mg_vec_alloc``."""
-    nvec = {'bicgstab': 9, 'cgs': 10}.get(name, 5 + 2 * (m + 1) + 2 * m + 2)
-    need = nvec * dev.nE * dev.dtype.itemsize
+    ``emg3d_mg_vec_alloc``.  ``nsys``: the batched workspace (``emg3d_mg_bvec_alloc``) holds every vector once per system."""
+    need = _krylov_workspace_bytes(dev, name, m, nsys)
     try:
         # what is FREE now (other handles, torch allocations and other processes share the GPU), plus the DEVICE blocks this
         # process's own pool has parked for this device, which the vectors may take (not the blocks of other devices, not the
@@ -1059,6 +1500,11 @@ def _krylov_fits_device(dev, name, m=20):
     except Exception:
         return True
     return need < 0.92 * (mi["free"] + mi["pooled_on_device"])
+
+
+def _krylov_workspace_bytes(dev, name, m=20, nsys=1):
+    nvec = {'bicgstab': 9, 'cgs': 10}.get(name, 5 + 2 * (m + 1) + 2 * m + 2)
+    return nvec * dev.nE * dev.dtype.itemsize * int(nsys)
 
 
 def _gcrotmk_device(dev, b, x0, rtol, maxiter, atol, psolve, callback, m=20, k=None):
@@ -1214,6 +1660,41 @@ def _gcrotmk_device(dev, b, x0, rtol, maxiter, atol, psolve, callback, m=20, k=N
     return dev.vec_get(X), j_outer + 1
 
 
+def _count_krylov_step(var):
+    var._ssl_it += 1
+    var.runtime_at_cycle = np.r_[var.runtime_at_cycle, var.time.elapsed]
+
+
+def _log_krylov_step(var):
+    """End of a Krylov iteration, ``var.l2`` = || sfield - A x ||: bookkeeping and log line (solver.py:685-708)."""
+    var.error_at_cycle = np.r_[var.error_at_cycle, var.l2]
+    if var.verb > 3:
+        log = f"   [{var.time.now}]   {var.l2/var.l2_refe:.3e} "
+        log += f" after {var._ssl_it:3} {var.sslsolver}-cycles"
+        if var._ssl_it == 1 and var.it == 0 and var.cycle is not None:
+            log += "\n"
+        var.cprint(log, 3)
+    elif var.verb < 0:
+        var.one_liner(var.l2)
+
+
+def _krylov_exit_message(var, i, failed=False):
+    """Exit message from the Krylov driver's return code ``i`` (solver.py:721-734); ``failed``: the preconditioner failed
+    (``_ConvergenceError``) and ``i`` is -1."""
+    if failed:
+        var.exit_message += " (returned field is zero)"
+    pre = "\n   > "
+    if i < 0:
+        if var.exit_message == '':
+            var.exit_message = f"Error in {var.sslsolver} ({i})"
+        pre = "\n* ERROR   :: "
+    elif i > 0:
+        var.exit_message = "MAX. ITERATION REACHED, NOT CONVERGED"
+    else:
+        var.exit_message = "CONVERGED"
+    var.cprint(pre + var.exit_message, 2)
+
+
 def krylov(grid, model, sfield, efield, var, dev=None):
     """Krylov solver preconditioned by multigrid (reference solver.py:610-734).
 
@@ -1251,22 +1732,13 @@ def krylov(grid, model, sfield, efield, var, dev=None):
         M = ssl.LinearOperator(shape=(grid.nE, grid.nE), dtype=sfield.dtype, matvec=mg_matvec)
 
     def callback(x):
-        var._ssl_it += 1
-        var.runtime_at_cycle = np.r_[var.runtime_at_cycle, var.time.elapsed]
+        _count_krylov_step(var)
         if isinstance(x, float):        # device path: the norm of s - A x, computed on the device
             var.l2 = x
         else:
             r = np.asarray(sfield) - dev.amatvec(np.asarray(x))
             var.l2 = float(np.linalg.norm(r))
-        var.error_at_cycle = np.r_[var.error_at_cycle, var.l2]
-        if var.verb > 3:
-            log = f"   [{var.time.now}]   {var.l2/var.l2_refe:.3e} "
-            log += f" after {var._ssl_it:3} {var.sslsolver}-cycles"
-            if var._ssl_it == 1 and var.it == 0 and var.cycle is not None:
-                log += "\n"
-            var.cprint(log, 3)
-        elif var.verb < 0:
-            var.one_liner(var.l2)
+        _log_krylov_step(var)
 
     def mg_on_device(src, dst):
         """dst = M src with both vectors on the device (same cycles as mg_matvec)."""
@@ -1279,6 +1751,7 @@ def krylov(grid, model, sfield, efield, var, dev=None):
             var._dev_efield_current = False
         dev.vec_copy(dst, dev.EFIELD)
 
+    failed = False
     try:
         if var.sslsolver in ('bicgstab', 'cgs', 'gcrotmk') and DEVICE_KRYLOV and _krylov_fits_device(dev, var.sslsolver):
             drive = {'bicgstab': _bicgstab_device, 'cgs': _cgs_device, 'gcrotmk': _gcrotmk_device}[var.sslsolver]
@@ -1289,22 +1762,11 @@ def krylov(grid, model, sfield, efield, var, dev=None):
                                               maxiter=var.ssl_maxit, atol=1e-30, M=M, callback=callback)
         efield.field = x
     except _ConvergenceError:
-        i = -1
-        var.exit_message += " (returned field is zero)"
+        i, failed = -1, True
     finally:
         if own:
             dev.close()
-
-    pre = "\n   > "
-    if i < 0:
-        if var.exit_message == '':
-            var.exit_message = f"Error in {var.sslsolver} ({i})"
-        pre = "\n* ERROR   :: "
-    elif i > 0:
-        var.exit_message = "MAX. ITERATION REACHED, NOT CONVERGED"
-    else:
-        var.exit_message = "CONVERGED"
-    var.cprint(pre + var.exit_message, 2)
+    _krylov_exit_message(var, i, failed)
 
 
 # --------------------------------------------------------------------------

@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 105
+#define EMG3D_HIP_ABI_VERSION 106
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -304,7 +304,8 @@ int emg3d_interp3d_grid(int dtype, int64_t nx, int64_t ny, int64_t nz, const dou
  *   emg3d_mg_set_mask(mg, act)  act[n]: 0 freezes a system (converged: its cycles are skipped, its field stays
  *                               untouched); the norms reported for a frozen system are 0.
  * emg3d_mg_cycle / emg3d_mg_residual_norm then write n norms, emg3d_mg_cycles ncycles x n ([cycle][system]).
- * The Krylov workspace (emg3d_mg_vec_*) addresses the selected system only.  Environment EMG3D_BATCH_TUNE=1 (read at
+ * The Krylov workspace (emg3d_mg_vec_*) addresses the selected system only; emg3d_mg_bvec_* (below) is its batched
+ * counterpart.  set_batch also returns -6 once either workspace holds vectors.  Environment EMG3D_BATCH_TUNE=1 (read at
  * emg3d_mg_create): coarse-level kernel choice by lines x systems -- faster (6-11 %), results then equal stand-alone
  * solves to rounding instead of bit for bit.                                                                      */
 int emg3d_mg_set_batch(emg3d_mg_t* mg, int n);
@@ -430,6 +431,30 @@ int emg3d_mg_vec_axpy(emg3d_mg_t* mg, int y, double alpha_re, double alpha_im, i
 int emg3d_mg_vec_scale(emg3d_mg_t* mg, int y, double alpha_re, double alpha_im);
 int emg3d_mg_vec_dot(emg3d_mg_t* mg, int a, int b, double* out2);
 int emg3d_mg_vec_amatvec(emg3d_mg_t* mg, int dst, int src);
+
+/* The same workspace for ALL systems of a batched handle at once (solver.solve_sources with a Krylov solver): "batched
+ * vectors" [nsys][nE] addressed by index 0..n-1 (zero-initialised; n <= 256), -1 = the whole level-0 source array,
+ * -2 = the whole level-0 field array (brought to the reference layout first).  Every primitive acts on the systems that
+ * are not frozen (emg3d_mg_set_mask) and leaves the others' data untouched; per system the result is bit for bit that
+ * of the emg3d_mg_vec_* primitive on that system's vectors (same launch geometry per system, same summation order).
+ * The emg3d_mg_vec_* workspace keeps its meaning on batched handles (nE-sized vectors, -1 / -2 = the selected system).
+ *   bvec_alloc  : optional memory -- on failure hipErrorOutOfMemory is returned and the handle stays usable
+ *   bvec_copy   : dst_b = src_b       bvec_zero : dst_b = 0
+ *   bvec_axpy   : y_b += alpha_b x_b  bvec_scale: y_b *= alpha_b     alpha: [nsys][2] doubles (Re, Im; Im ignored for
+ *                 float64 handles), passed to the kernel by value: no upload, no synchronisation
+ *   bvec_dot    : out[2 b], out[2 b + 1] = (Re, Im) of sum conj(a_b,i) b_b,i; ONE device-to-host copy for all systems;
+ *                 the entries of frozen systems are not written; synchronises the stream
+ *   bvec_amatvec: dst_b = A src_b
+ *   bvec_get / bvec_set: system b's slice of a batched vector <-> host (nE entries), frozen or not             */
+int emg3d_mg_bvec_alloc(emg3d_mg_t* mg, int n);
+int emg3d_mg_bvec_copy(emg3d_mg_t* mg, int dst, int src);
+int emg3d_mg_bvec_zero(emg3d_mg_t* mg, int id);
+int emg3d_mg_bvec_axpy(emg3d_mg_t* mg, int y, const double* alpha, int x);
+int emg3d_mg_bvec_scale(emg3d_mg_t* mg, int y, const double* alpha);
+int emg3d_mg_bvec_dot(emg3d_mg_t* mg, int a, int b, double* out);
+int emg3d_mg_bvec_amatvec(emg3d_mg_t* mg, int dst, int src);
+int emg3d_mg_bvec_get(emg3d_mg_t* mg, int id, int b, void* host);
+int emg3d_mg_bvec_set(emg3d_mg_t* mg, int id, int b, const void* host);
 
 #ifdef __cplusplus
 }
