@@ -632,6 +632,78 @@ static int cells2edges_impl(const i64 nC[3], const void* const v[3], const doubl
     return 0;
 }
 
+// s of the selected system (+)= P^T w: emg3d_mg_set_receiver_adjoint_ex (include/emg3d_hip.h)
+template <class T>
+int receiver_adjoint_impl(MG<T>* m, int method, int magnetic, double sr, double si, i64 n, const double* xyz, const double* fac,
+                          const T* w, int accumulate) {
+    HIP_TRY(hipSetDevice(m->device));
+    auto& L = *m->lv0;
+    if (L.nC[0] < 3 || L.nC[1] < 3 || L.nC[2] < 3) return -2;
+    if (magnetic && sizeof(T) == 8 && si != 0.0) return -2;
+    if (method == 1 && !m->scratch_field) m->scratch_field = m->template dalloc<T>(L.nE);
+    if (m->broken) return (int)hipErrorOutOfMemory;
+    if (!accumulate) HIP_TRY(hipMemsetAsync(m->sel_s(), 0, (size_t)L.nE * sizeof(T), m->stream));
+    m->source_changed();
+    RcvComp<T> comp[3];
+    int rc;
+    if (!magnetic) {
+        receiver_components<T>(L.nodes, L.centers, L.nC, true, m->sel_s(), comp);
+        rc = method ? receiver_adjoint_cubic_device<T>(m->stream, comp, L.fl, n, xyz, fac, w, m->scratch_field, m->sel_s())
+                    : receiver_adjoint_device<T>(m->stream, comp, L.fl, n, xyz, fac, w, m->sel_s());
+    } else {
+        // P_faces^T w on the face arrays [hx | hy | hz] in the residual buffer (scratch between calls, nH < nE), then C^T
+        T* faces = L.r;
+        HIP_TRY(hipMemsetAsync(faces, 0, (size_t)hfield_size(L.nC) * sizeof(T), m->stream));
+        receiver_components<T>(L.nodes, L.centers, L.nC, false, faces, comp);
+        FieldLayout hl;
+        i64 o = 0;
+        for (int c = 0; c < 3; ++c) {
+            hl.off[c] = o;
+            hl.st[c][0] = 1; hl.st[c][1] = comp[c].n[0]; hl.st[c][2] = comp[c].n[0] * comp[c].n[1];
+            o += comp[c].n[0] * comp[c].n[1] * comp[c].n[2];
+        }
+        rc = method ? receiver_adjoint_cubic_device<T>(m->stream, comp, hl, n, xyz, fac, w, m->scratch_field, faces)
+                    : receiver_adjoint_device<T>(m->stream, comp, hl, n, xyz, fac, w, faces);
+        if (rc == 0) {
+            HFieldAdjArgs<T> a;
+            i64 big = 0;
+            for (int q = 0; q < 3; ++q) {
+                a.nC[q] = L.nC[q]; a.ih[q] = L.ih[q];
+                i64 sz = 1;
+                for (int d = 0; d < 3; ++d) sz *= (d == q) ? L.nC[d] : L.nC[d] + 1;
+                big = std::max(big, sz);
+            }
+            a.fl = L.fl; a.f = faces; a.s = m->sel_s();
+            a.scl = -recip(scalar_of<T>(sr, si));
+            hipLaunchKernelGGL(k_hfield_adjoint<T>, dim3((unsigned)((big + EMG_BLOCK - 1) / EMG_BLOCK), 3), dim3(EMG_BLOCK), 0,
+                               m->stream, a);
+            m->check_launch();
+        }
+    }
+    const int st = finish(m);
+    return rc ? rc : st;
+}
+
+template <class T>
+int receiver_response_linear_impl(MG<T>* m, int magnetic, double sr, double si, i64 n, const double* xyz, const double* fac, void* resp) {
+    HIP_TRY(hipSetDevice(m->device));
+    auto& L = *m->lv0;
+    if (L.nC[0] < 3 || L.nC[1] < 3 || L.nC[2] < 3) return -2;
+    const T* fdev = m->sel_e();
+    if (m->broken) return (int)hipErrorOutOfMemory;
+    if (magnetic) {        // H = get_h_field(E) into the residual buffer (scratch between calls, nH < nE)
+        if (sizeof(T) == 8 && si != 0.0) return -2;
+        launch_hfield(m->stream, L.nC, L.fl, m->sel_e(), (const double*)nullptr, L.h, L.ih, sr, si, L.r);
+        m->check_launch();
+        fdev = L.r;
+    }
+    RcvComp<T> comp[3];
+    receiver_components<T>(L.nodes, L.centers, L.nC, !magnetic, fdev, comp);
+    const int rc = receiver_response_device<T>(m->stream, comp, n, xyz, fac, (T*)nullptr, (T*)resp, 0);
+    const int st = finish(m);
+    return rc ? rc : st;
+}
+
 extern "C" {
 
 int emg3d_hip_version(void) { return EMG3D_HIP_VERSION; }
@@ -947,37 +1019,53 @@ int emg3d_mg_jvec_source(emg3d_mg_t* mg, int efield_vec, double smu0_re, double 
     DISPATCH(mg, return jvec_source_impl<T>(m, efield_vec, smu0_re, smu0_im, vx, vy, vz));
 }
 
+int emg3d_mg_set_receiver_adjoint_ex(emg3d_mg_t* mg, int method, int magnetic, double smu0_re, double smu0_im, int64_t n,
+                                     const double* xyz, const double* factors, const void* w, int accumulate) {
+    if (!mg || n < 1 || !xyz || !factors || !w || method < 0 || method > 1) return -2;
+    if (magnetic && smu0_re == 0.0 && smu0_im == 0.0) return -2;
+    DISPATCH(mg, return receiver_adjoint_impl<T>(m, method, magnetic, smu0_re, smu0_im, n, xyz, factors, (const T*)w, accumulate));
+}
+
 int emg3d_mg_set_receiver_adjoint(emg3d_mg_t* mg, int64_t n, const double* xyz, const double* factors, const void* w,
                                   int accumulate) {
-    if (!mg || n < 1 || !xyz || !factors || !w) return -2;
-    DISPATCH(mg, {
-        HIP_TRY(hipSetDevice(m->device));
-        auto& L = *m->lv0;
-        if (L.nC[0] < 3 || L.nC[1] < 3 || L.nC[2] < 3) return -2;
-        if (!accumulate) HIP_TRY(hipMemsetAsync(m->sel_s(), 0, (size_t)L.nE * sizeof(T), m->stream));
-        m->source_changed();
-        RcvComp<T> comp[3];
-        receiver_components<T>(L.nodes, L.centers, L.nC, true, m->sel_s(), comp);
-        const int rc = receiver_adjoint_device<T>(m->stream, comp, L.fl, n, xyz, factors, (const T*)w, m->sel_s());
-        const int st = finish(m);
-        return rc ? rc : st;
-    });
+    return emg3d_mg_set_receiver_adjoint_ex(mg, 0, 0, 0.0, 0.0, n, xyz, factors, w, accumulate);
+}
+
+int emg3d_receiver_adjoint(int dtype, int64_t nx, int64_t ny, int64_t nz, const double* hx, const double* hy, const double* hz,
+                           const double* origin, int is_electric, int method, double smu0_re, double smu0_im, int64_t n,
+                           const double* xyz, const double* factors, const void* w, void* field) {
+    if (nx < 3 || ny < 3 || nz < 3 || n < 1 || !hx || !hy || !hz || !xyz || !factors || !w || !field) return -2;
+    // a throw-away handle gives the device grid vectors (the model is not used)
+    emg3d_mg_t* h = nullptr;
+    const i64 nC = nx * ny * nz;
+    std::vector<double> zeta((size_t)nC, 1.0);
+    int st;
+    if (dtype) {
+        std::vector<c128> eta((size_t)nC, mk(0.0, 0.0));
+        st = create_impl<c128>(&h, 1, nx, ny, nz, hx, hy, hz, origin, eta.data(), eta.data(), eta.data(), zeta.data(), current_device());
+    } else {
+        std::vector<double> eta((size_t)nC, 0.0);
+        st = create_impl<double>(&h, 0, nx, ny, nz, hx, hy, hz, origin, eta.data(), eta.data(), eta.data(), zeta.data(), current_device());
+    }
+    if (st) return st;
+    st = emg3d_mg_set_receiver_adjoint_ex(h, method, !is_electric, smu0_re, smu0_im, n, xyz, factors, w, 0);
+    if (!st) {
+        if (dtype) st = get_field(as<c128>(h), as<c128>(h)->lv0->s, field);
+        else st = get_field(as<double>(h), as<double>(h)->lv0->s, field);
+    }
+    emg3d_mg_destroy(h);
+    return st;
 }
 
 int emg3d_mg_get_receiver_response_linear(emg3d_mg_t* mg, int64_t n, const double* xyz, const double* factors, void* resp) {
     if (!mg || n < 1 || !xyz || !factors || !resp) return -2;
-    DISPATCH(mg, {
-        HIP_TRY(hipSetDevice(m->device));
-        auto& L = *m->lv0;
-        if (L.nC[0] < 3 || L.nC[1] < 3 || L.nC[2] < 3) return -2;
-        const T* fdev = m->sel_e();
-        if (m->broken) return (int)hipErrorOutOfMemory;
-        RcvComp<T> comp[3];
-        receiver_components<T>(L.nodes, L.centers, L.nC, true, fdev, comp);
-        const int rc = receiver_response_device<T>(m->stream, comp, n, xyz, factors, (T*)nullptr, (T*)resp, 0);
-        const int st = finish(m);
-        return rc ? rc : st;
-    });
+    DISPATCH(mg, return receiver_response_linear_impl<T>(m, 0, 0.0, 0.0, n, xyz, factors, resp));
+}
+
+int emg3d_mg_get_receiver_response_linear_h(emg3d_mg_t* mg, double smu0_re, double smu0_im, int64_t n, const double* xyz,
+                                            const double* factors, void* resp) {
+    if (!mg || n < 1 || !xyz || !factors || !resp || (smu0_re == 0.0 && smu0_im == 0.0)) return -2;
+    DISPATCH(mg, return receiver_response_linear_impl<T>(m, 1, smu0_re, smu0_im, n, xyz, factors, resp));
 }
 
 int emg3d_cells2edges(int dtype, int64_t nx, int64_t ny, int64_t nz, const void* vx, const void* vy, const void* vz,

@@ -407,7 +407,7 @@ int receiver_response_device(hipStream_t st, const RcvComp<T> comp[3], i64 npts,
         return rc;
 }
 
-// ---- transpose of the linear receiver operator -------------------------------------------------------------------------------
+// ---- transpose of the receiver operators ------------------------------------------------------------------------------------
 // s[edge] (+)= sum over the receivers r that touch the edge of weight * w[r]: thread per TOUCHED edge, contributions in the fixed
 // order of the host's table (receiver, then corner) -- deterministic although receivers share edges, no atomics.
 template <class T>
@@ -419,64 +419,116 @@ __global__ void k_receiver_adjoint(T* s, const i64* edges, const int* ptr, const
     s[edges[k]] += acc;
 }
 
-// s (+)= P^T w, P the operator of receiver_response_device(method 0) on the electric components comp (only n / pts are used),
-// fl the layout of s.  Host: 8 weights per receiver and active component, O(npts log npts); CSR by edge.  A receiver outside the
-// trimmed points of an active component (its datum is NaN) contributes nothing.
+// Transpose of k_spline_eval: coef[idx] = sum of w[r] * (fac[r] w0 w1 w2) over the (receiver, stencil point) pairs that read the
+// coefficient idx -- thread per TOUCHED coefficient of the zeroed trimmed array, summed in the order of the host's table
+// (receiver, then stencil order; stencil indices that the mirror extension folds onto one coefficient add up).
 template <class T>
-int receiver_adjoint_device(hipStream_t st, const RcvComp<T> comp[3], const FieldLayout& fl, i64 npts, const double* xyz,
-                            const double* fac, const T* w_host, T* s) {
-    if (npts < 1) return -2;
-    struct Entry { i64 edge; int r; double w; };
-    std::vector<Entry> ent;
-    std::vector<char> inside((size_t)npts, 1);
-    bool active[3];
-    for (int c = 0; c < 3; ++c) {
-        active[c] = false;
-        for (i64 r = 0; r < npts; ++r) if (std::fabs(fac[c * npts + r]) > 1e-10) { active[c] = true; break; }
-        if (!active[c]) continue;
-        for (int a = 0; a < 3; ++a) {
-            if (comp[c].n[a] < 3) return -2;
-            const double* g = comp[c].pts[a].data() + 1;
-            const i64 m = comp[c].n[a] - 2;
-            for (i64 r = 0; r < npts; ++r) if (!(xyz[a * npts + r] >= g[0] && xyz[a * npts + r] <= g[m - 1])) inside[r] = 0;
-        }
+__global__ void k_spline_eval_adjoint(T* coef, const i64* idx, const int* ptr, const int* rcv, const double* wgt, const T* w, i64 ntouched) {
+    const i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= ntouched) return;
+    T acc = Zero<T>::v();
+    for (int q = ptr[k]; q < ptr[k + 1]; ++q) acc += w[rcv[q]] * wgt[q];
+    coef[idx[k]] = acc;
+}
+
+// First and last entry of every line along `axis` of an F-ordered (n0, n1, n2) array times f; thread per line.  The prefilter
+// F of k_spline_filter_axis (mirror initialisation) is the inverse of tridiag(1/6, 4/6, 1/6) with the end rows (4/6, 2/6): not
+// symmetric, but F^T = D F D^-1 with D = diag(1/2, 1, ..., 1, 1/2) -- the transposed filter is this kernel with f = 2, the
+// forward filter, this kernel with f = 1/2 (both scalings are exact).  Lines with n < 2 are left alone, as the filter leaves them.
+template <class T>
+__global__ void k_line_ends_scale(T* c, i64 n0, i64 n1, i64 n2, int axis, double f) {
+    const i64 n = axis == 0 ? n0 : axis == 1 ? n1 : n2;
+    const i64 nlines = (n0 * n1 * n2) / n;
+    const i64 line = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (line >= nlines || n < 2) return;
+    i64 base, st;
+    if (axis == 0) { base = line * n0; st = 1; }
+    else if (axis == 1) { const i64 i0 = line % n0, i2 = line / n0; base = i0 + n0 * n1 * i2; st = n0; }
+    else { base = line; st = n0 * n1; }
+    c[base] *= f;
+    c[base + (n - 1) * st] *= f;
+}
+
+// Transpose of k_trim_copy through a field layout: s[off + (i0+1) st0 + (i1+1) st1 + (i2+1) st2] += coef[i0, i1, i2] for the
+// F-ordered (m0, m1, m2) array coef; thread per trimmed element, i0 fastest.
+template <class T>
+__global__ void k_trim_add(T* s, const T* coef, i64 m0, i64 m1, i64 m2, i64 off, i64 st0, i64 st1, i64 st2) {
+    const i64 tot = m0 * m1 * m2;
+    for (i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (i64)gridDim.x * blockDim.x) {
+        i64 i0, i1, i2;
+        unlin3(idx, m0, m1, m2, i0, i1, i2);
+        s[off + (i0 + 1) * st0 + (i1 + 1) * st1 + (i2 + 1) * st2] += coef[idx];
     }
-    for (int c = 0; c < 3; ++c) {
-        if (!active[c]) continue;
-        for (i64 r = 0; r < npts; ++r) {
-            if (!inside[r]) continue;
-            i64 ii[3];
-            double tt[3];
-            for (int a = 0; a < 3; ++a) {           // as interp3d_device, method 0
-                const double* g = comp[c].pts[a].data() + 1;
-                const i64 m = comp[c].n[a] - 2;
-                const double v = xyz[a * npts + r];
-                i64 i = (i64)(std::lower_bound(g, g + m, v) - g) - 1;
-                if (i < 0) i = 0;
-                if (i > m - 2) i = m - 2;
-                if (m == 1) { ii[a] = 1; tt[a] = 0.0; continue; }
-                ii[a] = i + 1;
-                tt[a] = (v - g[i]) / (g[i + 1] - g[i]);
-            }
-            for (int a0 = 0; a0 < 2; ++a0)
-                for (int a1 = 0; a1 < 2; ++a1)
-                    for (int a2 = 0; a2 < 2; ++a2) {
-                        const double wg = (a0 ? tt[0] : 1 - tt[0]) * (a1 ? tt[1] : 1 - tt[1]) * (a2 ? tt[2] : 1 - tt[2]);
-                        // (an axis with one trimmed point: both corners are that point, weights 1 and 0)
-                        const i64 i0 = ii[0] + (comp[c].n[0] == 3 ? 0 : a0), i1 = ii[1] + (comp[c].n[1] == 3 ? 0 : a1),
-                                  i2 = ii[2] + (comp[c].n[2] == 3 ? 0 : a2);
-                        ent.push_back({fl.off[c] + i0 * fl.st[c][0] + i1 * fl.st[c][1] + i2 * fl.st[c][2], (int)r,
-                                       fac[c * npts + r] * wg});
-                    }
-        }
+}
+
+// host twins of bspline3_weights / mirror_index (the tables of k_spline_eval_adjoint are built on the host)
+inline void bspline3_weights_host(double t, double w[4]) {
+    w[1] = (t * t * (t - 2.0) * 3.0 + 4.0) / 6.0;
+    const double u = 1.0 - t;
+    w[2] = (u * u * (u - 2.0) * 3.0 + 4.0) / 6.0;
+    w[0] = u * u * u / 6.0;
+    w[3] = 1.0 - w[0] - w[1] - w[2];
+}
+inline i64 mirror_index_host(i64 j, i64 n) {
+    if (n == 1) return 0;
+    const i64 s2 = 2 * n - 2;
+    if (j < 0) {
+        j = s2 * (i64)(-j / s2) + j;
+        j = (j <= 1 - n) ? j + s2 : -j;
+    } else if (j >= n) {
+        j -= s2 * (i64)(j / s2);
+        if (j >= n) j = s2 - j;
     }
+    return j;
+}
+
+// One contribution of a receiver to an entry of the target array.
+struct AdjEntry { i64 idx; int r; double w; };
+
+// The 8 trilinear weights per receiver of component c (as interp3d_device, method 0, on the trimmed points) for every receiver
+// with skip[r] == 0, appended to `ent` with target indices through the layout tl.
+template <class T>
+void linear_adjoint_entries(const RcvComp<T>& C, const FieldLayout& tl, int c, i64 npts, const double* xyz, const double* fac,
+                            const std::vector<char>& skip, std::vector<AdjEntry>& ent) {
+    for (i64 r = 0; r < npts; ++r) {
+        if (skip[r]) continue;
+        i64 ii[3];
+        double tt[3];
+        for (int a = 0; a < 3; ++a) {           // as interp3d_device, method 0
+            const double* g = C.pts[a].data() + 1;
+            const i64 m = C.n[a] - 2;
+            const double v = xyz[a * npts + r];
+            i64 i = (i64)(std::lower_bound(g, g + m, v) - g) - 1;
+            if (i < 0) i = 0;
+            if (i > m - 2) i = m - 2;
+            if (m == 1) { ii[a] = 1; tt[a] = 0.0; continue; }
+            ii[a] = i + 1;
+            tt[a] = (v - g[i]) / (g[i + 1] - g[i]);
+        }
+        for (int a0 = 0; a0 < 2; ++a0)
+            for (int a1 = 0; a1 < 2; ++a1)
+                for (int a2 = 0; a2 < 2; ++a2) {
+                    const double wg = (a0 ? tt[0] : 1 - tt[0]) * (a1 ? tt[1] : 1 - tt[1]) * (a2 ? tt[2] : 1 - tt[2]);
+                    // (an axis with one trimmed point: both corners are that point, weights 1 and 0)
+                    const i64 i0 = ii[0] + (C.n[0] == 3 ? 0 : a0), i1 = ii[1] + (C.n[1] == 3 ? 0 : a1),
+                              i2 = ii[2] + (C.n[2] == 3 ? 0 : a2);
+                    ent.push_back({tl.off[c] + i0 * tl.st[c][0] + i1 * tl.st[c][1] + i2 * tl.st[c][2], (int)r,
+                                   fac[c * npts + r] * wg});
+                }
+    }
+}
+
+// CSR by target index of `ent` (stable: the entries of one index keep their order), uploaded with w; then one thread per touched
+// index: ASSIGN ? k_spline_eval_adjoint (dst[idx] = sum) : k_receiver_adjoint (dst[idx] += sum).  Synchronises the stream.
+template <class T, bool ASSIGN>
+int csr_adjoint_launch(hipStream_t st, std::vector<AdjEntry>& ent, i64 npts, const T* w_host, T* dst) {
     if (ent.empty()) return 0;
-    std::stable_sort(ent.begin(), ent.end(), [](const Entry& a, const Entry& b) { return a.edge < b.edge; });
+    std::stable_sort(ent.begin(), ent.end(), [](const AdjEntry& a, const AdjEntry& b) { return a.idx < b.idx; });
     std::vector<i64> edges;
     std::vector<int> ptr, rcv(ent.size());
     std::vector<double> wgt(ent.size());
     for (size_t q = 0; q < ent.size(); ++q) {
-        if (q == 0 || ent[q].edge != ent[q - 1].edge) { edges.push_back(ent[q].edge); ptr.push_back((int)q); }
+        if (q == 0 || ent[q].idx != ent[q - 1].idx) { edges.push_back(ent[q].idx); ptr.push_back((int)q); }
         rcv[q] = ent[q].r; wgt[q] = ent[q].w;
     }
     ptr.push_back((int)ent.size());
@@ -493,10 +545,129 @@ int receiver_adjoint_device(hipStream_t st, const RcvComp<T> comp[3], const Fiel
     HIP_TRY(hipMemcpyAsync(dw, w_host, (size_t)npts * sizeof(T), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dptr, ptr.data(), (ne + 1) * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(drcv, rcv.data(), nq * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_receiver_adjoint<T>, dim3((unsigned)((ne + EMG_RCV_BLOCK - 1) / EMG_RCV_BLOCK)), dim3(EMG_RCV_BLOCK), 0, st, s,
-                       (const i64*)dedges, (const int*)dptr, (const int*)drcv, (const double*)dwgt, (const T*)dw, (i64)ne);
+    const dim3 grid((unsigned)((ne + EMG_RCV_BLOCK - 1) / EMG_RCV_BLOCK));
+    if (ASSIGN)
+        hipLaunchKernelGGL(k_spline_eval_adjoint<T>, grid, dim3(EMG_RCV_BLOCK), 0, st, dst, (const i64*)dedges, (const int*)dptr,
+                           (const int*)drcv, (const double*)dwgt, (const T*)dw, (i64)ne);
+    else
+        hipLaunchKernelGGL(k_receiver_adjoint<T>, grid, dim3(EMG_RCV_BLOCK), 0, st, dst, (const i64*)dedges, (const int*)dptr,
+                           (const int*)drcv, (const double*)dwgt, (const T*)dw, (i64)ne);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);             // (the host tables and the device block go out of scope)
     if (e != hipSuccess) { fprintf(stderr, "[emg3d_hip] receiver adjoint: %s\n", hipGetErrorString(e)); return (int)e; }
     return 0;
+}
+
+// s (+)= P^T w, P the operator of receiver_response_device(method 0) on the components comp (only n / pts are used; electric
+// edges or magnetic faces), fl the layout of s.  Host: 8 weights per receiver and active component, O(npts log npts); CSR by
+// edge.  A receiver outside the trimmed points of an active component (its datum is NaN) contributes nothing.
+template <class T>
+int receiver_adjoint_device(hipStream_t st, const RcvComp<T> comp[3], const FieldLayout& fl, i64 npts, const double* xyz,
+                            const double* fac, const T* w_host, T* s) {
+    if (npts < 1) return -2;
+    std::vector<AdjEntry> ent;
+    std::vector<char> outside((size_t)npts, 0);
+    bool active[3];
+    for (int c = 0; c < 3; ++c) {
+        active[c] = false;
+        for (i64 r = 0; r < npts; ++r) if (std::fabs(fac[c * npts + r]) > 1e-10) { active[c] = true; break; }
+        if (!active[c]) continue;
+        for (int a = 0; a < 3; ++a) {
+            if (comp[c].n[a] < 3) return -2;
+            const double* g = comp[c].pts[a].data() + 1;
+            const i64 m = comp[c].n[a] - 2;
+            for (i64 r = 0; r < npts; ++r) if (!(xyz[a * npts + r] >= g[0] && xyz[a * npts + r] <= g[m - 1])) outside[r] = 1;
+        }
+    }
+    for (int c = 0; c < 3; ++c)
+        if (active[c]) linear_adjoint_entries<T>(comp[c], fl, c, npts, xyz, fac, outside, ent);
+    return csr_adjoint_launch<T, false>(st, ent, npts, w_host, s);
+}
+
+// s (+)= P^T w, P the operator of receiver_response_device(method 1): per active component
+//     P = R Eval(xi) F_2 F_1 F_0 Trim,       P^T w = Trim^T F_0^T F_1^T F_2^T Eval^T R^T w
+// with the 64 weights fac w0 w1 w2 per receiver scattered into the zeroed coefficient array `coef` (k_spline_eval_adjoint), the
+// transposed prefilter per axis (k_line_ends_scale, k_spline_filter_axis, k_line_ends_scale) and k_trim_add into s.  The rules of
+// the forward operator: a component with fewer than four trimmed points along an axis is linear with fill value 0 (a receiver
+// outside ITS points adds nothing for that component); a receiver whose index coordinates leave [0, n - 1] on an axis of a cubic
+// component has a NaN datum and contributes nothing at all.  coef: >= the largest trimmed component.
+template <class T>
+int receiver_adjoint_cubic_device(hipStream_t st, const RcvComp<T> comp[3], const FieldLayout& fl, i64 npts, const double* xyz,
+                                  const double* fac, const T* w_host, T* coef, T* s) {
+    if (npts < 1) return -2;
+    bool active[3], cubic[3];
+    i64 m[3][3];
+    std::vector<double> co[3];
+    std::vector<char> dead((size_t)npts, 0);
+    for (int c = 0; c < 3; ++c) {
+        active[c] = false;
+        for (i64 r = 0; r < npts; ++r) if (std::fabs(fac[c * npts + r]) > 1e-10) { active[c] = true; break; }
+        if (!active[c]) continue;
+        cubic[c] = true;
+        for (int a = 0; a < 3; ++a) {
+            if (comp[c].n[a] < 3) return -2;
+            m[c][a] = comp[c].n[a] - 2;
+            if (m[c][a] < 4) cubic[c] = false;              // maps.py:238-240
+        }
+        if (!cubic[c]) continue;
+        co[c].resize((size_t)3 * npts);
+        for (int a = 0; a < 3; ++a) {
+            notaknot_index_coords(comp[c].pts[a].data() + 1, m[c][a], xyz + a * npts, npts, co[c].data() + a * npts);
+            for (i64 r = 0; r < npts; ++r) {
+                const double cc = co[c][a * npts + r];
+                if (!(cc >= 0.0 && cc <= (double)(m[c][a] - 1))) dead[r] = 1;
+            }
+        }
+    }
+    // linear components, straight into s
+    std::vector<AdjEntry> ent;
+    for (int c = 0; c < 3; ++c) {
+        if (!active[c] || cubic[c]) continue;
+        std::vector<char> skip(dead);
+        for (int a = 0; a < 3; ++a) {
+            const double* g = comp[c].pts[a].data() + 1;
+            for (i64 r = 0; r < npts; ++r) if (!(xyz[a * npts + r] >= g[0] && xyz[a * npts + r] <= g[m[c][a] - 1])) skip[r] = 1;
+        }
+        linear_adjoint_entries<T>(comp[c], fl, c, npts, xyz, fac, skip, ent);
+    }
+    int rc = csr_adjoint_launch<T, false>(st, ent, npts, w_host, s);
+    for (int c = 0; c < 3 && rc == 0; ++c) {
+        if (!active[c] || !cubic[c]) continue;
+        const i64 m0 = m[c][0], m1 = m[c][1], m2 = m[c][2], tot = m0 * m1 * m2;
+        ent.clear();
+        for (i64 r = 0; r < npts; ++r) {
+            if (dead[r]) continue;
+            i64 idx[3][4];
+            double wt[3][4];
+            for (int a = 0; a < 3; ++a) {           // as spline_point, edge 0
+                const double cc = co[c][a * npts + r];
+                const double flr = std::floor(cc);
+                bspline3_weights_host(cc - flr, wt[a]);
+                const i64 start = (i64)flr - 1;
+                for (int l = 0; l < 4; ++l) idx[a][l] = mirror_index_host(start + l, m[c][a]);
+            }
+            for (int a0 = 0; a0 < 4; ++a0)
+                for (int a1 = 0; a1 < 4; ++a1)
+                    for (int a2 = 0; a2 < 4; ++a2)
+                        ent.push_back({idx[0][a0] + m0 * (idx[1][a1] + m1 * idx[2][a2]), (int)r,
+                                       fac[c * npts + r] * (wt[0][a0] * wt[1][a1] * wt[2][a2])});
+        }
+        if (ent.empty()) continue;
+        HIP_TRY(hipMemsetAsync(coef, 0, (size_t)tot * sizeof(T), st));
+        rc = csr_adjoint_launch<T, true>(st, ent, npts, w_host, coef);
+        if (rc) break;
+        for (int a = 2; a >= 0; --a) {
+            const i64 nl = tot / m[c][a];
+            const dim3 grid((unsigned)((nl + 63) / 64));
+            hipLaunchKernelGGL(k_line_ends_scale<T>, grid, dim3(64), 0, st, coef, m0, m1, m2, a, 2.0);
+            hipLaunchKernelGGL(k_spline_filter_axis<T>, grid, dim3(64), 0, st, coef, m0, m1, m2, a, 0);
+            hipLaunchKernelGGL(k_line_ends_scale<T>, grid, dim3(64), 0, st, coef, m0, m1, m2, a, 0.5);
+        }
+        hipLaunchKernelGGL(k_trim_add<T>, dim3((unsigned)std::min<i64>((tot + 255) / 256, 8192)), dim3(256), 0, st, s, (const T*)coef,
+                           m0, m1, m2, fl.off[c], fl.st[c][0], fl.st[c][1], fl.st[c][2]);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { fprintf(stderr, "[emg3d_hip] cubic receiver adjoint: %s\n", hipGetErrorString(e)); rc = (int)e; }
+    }
+    return rc;
 }

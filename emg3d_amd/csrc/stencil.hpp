@@ -784,6 +784,53 @@ __global__ __launch_bounds__(EMG_BLOCK) void k_hfield(HFieldArgs<T> a) {
 #undef EZ
 #undef ZT
 
+// Transpose of k_hfield without mu_r: s += C^T f, C e = -curl e / (s mu_0), f a face array in k_hfield's output layout.
+// A gather: the thread of an INTERIOR edge sums the four faces around it with the signs and 1/h of k_hfield and adds
+// scl = -1 / (s mu_0) times that sum to its entry of s; the PEC boundary edges are left alone (the trimmed faces of the receiver
+// operators do not reach them).  blockIdx.y: component, thread per edge of it (x fastest).
+template <class T>
+struct HFieldAdjArgs {
+    i64 nC[3];
+    FieldLayout fl;         // layout of s
+    const T* f;             // faces [hx | hy | hz]
+    const double* ih[3];    // 1.0 / h
+    T scl;                  // -1 / (s mu_0)
+    T* s;
+};
+
+template <class T>
+__global__ __launch_bounds__(EMG_BLOCK) void k_hfield_adjoint(HFieldAdjArgs<T> a) {
+    const i64 nx = a.nC[0], ny = a.nC[1], nz = a.nC[2];
+    const i64 nNx = nx + 1, nNy = ny + 1, nNz = nz + 1;
+    const int c = (int)blockIdx.y;
+    const i64 d0 = c == 0 ? nx : nNx, d1 = c == 1 ? ny : nNy, d2 = c == 2 ? nz : nNz;
+    const i64 lin = (i64)blockIdx.x * EMG_BLOCK + threadIdx.x;
+    if (lin >= d0 * d1 * d2) return;
+    i64 i, j, k;
+    unlin3(lin, d0, d1, d2, i, j, k);
+    const T* hx = a.f;
+    const T* hy = hx + nNx * ny * nz;
+    const T* hz = hy + nx * nNy * nz;
+#define HX(i, j, k) hx[(i) + nNx * ((j) + ny * (k))]
+#define HY(i, j, k) hy[(i) + nx * ((j) + nNy * (k))]
+#define HZ(i, j, k) hz[(i) + nx * ((j) + ny * (k))]
+    T g;
+    if (c == 0) {           // E_x (cell i, node j, node k): H_y = dEx/dz - ..., H_z = ... - dEx/dy
+        if (j < 1 || j >= ny || k < 1 || k >= nz) return;
+        g = (HY(i, j, k - 1) * a.ih[2][k - 1] - HY(i, j, k) * a.ih[2][k]) - (HZ(i, j - 1, k) * a.ih[1][j - 1] - HZ(i, j, k) * a.ih[1][j]);
+    } else if (c == 1) {    // E_y (node i, cell j, node k): H_z = dEy/dx - ..., H_x = ... - dEy/dz
+        if (i < 1 || i >= nx || k < 1 || k >= nz) return;
+        g = (HZ(i - 1, j, k) * a.ih[0][i - 1] - HZ(i, j, k) * a.ih[0][i]) - (HX(i, j, k - 1) * a.ih[2][k - 1] - HX(i, j, k) * a.ih[2][k]);
+    } else {                // E_z (node i, node j, cell k): H_x = dEz/dy - ..., H_y = ... - dEz/dx
+        if (i < 1 || i >= nx || j < 1 || j >= ny) return;
+        g = (HX(i, j - 1, k) * a.ih[1][j - 1] - HX(i, j, k) * a.ih[1][j]) - (HY(i - 1, j, k) * a.ih[0][i - 1] - HY(i, j, k) * a.ih[0][i]);
+    }
+#undef HX
+#undef HY
+#undef HZ
+    a.s[a.fl.off[c] + i * a.fl.st[c][0] + j * a.fl.st[c][1] + k * a.fl.st[c][2]] += a.scl * g;
+}
+
 // out = alpha * v for a REAL input array (eta = s mu_0 * (sigma V), models.py:631-658; source
 // s = s mu_0 * vector, fields.py:624): the frequency enters the device problem as one scalar.
 template <class T>

@@ -509,3 +509,34 @@ def get_receiver_response(grid, field, rec, method='cubic'):
                                                _lib.ptr(xyz), _lib.ptr(fac), _lib.ptr(out)),
                "emg3d_get_receiver_response")
     return out
+
+
+def get_receiver_adjoint(grid, rec, w, method='cubic', electric=True, freq=None):
+    """``P^T w`` as an electric source-sized ``Field``: the transpose of the receiver operator ``P`` of
+    ``get_receiver_response(grid, field, rec, method)`` applied to the data-space vector ``w`` (one value per receiver), on the
+    device and without a handle (``emg3d_receiver_adjoint``; with a field in HBM use ``DeviceMG.set_receiver_adjoint``).
+
+    ``electric=False``: magnetic receivers, ``P = P_faces C`` with ``H = C e = -curl e / (s mu_0)`` (no ``mu_r``); needs
+    ``freq``.  ``freq`` < 0 (Laplace domain) takes a real ``w`` and returns a real field; otherwise the field is complex.
+    Receivers with a NaN datum contribute nothing; PEC boundary edges are exact zeros."""
+    if method not in ('cubic', 'linear'):
+        raise ValueError(f"`method` must be 'cubic' or 'linear'; provided: {method!r}.")
+    if not electric and freq is None:
+        raise ValueError("magnetic receivers need `freq` (H = -curl E / (s mu_0)).")
+    from . import _lib
+    n, xyz, fac = _receiver_args(rec)
+    spec = FrequencySpec(freq) if freq is not None else None
+    dtype = np.dtype(np.complex128) if spec is None else spec.dtype
+    if np.iscomplexobj(w) and dtype.kind != 'c':
+        raise TypeError("`w` must be real in the Laplace domain.")
+    wv = np.ascontiguousarray(np.broadcast_to(np.asarray(w), (n,)), dtype=dtype)
+    nx, ny, nz = (int(v) for v in grid.vnC)
+    hx, hy, hz = (np.ascontiguousarray(h, dtype=np.float64) for h in grid.h)
+    origin = np.ascontiguousarray(grid.origin, dtype=np.float64)
+    a = complex(spec.smu0) if not electric else 0j
+    out = np.empty(grid.nE, dtype=dtype)
+    _lib.check(_lib.load().emg3d_receiver_adjoint(_lib.dtype_code(dtype), nx, ny, nz, _lib.ptr(hx), _lib.ptr(hy), _lib.ptr(hz),
+                                                  _lib.ptr(origin), int(bool(electric)), int(method == 'cubic'), a.real, a.imag,
+                                                  n, _lib.ptr(xyz), _lib.ptr(fac), _lib.ptr(wv), _lib.ptr(out)),
+               "emg3d_receiver_adjoint")
+    return Field(grid, out, freq=freq)

@@ -28,7 +28,8 @@ def misfit(synthetic, observed, weights):
     return float(np.nansum(weights * (residual.conj() * residual)).real / 2), residual
 
 
-def gradient(grid, model, src, freq, rec, observed, weights=None, strength=0, device=0, electric=True, **solver_opts):
+def gradient(grid, model, src, freq, rec, observed, weights=None, strength=0, device=0, electric=True, adjoint='reference',
+             **solver_opts):
     """Misfit and adjoint-state gradient with respect to conductivity for one source and frequency (isotropic
     models without ``epsilon_r`` / ``mu_r``: the reference's limitations, optimize.py:160-170).  ``electric=False``:
     magnetic receivers -- the data are responses of ``H = get_h_field(E)``, the residual sources magnetic point dipoles
@@ -44,7 +45,15 @@ def gradient(grid, model, src, freq, rec, observed, weights=None, strength=0, de
     (``maps.grid2grid``, optimize.py:202-211) and applies the property map's ``derivative_chain`` (optimize.py:214):
     the derivative of the misfit with respect to CONDUCTIVITY on this grid is ``-grad`` (what the finite-difference check
     of tests/test_gpu_gradient.py compares with); for a model in another property (resistivity, log-conductivity) the
-    caller applies that map's chain factor, as the reference does.  ``model_gradient()`` below returns that quantity."""
+    caller applies that map's chain factor, as the reference does.  ``model_gradient()`` below returns that quantity.
+
+    ``adjoint='reference'`` (default): the residual source follows the reference's rule, every receiver a 1 m dipole (or loop)
+    SOURCE -- which is not the transpose of the cubic-spline interpolation the data come through, so ``-grad`` is the
+    derivative of the misfit only approximately.  ``adjoint='exact'``: one ``DeviceMG.set_receiver_adjoint(rec, conj(weights *
+    residual), method='cubic')`` builds ``P^T conj(W r)`` with the exact transpose of the receiver operator (electric or
+    magnetic): ``-grad`` is then the derivative of the misfit to the accuracy of the two solves."""
+    if adjoint not in ('reference', 'exact'):
+        raise ValueError(f"`adjoint` must be 'reference' or 'exact'; provided: {adjoint!r}.")
     if getattr(model, 'case', 0) != 0:
         raise NotImplementedError("Gradient only implemented for isotropic models.")
     if getattr(model, 'mu_r', None) is not None or getattr(model, 'epsilon_r', None) is not None:
@@ -70,16 +79,24 @@ def gradient(grid, model, src, freq, rec, observed, weights=None, strength=0, de
         # (simulations.py:1184-1188); magnetic receivers: / s mu_0 once more, loop sources (1190-1197)
         rec = [np.broadcast_to(np.asarray(c, dtype=np.float64), (n,)) for c in rec]
         first = True
-        for i in range(n):
-            if np.isnan(residual[i]):
-                continue
-            st = residual[i].conj() * np.conj(weights[i]) / smu0
-            if not electric:
-                st = st / smu0
-            if st == 0:
-                continue
-            dev.set_source([c[i] for c in rec], smu0, strength=st, accumulate=not first, electric=electric)
-            first = False
+        if adjoint == 'exact':
+            # P^T conj(W r) with the exact transpose of the receiver operator the data came through
+            cw = np.conj(weights * residual)
+            cw = np.where(np.isnan(cw), 0, cw)
+            if np.any(cw != 0):
+                dev.set_receiver_adjoint(rec, cw, method='cubic', magnetic=not electric, smu0=smu0)
+                first = False
+        else:
+            for i in range(n):
+                if np.isnan(residual[i]):
+                    continue
+                st = residual[i].conj() * np.conj(weights[i]) / smu0
+                if not electric:
+                    st = st / smu0
+                if st == 0:
+                    continue
+                dev.set_source([c[i] for c in rec], smu0, strength=st, accumulate=not first, electric=electric)
+                first = False
         if first:
             return phi, np.zeros(grid.vnC, order='F'), dict(synthetic=synthetic, forward=finfo, backward=None)
         rfield = fields.SourceField(grid, freq=freq)
@@ -144,14 +161,23 @@ class Jacobian:
     ``nvec = k > 1``: the handle carries ``k`` systems (``DeviceMG.set_batch``); a product with up to ``k`` vectors runs them through
     the same cycles, each stopping by its own termination test (``solver.solve_sources``), more in groups of ``k`` -- the results
     equal those of one vector at a time bit for bit.  ``solver_opts`` go to the solver (``cycle, semicoarsening, linerelaxation,
-    tol, maxit, ordering, verb, ...``; multigrid only).  Electric receivers, models without ``mu_r`` / ``epsilon_r``."""
+    tol, maxit, ordering, verb, ...``; multigrid only).  Models without ``mu_r`` / ``epsilon_r``.
+
+    ``adjoint='exact'``: with ``'cubic'`` receivers ``jtvec`` applies the exact transpose of the cubic-spline receiver operator
+    (``DeviceMG.set_receiver_adjoint(method='cubic')``) instead of the reference's rule, and ``jvec`` / ``jtvec`` are an adjoint
+    pair; ``'linear'`` is exact either way.  ``electric=False``: magnetic receivers -- the data and ``jvec`` are responses of
+    ``H = get_h_field(E)``, the ``jtvec`` source is ``C^T P_faces^T conj(w)``; they need ``adjoint='exact'`` (the reference's
+    rule for them, loop sources, is not implemented here), with ``'linear'`` or ``'cubic'`` receivers."""
 
     def __init__(self, grid, model, src, freq, rec, receiver_interpolation='linear', nvec=1, strength=0, device=0,
-                 electric=True, **solver_opts):
+                 electric=True, adjoint='reference', **solver_opts):
         if receiver_interpolation not in ('linear', 'cubic'):
             raise ValueError(f"`receiver_interpolation` must be 'linear' or 'cubic'; provided: {receiver_interpolation!r}.")
-        if not electric:
-            raise NotImplementedError("Jacobian: magnetic receivers are not implemented.")
+        if adjoint not in ('reference', 'exact'):
+            raise ValueError(f"`adjoint` must be 'reference' or 'exact'; provided: {adjoint!r}.")
+        if not electric and adjoint != 'exact':
+            raise NotImplementedError("Jacobian: magnetic receivers are implemented with adjoint='exact' only (the reference's "
+                                      "rule, loop sources, is not).")
         if getattr(model, 'mu_r', None) is not None or getattr(model, 'epsilon_r', None) is not None:
             raise NotImplementedError("Jacobian not implemented for el. permittivity / magn. permeability.")
         if int(nvec) != nvec or not 1 <= int(nvec) <= 64:
@@ -165,6 +191,7 @@ class Jacobian:
         self.n_rec = max(np.atleast_1d(c).size for c in rec)
         self.rec = tuple(np.broadcast_to(np.asarray(c, dtype=np.float64), (self.n_rec,)) for c in rec)
         self.receiver_interpolation = receiver_interpolation
+        self.adjoint, self.electric = adjoint, bool(electric)
         self.nvec, self.strength, self.device = int(nvec), strength, device
         self._opts = {k: v for k, v in solver_opts.items() if k not in ('return_info', 'sslsolver')}
         self._spec = fields.FrequencySpec(freq)
@@ -188,7 +215,7 @@ class Jacobian:
             dev.set_source(self.src, smu0, strength=self.strength)
             self.forward_info = self._solve(dev, 1)[0]
             dev.select(0)
-            self.synthetic = dev.get_receiver_response(self.rec, method=self.receiver_interpolation)
+            self.synthetic = self._data(dev)
             dev.vec_alloc(1)
             dev.vec_copy(0, dev.EFIELD)                     # keep the forward field
         except BaseException:
@@ -212,6 +239,12 @@ class Jacobian:
         """Solve the systems 0 .. n-1 of the handle for the sources they hold; the fields stay in HBM."""
         _, infos = solver.solve_sources(self.grid, None, None, self.freq, handle=dev, resident=n, download=False, **self._opts)
         return infos
+
+    def _data(self, dev):
+        """Receiver responses of the selected system's field."""
+        if self.electric:
+            return dev.get_receiver_response(self.rec, method=self.receiver_interpolation)
+        return dev.get_receiver_response(self.rec, magnetic=True, smu0=self._spec.smu0, method=self.receiver_interpolation)
 
     def _require_open(self):
         if self._dev is None:
@@ -269,7 +302,7 @@ class Jacobian:
             infos += self._solve(dev, len(group))
             for b in range(len(group)):
                 dev.select(b)
-                out[g0 + b] = dev.get_receiver_response(self.rec, method=self.receiver_interpolation)
+                out[g0 + b] = self._data(dev)
         self.info = infos[0] if single else infos
         return out[0] if single else out
 
@@ -287,8 +320,9 @@ class Jacobian:
         """Source of the selected system for ``jtvec``."""
         smu0 = self._spec.smu0
         cw = np.where(np.isnan(w), 0, np.conj(w))           # NaN data (receivers outside, missing data) are skipped
-        if self.receiver_interpolation == 'linear':
-            dev.set_receiver_adjoint(self.rec, cw)          # exact transpose of the linear receiver operator
+        if self.receiver_interpolation == 'linear' or self.adjoint == 'exact':
+            # exact transpose of the receiver operator (linear or cubic, on E or on H = C E)
+            dev.set_receiver_adjoint(self.rec, cw, method=self.receiver_interpolation, magnetic=not self.electric, smu0=smu0)
             return
         # 'cubic': the reference's rule, every receiver a 1 m dipole source of strength conj(w) / s mu_0
         # (simulations.py:1171-1213), as gradient() does
@@ -305,8 +339,10 @@ class Jacobian:
         """``J^T w = Re(J^H w)``, a real cell array of shape ``grid.vnC`` (F-ordered); ``components=True``: the three terms
         ``(g_x, g_y, g_z)`` that belong to sigma_x, sigma_y, sigma_z (their sum is the default result).
 
-        With ``receiver_interpolation='linear'`` this is the exact transpose of ``jvec``.  With ``'cubic'`` the right-hand
-        side follows the reference's rule -- every receiver becomes a 1 m dipole SOURCE (emg3d/simulations.py:1171-1213) --, so
+        With ``receiver_interpolation='linear'``, or with ``adjoint='exact'``, this is the exact transpose of ``jvec`` (on the
+        12 x 10 x 8 grid below the cubic pair then agrees as well as the linear one, to the accuracy of the solves; the gradient
+        of ``1/2 sum W |r|^2`` is ``jtvec(W r) == -gradient(..., adjoint='exact')[1]``).  With ``'cubic'`` and the default
+        ``adjoint='reference'`` the right-hand side follows the reference's rule -- every receiver becomes a 1 m dipole SOURCE (emg3d/simulations.py:1171-1213) --, so
         that ``jtvec(weights * residual) == -gradient(...)[1]``; that rule is not the transpose of the cubic-spline
         interpolation which ``jvec`` and the data use, and the two are NOT an adjoint pair: on the 12 x 10 x 8 grid of
         tests/golden/gradient.npz (1.5 Hz, random v and w) ``Re sum(conj(w) J v) = 0.4596`` against ``v . J^T w = 0.1202``, a

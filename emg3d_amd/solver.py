@@ -175,21 +175,27 @@ class DeviceMG:
     def get_receiver_response(self, rec, magnetic=False, smu0=None, mu_r=False, method='cubic'):
         """``fields.get_receiver_response`` (reference fields.py:733-817) of the DEVICE-RESIDENT electric field
         (``magnetic=True``: of ``H = get_h_field(E)``, formed on the device; needs ``smu0``): spline
-        prefilter and evaluation run on the device, 16 bytes per receiver cross PCIe.  ``method='linear'`` (electric only):
-        trilinear interpolation on the same trimmed points, NaN outside (``emg3d_mg_get_receiver_response_linear``)."""
+        prefilter and evaluation run on the device, 16 bytes per receiver cross PCIe.  ``method='linear'``:
+        trilinear interpolation on the same trimmed points, NaN outside (``emg3d_mg_get_receiver_response_linear``,
+        ``..._linear_h`` for magnetic receivers: models without ``mu_r``)."""
         if method not in ('cubic', 'linear'):
             raise ValueError(f"`method` must be 'cubic' or 'linear'; provided: {method!r}.")
         n, xyz, fac = fields._receiver_args(rec)
         out = np.empty(n, dtype=self.dtype)
+        if magnetic and smu0 is None:
+            raise ValueError("magnetic receivers need `smu0` (field.smu0).")
+        a = complex(smu0) if smu0 is not None else 0j
         if method == 'linear':
             if magnetic:
-                raise NotImplementedError("Linear receivers are implemented for the electric field only.")
+                if mu_r:
+                    raise NotImplementedError("Linear magnetic receivers are implemented for models without `mu_r`.")
+                _lib.check(self._lib.emg3d_mg_get_receiver_response_linear_h(self._h, a.real, a.imag, n, _lib.ptr(xyz),
+                                                                             _lib.ptr(fac), _lib.ptr(out)),
+                           "emg3d_mg_get_receiver_response_linear_h")
+                return out
             _lib.check(self._lib.emg3d_mg_get_receiver_response_linear(self._h, n, _lib.ptr(xyz), _lib.ptr(fac), _lib.ptr(out)),
                        "emg3d_mg_get_receiver_response_linear")
             return out
-        a = complex(smu0) if smu0 is not None else 0j
-        if magnetic and smu0 is None:
-            raise ValueError("magnetic receivers need `smu0` (field.smu0).")
         _lib.check(self._lib.emg3d_mg_get_receiver_response(self._h, int(bool(magnetic)), int(bool(mu_r)), a.real,
                                                             a.imag, n, _lib.ptr(xyz), _lib.ptr(fac), _lib.ptr(out)),
                    "emg3d_mg_get_receiver_response")
@@ -227,13 +233,21 @@ class DeviceMG:
             ptrs.append(_lib.ptr(arr))
         _lib.check(self._lib.emg3d_mg_jvec_source(self._h, int(efield_vec), a.real, a.imag, *ptrs), "emg3d_mg_jvec_source")
 
-    def set_receiver_adjoint(self, rec, w, accumulate=False):
-        """Source of the selected system (+)= ``P^T w``, ``P`` the linear receiver operator of
-        ``get_receiver_response(rec, method='linear')`` (``emg3d_mg_set_receiver_adjoint``); ``w``: one value per receiver."""
+    def set_receiver_adjoint(self, rec, w, accumulate=False, method='linear', magnetic=False, smu0=None):
+        """Source of the selected system (+)= ``P^T w``, ``P`` the receiver operator of ``get_receiver_response(rec, method=method,
+        magnetic=magnetic, smu0=smu0)`` -- linear or cubic-spline receivers on the electric field or on ``H = get_h_field(E)``
+        (without ``mu_r``; needs ``smu0``) -- applied on the device (``emg3d_mg_set_receiver_adjoint_ex``); ``w``: one value per
+        receiver.  Receivers with a NaN datum contribute nothing; results repeat bit for bit."""
+        if method not in ('cubic', 'linear'):
+            raise ValueError(f"`method` must be 'cubic' or 'linear'; provided: {method!r}.")
+        if magnetic and smu0 is None:
+            raise ValueError("magnetic receivers need `smu0` (field.smu0).")
         n, xyz, fac = fields._receiver_args(rec)
         wv = np.ascontiguousarray(np.broadcast_to(np.asarray(w), (n,)), dtype=self.dtype)
-        _lib.check(self._lib.emg3d_mg_set_receiver_adjoint(self._h, n, _lib.ptr(xyz), _lib.ptr(fac), _lib.ptr(wv),
-                                                           int(bool(accumulate))), "emg3d_mg_set_receiver_adjoint")
+        a = complex(smu0) if magnetic else 0j
+        _lib.check(self._lib.emg3d_mg_set_receiver_adjoint_ex(self._h, int(method == 'cubic'), int(bool(magnetic)), a.real, a.imag,
+                                                              n, _lib.ptr(xyz), _lib.ptr(fac), _lib.ptr(wv),
+                                                              int(bool(accumulate))), "emg3d_mg_set_receiver_adjoint_ex")
 
     def set_source(self, src, smu0, strength=0, length=1.0, decimals=6, accumulate=False, electric=True):
         """Build the source field ``s mu_0 J_s`` of an electric source IN HBM (``fields.get_source_field``,

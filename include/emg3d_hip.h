@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 106
+#define EMG3D_HIP_ABI_VERSION 107
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -263,6 +263,27 @@ int emg3d_mg_get_receiver_response_linear(emg3d_mg_t* mg, int64_t n, const doubl
  * order -- results repeat bit for bit.                                                                                 */
 int emg3d_mg_set_receiver_adjoint(emg3d_mg_t* mg, int64_t n, const double* xyz, const double* factors, const void* w,
                                   int accumulate);
+/* The linear receivers on H = get_h_field(E) of the selected system's field (without mu_r; formed on the device in the residual
+ * buffer, which is overwritten): resp[r] = sum_c factors[c][r] * (trilinear interpolation of H_c on its trimmed face points).    */
+int emg3d_mg_get_receiver_response_linear_h(emg3d_mg_t* mg, double smu0_re, double smu0_im, int64_t n, const double* xyz,
+                                            const double* factors, void* resp);
+/* Source of the selected system (+)= P^T w for every receiver operator of this library.  method 0: the linear receivers
+ * (emg3d_mg_set_receiver_adjoint is method 0, magnetic 0); method 1: the cubic-spline receivers of
+ * emg3d_mg_get_receiver_response, P = R Eval F_2 F_1 F_0 Trim per component, transposed factor by factor: the 64 stencil weights
+ * per receiver are gathered per touched coefficient of a zeroed trimmed array (host-built table, fixed order), the transposed
+ * B-spline prefilter runs along the three axes (F^T = D F D^-1, D = diag(1/2, 1, ..., 1, 1/2): the forward filter between two
+ * scalings of the line ends), the result is added to the interior of the source.  A component with fewer than four trimmed
+ * points along an axis is linear, as in the forward operator; receivers with a NaN datum contribute nothing.  magnetic != 0: the
+ * receivers act on H = -curl E / (s mu_0) (no mu_r): P^T w is formed on the faces (in the residual buffer, which is overwritten)
+ * and every interior edge gathers its four faces (the transposed curl) times -1 / (s mu_0); smu0 is not used otherwise.  No
+ * atomics: results repeat bit for bit; PEC boundary edges stay exact zeros.                                                  */
+int emg3d_mg_set_receiver_adjoint_ex(emg3d_mg_t* mg, int method, int magnetic, double smu0_re, double smu0_im, int64_t n,
+                                     const double* xyz, const double* factors, const void* w, int accumulate);
+/* The same without a handle (mirrors emg3d_get_receiver_response): field (host, nE values of dtype, [fx|fy|fz]) = P^T w for the
+ * electric (is_electric != 0) or magnetic (needs smu0) component set on the grid (hx, hy, hz, origin).                       */
+int emg3d_receiver_adjoint(int dtype, int64_t nx, int64_t ny, int64_t nz, const double* hx, const double* hy, const double* hz,
+                           const double* origin, int is_electric, int method, double smu0_re, double smu0_im, int64_t n,
+                           const double* xyz, const double* factors, const void* w, void* field);
 
 /* ---- regridding ---------------------------------------------------------------------------------------------------
  * maps._volume_average_weights(x1, x2), reference emg3d/maps.py:526-576, for one axis: x1 (n1 >= 2 edges, old grid) and
