@@ -22,7 +22,7 @@ c_double = ctypes.c_double
 c_dp = ctypes.POINTER(ctypes.c_double)
 
 # include/emg3d_hip.h: EMG3D_HIP_ABI_VERSION -- a library built from another header version is refused at load
-ABI_VERSION = 107
+ABI_VERSION = 108
 
 # name -> (restype, argtypes); mirrors include/emg3d_hip.h one to one.
 SIGNATURES = {
@@ -76,6 +76,9 @@ SIGNATURES = {
     "emg3d_edges2cellaverages": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "emg3d_mg_gradient": (c_int, [c_vp, c_int, c_double, c_double, c_vp]),
     "emg3d_mg_gradient3": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_vp]),
+    "emg3d_mg_grad_acc_reset": (c_int, [c_vp]),
+    "emg3d_mg_grad_acc_add": (c_int, [c_vp, c_int, c_double, c_double, c_vp]),
+    "emg3d_mg_grad_acc_get": (c_int, [c_vp, c_vp]),
     "emg3d_cells2edges": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "emg3d_mg_jvec_source": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_vp]),
     "emg3d_mg_get_receiver_response_linear": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),

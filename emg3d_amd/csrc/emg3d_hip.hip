@@ -1013,6 +1013,34 @@ int emg3d_mg_gradient3(emg3d_mg_t* mg, int efield_vec, double smu0_re, double sm
     return gradient_impl(mg, efield_vec, smu0_re, smu0_im, grad_x, grad_y, grad_z);
 }
 
+int emg3d_mg_grad_acc_reset(emg3d_mg_t* mg) {
+    if (!mg) return -2;
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        const int st = m->grad_acc_reset();
+        return st ? st : finish(m);
+    });
+}
+
+int emg3d_mg_grad_acc_add(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use) {
+    if (!mg || !use) return -2;
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        const int st = m->grad_acc_add(fwd_bvec, smu0_re, smu0_im, use);
+        return st ? st : finish(m);
+    });
+}
+
+int emg3d_mg_grad_acc_get(emg3d_mg_t* mg, double* out) {
+    if (!mg || !out) return -2;
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        if (!m->grad_acc) { const int st = m->grad_acc_reset(); if (st) return st; }
+        HIP_TRY(m->d2h(out, m->grad_acc, (size_t)m->lv0->nCells * sizeof(double)));
+        return finish(m);
+    });
+}
+
 int emg3d_mg_jvec_source(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, const double* vx, const double* vy,
                          const double* vz) {
     if (!mg) return -2;

@@ -2,7 +2,8 @@
 //   k_edges2cell  = maps.edges2cellaverages (reference emg3d/maps.py:578-630): edge values -> volume-weighted cell
 //                   averages, one output array per component;
 //   k_gradient    = optimize.gradient for one (source, frequency) pair on its computational grid (reference
-//                   emg3d/optimize.py:176-199): -Re(lambda E s mu_0) on the edges, mapped to cells, components added.
+//                   emg3d/optimize.py:176-199): -Re(lambda E s mu_0) on the edges, mapped to cells, components added;
+//   k_gradient_acc = the same for all systems of a batch in one launch, added into a per-cell accumulator in system order.
 // Gather form: one thread per CELL sums the contributions of its 12 edges in the order in which the reference's
 // loops (iz, iy, ix ascending, four statements per edge) add them -- deterministic and equal to the reference's
 // accumulation order, no atomics.
@@ -63,6 +64,23 @@ __device__ __forceinline__ double grad_prod(c128 b, c128 e, double sr, double si
     return -(be.re * sr - be.im * si);
 }
 
+// The three components of one cell's gradient value: g[c] = edges2cellaverages_c( -Re(b * e * smu0) ) at cell j.  One body for
+// k_gradient and k_gradient_acc, so that both round (and contract) alike.
+template <class T>
+__device__ __forceinline__ void grad_cell(const i64 j[3], const i64 nC[3], double vol, const FieldLayout& fl, const T* e, const T* b,
+                                          double sr, double si, double g[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const T* ec = e + fl.off[c];
+        const T* bc = b + fl.off[c];
+        const i64 s0 = fl.st[c][0], s1 = fl.st[c][1], s2 = fl.st[c][2];
+        g[c] = e2c_component<double>(c, j, nC, vol, [&](i64 i0, i64 i1, i64 i2) {
+            const i64 o = i0 * s0 + i1 * s1 + i2 * s2;
+            return grad_prod(bc[o], ec[o], sr, si);
+        });
+    }
+}
+
 // grad[cell] = sum_c edges2cellaverages_c( -Re(b * e * smu0) ), vol = (hx*hy)*hz (meshes cell_volumes).
 // SPLIT: the three components go to g0, g1, g2 instead (emg3d_mg_gradient3); their sum (g0 + g1) + g2 is the one-output result.
 template <class T, bool SPLIT>
@@ -75,18 +93,32 @@ __global__ void k_gradient(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* e, c
     const i64 j[3] = {idx % n0, (idx / n0) % n1, idx / (n0 * n1)};
     const double vol = (h0[j[0]] * h1[j[1]]) * h2[j[2]];
     double g[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const T* ec = e + fl.off[c];
-        const T* bc = b + fl.off[c];
-        const i64 s0 = fl.st[c][0], s1 = fl.st[c][1], s2 = fl.st[c][2];
-        g[c] = e2c_component<double>(c, j, nC, vol, [&](i64 i0, i64 i1, i64 i2) {
-            const i64 o = i0 * s0 + i1 * s1 + i2 * s2;
-            return grad_prod(bc[o], ec[o], sr, si);
-        });
-    }
+    grad_cell<T>(j, nC, vol, fl, e, b, sr, si, g);
     if (SPLIT) { g0[idx] = g[0]; g1[idx] = g[1]; g2[idx] = g[2]; }
     else g0[idx] = (g[0] + g[1]) + g[2];          // grad_x + grad_y + grad_z, optimize.py:199
+}
+
+// Survey gradient (optimize.survey_gradient): acc[cell] = (((acc[cell] + g_0) + g_1) + ...) over the systems b = 0 .. nsys-1 (ascending)
+// whose bit is set in `use`, g_b = what k_gradient<T, false> gives for the forward field e + b * nE (slice b of a batched vector) and
+// the back-propagated field bk + b * nE (slice b of the level-0 field array).  One thread per cell, one read and one write of acc, no
+// atomics: the order of the sum is fixed.  Per active system the two fields are read once (2 nE sizeof(T) bytes).
+template <class T>
+__global__ void k_gradient_acc(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* e, const T* bk, i64 nE, int nsys, unsigned long long use,
+                               double sr, double si, const double* h0, const double* h1, const double* h2, double* acc) {
+    const i64 nC[3] = {n0, n1, n2};
+    const i64 n = n0 * n1 * n2;
+    const i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const i64 j[3] = {idx % n0, (idx / n0) % n1, idx / (n0 * n1)};
+    const double vol = (h0[j[0]] * h1[j[1]]) * h2[j[2]];
+    double run = acc[idx];
+    for (int b = 0; b < nsys; ++b) {
+        if (!((use >> b) & 1ull)) continue;
+        double g[3];
+        grad_cell<T>(j, nC, vol, fl, e + (i64)b * nE, bk + (i64)b * nE, sr, si, g);
+        run += (g[0] + g[1]) + g[2];
+    }
+    acc[idx] = run;
 }
 
 // ---- the transpose: cells -> edges (J v of optimize.Jacobian) ---------------------------------------------------------------

@@ -21,6 +21,7 @@
 #include "common.hpp"
 #include "smooth.hpp"
 #include "stencil.hpp"
+#include "gradient.hpp"        // k_gradient_acc (grad_acc_add)
 #include "smooth_qpl.hpp"
 #include "smooth_qc.hpp"
 #include "smooth_thm.hpp"
@@ -878,6 +879,34 @@ struct MG : emg3d_mg {
         if (!broken) residual_launch<T>(0, 1, grid, stream, a);   // pd = 0 - A ps
         MG_LAUNCH(k_negate_b<T>, bgrid_y(vec_grid()), dim3(EMG_BLOCK), 0, stream, pd, L.nE, a.bt);
         touched(dst);
+        check_launch();
+        return err;
+    }
+
+    // ------------------------------------------- survey gradient accumulator (emg3d_mg_grad_acc_*)
+    // nC doubles of the handle's own (not the residual buffer emg3d_mg_gradient stages in): allocated on first use, counted in
+    // `bytes`, freed with the handle; cycles, set_smu0 and set_mask do not touch it.
+    double* grad_acc = nullptr;
+    int grad_acc_reset() {
+        if (!grad_acc) grad_acc = dalloc<double>(lv0->nCells);
+        if (!grad_acc) return err ? err : (int)hipErrorOutOfMemory;
+        hipMemsetAsync(grad_acc, 0, (size_t)lv0->nCells * sizeof(double), stream);
+        return 0;
+    }
+    // acc += g_b for the systems with use[b] != 0, ascending b, in ONE launch (k_gradient_acc): forward fields = batched vector
+    // `fwd_bvec` (a saved copy, not the live field array), back-propagated fields = the level-0 field array.
+    int grad_acc_add(int fwd_bvec, double sr, double si, const int32_t* use) {
+        if (fwd_bvec < 0 || fwd_bvec >= (int)bvecs.size()) return -2;
+        if (!grad_acc) { const int st = grad_acc_reset(); if (st) return st; }
+        Level<T>& L = *lv0;
+        unsigned long long bits = 0;
+        for (int b = 0; b < nsys; ++b) if (use[b]) bits |= 1ull << b;
+        const T* fwd = bvecs[(size_t)fwd_bvec];
+        e_to_ref(L);
+        const T* bwd = L.e;
+        const unsigned blocks = (unsigned)((L.nCells + 255) / 256);
+        MG_LAUNCH(k_gradient_acc<T>, dim3(blocks), dim3(256), 0, stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd, bwd, L.nE, nsys, bits,
+                  sr, si, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], grad_acc);
         check_launch();
         return err;
     }

@@ -11,7 +11,8 @@ containers (xarray; out of scope).  Everything field-sized stays in HBM on ONE h
 of the pair, ``J v`` and ``J^T w``, one multigrid solve each on the operator the forward solve has set up (the reference
 v0.17.0 has the gradient only).
 
-The loop over (source, frequency) pairs belongs to the caller, as in the reference; ``model_gradient(...,
+``survey_gradient`` sums the gradient over the (source, frequency) pairs of a survey: batched forward and back-propagation solves
+on one handle per dtype, the sum over the sources formed on the device (``DeviceMG.grad_acc_add``).  ``model_gradient(...,
 model_grid=)`` maps the gradient to the model grid as the reference does (``maps.grid2grid(grid, -grad, model_grid,
 'cubic')``, optimize.py:201-211) and applies the chain rule there.
 """
@@ -104,6 +105,186 @@ def gradient(grid, model, src, freq, rec, observed, weights=None, strength=0, de
                                 download=False, **opts)
         grad = dev.gradient(0, smu0).reshape(grid.vnC, order='F')
     return phi, grad, dict(synthetic=synthetic, forward=finfo, backward=binfo)
+
+
+def _sum_survey(partials, misfits, vnC):
+    """The defined order of the survey sums: ``grad = ((0 + G_0) + G_1) + ...`` over the frequencies as given, ``phi`` the
+    sequential sum of ``misfits[i_src, i_freq]`` with the frequency as the outer and the source as the inner loop."""
+    grad = np.zeros(vnC, order='F')
+    phi = 0.0
+    misfits = np.asarray(misfits)
+    for j, g in enumerate(partials):
+        grad = grad + np.asarray(g).reshape(vnC, order='F')
+        for i in range(misfits.shape[0]):
+            phi = phi + float(misfits[i, j])
+    return phi, grad
+
+
+def survey_gradient(grid, model, sources, freqs, rec, observed, weights=None, strength=0, device=0, electric=True,
+                    adjoint='reference', batch=8, **solver_opts):
+    """Misfit and adjoint-state gradient of a SURVEY -- every source of ``sources`` at every frequency of ``freqs`` -- on the
+    computational grid: what the reference's ``simulation.gradient`` (emg3d/optimize.py:115-217) sums over its (source, frequency)
+    pairs, i.e. the sum of ``gradient()`` over the pairs, without a handle, a hierarchy and an ``nC``-sized download per pair.
+
+    ``observed[i_src, i_freq, i_rec]`` are the data (NaN: no datum), ``weights`` broadcastable to that shape (default 1);
+    ``rec``, ``strength``, ``electric``, ``adjoint``, the model limits and the ``solver_opts`` (multigrid only) are those of
+    ``gradient()``.  Frequencies < 0 are Laplace-domain values and may be mixed with frequencies; their data are real.
+
+    One handle per dtype carries ``min(batch, n_src)`` systems and is re-targeted from frequency to frequency
+    (``DeviceMG.set_smu0``).  Per frequency the sources go through in chunks of that size (a shorter last chunk with the surplus
+    systems frozen): batched forward solve, data per system, ``misfit()`` per pair on the host, the forward fields parked with one
+    ``bvec_copy``, the residual source of every system built as ``gradient()`` builds it, batched back-propagation solve, then ONE
+    ``grad_acc_add`` adds the chunk's gradients on the device.  A pair without a usable datum gets no adjoint solve (its
+    ``backward`` info is None).  Nothing field-sized crosses PCIe; one ``nC``-sized array comes back per frequency.
+
+    SUMMATION ORDER (part of the contract): ``G_f``, the gradient of frequency ``f``, is the sequential sum over the sources in
+    ascending order starting from zero, formed by the kernel; ``grad`` is the sequential sum of the ``G_f`` in the order of
+    ``freqs`` starting from zeros, formed on the host; ``phi`` is the sum of the per-pair misfits in the same order (frequency
+    outer, source inner).  The results do not depend on ``batch``, bit for bit.
+
+    Returns ``(phi, grad, info)``: ``grad`` (shape ``grid.vnC``) is the sum over the pairs of ``gradient()``'s ``grad``, in its
+    sign convention -- ``model_gradient(grid, model, grad, model_grid)`` maps it to the model grid unchanged.  ``info``:
+    ``synthetic`` ``(n_src, n_freq, n_rec)``, ``misfit`` ``(n_src, n_freq)``, ``partial`` the ``G_f`` with shape ``(n_freq,) +
+    vnC`` (F-ordered; the unit of exchange of ``shard.gather_survey_gradient``), ``forward[i][j]`` / ``backward[i][j]`` the solver
+    info dicts, ``phases`` host seconds spent in the forward solves, the data, the adjoint sources, the backward solves and the
+    accumulation."""
+    import time
+    if adjoint not in ('reference', 'exact'):
+        raise ValueError(f"`adjoint` must be 'reference' or 'exact'; provided: {adjoint!r}.")
+    if getattr(model, 'case', 0) != 0:
+        raise NotImplementedError("Gradient only implemented for isotropic models.")
+    if getattr(model, 'mu_r', None) is not None or getattr(model, 'epsilon_r', None) is not None:
+        raise NotImplementedError("Gradient not implemented for el. permittivity / magn. permeability.")
+    if solver_opts.get('sslsolver'):
+        raise NotImplementedError("survey_gradient: resident sources are solved by multigrid only; Krylov solvers are not "
+                                  "implemented.")
+    if int(batch) != batch or not 1 <= int(batch) <= 64:
+        raise ValueError(f"`batch` must be an integer from 1 to 64; provided: {batch!r}.")
+    if len(rec) != 5:
+        raise ValueError("`rec` needs to be in the form (x, y, z, azimuth, dip).\n"
+                         f"Length of provided `rec`: {len(rec)}.")
+    sources = list(sources)
+    freqs = [float(f) for f in freqs]
+    ns, nf = len(sources), len(freqs)
+    if ns < 1:
+        raise ValueError("survey_gradient: no sources.")
+    nrec = max(np.atleast_1d(c).size for c in rec)
+    rec = tuple(np.broadcast_to(np.asarray(c, dtype=np.float64), (nrec,)) for c in rec)
+    observed = np.asarray(observed)
+    if observed.shape != (ns, nf, nrec):
+        raise ValueError(f"`observed` must have shape (n_src, n_freq, n_rec) = {(ns, nf, nrec)}; provided: {observed.shape}.")
+    try:
+        weights = np.ones(observed.shape) if weights is None else np.broadcast_to(np.asarray(weights), observed.shape)
+    except ValueError:
+        raise ValueError(f"`weights` must be broadcastable to the shape of `observed` {observed.shape}; "
+                         f"provided: {np.shape(weights)}.") from None
+    specs = [fields.FrequencySpec(f) for f in freqs]
+    opts = {k: v for k, v in solver_opts.items() if k not in ('return_info', 'sslsolver')}
+    vnC = tuple(int(n) for n in grid.vnC)
+    nb = min(int(batch), ns)
+    cplx = any(sp.dtype.kind == 'c' for sp in specs)
+    synthetic = np.full((ns, nf, nrec), np.nan, dtype=np.complex128 if cplx else np.float64)
+    misfits = np.zeros((ns, nf))
+    partial = np.zeros((nf,) + vnC[::-1]).transpose(0, 3, 2, 1)         # (n_freq,) + vnC, every G_f F-ordered
+    finfo = [[None] * nf for _ in range(ns)]
+    binfo = [[None] * nf for _ in range(ns)]
+    phases = dict(forward=0.0, data=0.0, adjoint_sources=0.0, backward=0.0, accumulate=0.0)
+
+    def lap(name, t0):
+        t1 = time.perf_counter()
+        phases[name] += t1 - t0
+        return t1
+
+    parts = models.model_parts(grid, model, raw=True)
+    handles = {}
+    try:
+        for j, spec in enumerate(specs):
+            smu0 = spec.smu0
+            key = spec.dtype.str
+            dev = handles.get(key)
+            if dev is None:
+                dev = handles[key] = solver.DeviceMG.from_model_parts(grid, *parts, smu0=smu0, device=device)
+                if nb > 1:
+                    dev.set_batch(nb)
+                dev.bvec_alloc(1)
+                dev._smu0 = smu0
+            elif dev._smu0 != smu0:
+                dev.set_smu0(smu0, sval=spec.sval)
+                dev._smu0 = smu0
+            real = spec.dtype.kind != 'c'
+            dev.grad_acc_reset()
+            for i0 in range(0, ns, nb):
+                n = min(nb, ns - i0)
+                t = time.perf_counter()
+                # 1. forward solve of the chunk's sources, built in HBM
+                for b in range(n):
+                    dev.select(b)
+                    dev.set_source(sources[i0 + b], smu0, strength=strength)
+                _, infos = solver.solve_sources(grid, None, None, freqs[j], handle=dev, resident=n, download=False, **opts)
+                t = lap('forward', t)
+                # 2. + 3. data and misfit per pair
+                residuals = []
+                for b in range(n):
+                    finfo[i0 + b][j] = infos[b]
+                    dev.select(b)
+                    syn = dev.get_receiver_response(rec) if electric else dev.get_receiver_response(rec, magnetic=True, smu0=smu0)
+                    obs = observed[i0 + b, j].real if real else observed[i0 + b, j]
+                    synthetic[i0 + b, j] = syn
+                    misfits[i0 + b, j], r = misfit(syn, obs, weights[i0 + b, j])
+                    residuals.append(r)
+                t = lap('data', t)
+                # 4. park the forward fields of the chunk (the solve has left all but the last system to finish frozen)
+                mask = np.zeros(nb, dtype=np.int32)
+                mask[:n] = 1
+                dev.set_mask(mask)
+                dev.bvec_copy(0, dev.EFIELD)
+                # 5. residual sources, per system exactly as gradient() builds them
+                use = np.zeros(nb, dtype=np.int32)
+                for b in range(n):
+                    dev.select(b)
+                    w, r = weights[i0 + b, j], residuals[b]
+                    first = True
+                    if adjoint == 'exact':
+                        cw = np.conj(w * r)
+                        cw = np.where(np.isnan(cw), 0, cw)
+                        if np.any(cw != 0):
+                            dev.set_receiver_adjoint(rec, cw, method='cubic', magnetic=not electric, smu0=smu0)
+                            first = False
+                    else:
+                        for k in range(nrec):
+                            if np.isnan(r[k]):
+                                continue
+                            st = r[k].conj() * np.conj(w[k]) / smu0
+                            if not electric:
+                                st = st / smu0
+                            if st == 0:
+                                continue
+                            dev.set_source([c[k] for c in rec], smu0, strength=st, accumulate=not first, electric=electric)
+                            first = False
+                    if first:
+                        dev.vec_scale(dev.SFIELD, 0.0)          # no usable datum: a zero source, frozen by the solve
+                    else:
+                        use[b] = 1
+                t = lap('adjoint_sources', t)
+                if not use.any():
+                    continue
+                # 6. back-propagation solve of the chunk
+                _, infos = solver.solve_sources(grid, None, None, freqs[j], handle=dev, resident=n, download=False, **opts)
+                for b in range(n):
+                    if use[b]:
+                        binfo[i0 + b][j] = infos[b]
+                t = lap('backward', t)
+                # 7. G_f += the chunk's gradients, in system order
+                dev.grad_acc_add(0, smu0, use)
+                t = lap('accumulate', t)
+            t = time.perf_counter()
+            partial[j] = dev.grad_acc_get().reshape(vnC, order='F')
+            lap('accumulate', t)
+    finally:
+        for dev in handles.values():
+            dev.close()
+    phi, grad = _sum_survey(partial, misfits, vnC)
+    return phi, grad, dict(synthetic=synthetic, misfit=misfits, partial=partial, forward=finfo, backward=binfo, phases=phases)
 
 
 def model_gradient(grid, model, grad, model_grid=None):

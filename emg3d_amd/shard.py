@@ -172,6 +172,71 @@ def gather_survey(resp_local, freqs, group=None):
     return out
 
 
+def combine_survey_gradient(per_rank, n_freq):
+    """The sums of a frequency-sharded survey gradient: ``per_rank[r] = (partial_r, misfit_r)`` holds what
+    ``optimize.survey_gradient`` returned on rank ``r`` for ``my_frequencies(freqs, r, world)`` -- ``info['partial']`` with shape
+    ``(n_r,) + vnC`` and ``info['misfit']`` with shape ``(n_src, n_r)``.  The per-frequency partials ``G_f`` and the per-pair
+    misfits are put back in the order of ``freqs`` (frequency ``r + j * world`` is rank ``r``'s ``j``-th) and summed in that
+    order, exactly as ``survey_gradient`` sums them: ``(phi, grad)`` is bit for bit the single-process result for any world
+    size."""
+    from emg3d_amd import optimize
+    world = len(per_rank)
+    partials, misfits = [None] * int(n_freq), [None] * int(n_freq)
+    vnC = None
+    for r, (p, m) in enumerate(per_rank):
+        p, m = np.asarray(p), np.asarray(m)
+        if p.ndim != 4 or m.ndim != 2 or m.shape[1] != p.shape[0]:
+            raise ValueError(f"combine_survey_gradient: rank {r}: partials of shape {p.shape}, misfits of shape {m.shape}.")
+        vnC = tuple(p.shape[1:]) if vnC is None else vnC
+        for j in range(p.shape[0]):
+            if r + j * world >= n_freq:
+                raise ValueError(f"combine_survey_gradient: rank {r} of {world} holds {p.shape[0]} of {n_freq} frequencies.")
+            partials[r + j * world], misfits[r + j * world] = p[j], m[:, j]
+    if any(p is None for p in partials):
+        raise ValueError(f"combine_survey_gradient: the ranks hold {sum(p is not None for p in partials)} of {n_freq} frequencies.")
+    if vnC is None:
+        raise ValueError("combine_survey_gradient: no rank.")
+    mis = np.stack(misfits, axis=1) if n_freq else np.zeros((np.asarray(per_rank[0][1]).shape[0], 0))
+    return optimize._sum_survey(partials, mis, vnC)
+
+
+def gather_survey_gradient(partial_local, misfit_local, freqs, group=None):
+    """End-of-run exchange of a frequency-sharded survey gradient: every rank has run ``optimize.survey_gradient`` on ITS
+    frequencies ``my_frequencies(freqs, rank, world)`` with its slice ``observed[:, rank::world, :]`` and passes
+    ``info['partial']`` (``(n_mine,) + vnC``) and ``info['misfit']`` (``(n_src, n_mine)``; a rank without frequencies passes the
+    empty arrays it got).  One header and one payload collective of host arrays (``gather_fields``): per frequency ``nC +
+    n_src`` doubles.  Every rank then sums the partials and the misfits in the order of ``freqs``
+    (``combine_survey_gradient``) and returns ``(phi, grad)`` -- identical on every rank and bit for bit the single-process
+    result, whatever the world size: that is why the per-frequency partials, not per-rank sums, are exchanged.  Without an
+    initialised process group the local arrays are summed.  No device collective."""
+    import torch.distributed as dist
+    freqs = [float(f) for f in freqs]
+    partial_local, misfit_local = np.asarray(partial_local, dtype=np.float64), np.asarray(misfit_local, dtype=np.float64)
+    if partial_local.ndim != 4 or misfit_local.ndim != 2 or misfit_local.shape[1] != partial_local.shape[0]:
+        raise ValueError("gather_survey_gradient: `partial_local` must have shape (n_mine, nx, ny, nz) and `misfit_local` "
+                         f"(n_src, n_mine); provided: {partial_local.shape}, {misfit_local.shape}.")
+    if not (dist.is_available() and dist.is_initialized()):
+        return combine_survey_gradient([(partial_local, misfit_local)], partial_local.shape[0])
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    n_mine = len(my_frequencies(freqs, rank, world))
+    if partial_local.shape[0] != n_mine:
+        raise ValueError(f"gather_survey_gradient: rank {rank} owns {n_mine} frequencies, got partials of shape "
+                         f"{partial_local.shape}.")
+    vnC, ns = tuple(partial_local.shape[1:]), misfit_local.shape[0]
+    nC = int(np.prod(vnC))
+    local = [np.concatenate([partial_local[j].ravel(order='F'), misfit_local[:, j]]) for j in range(n_mine)]
+    got = gather_fields(local, group=group)
+    per_rank = []
+    for r in range(world):
+        p = np.zeros((len(got[r]),) + vnC[::-1]).transpose(0, 3, 2, 1)
+        m = np.zeros((ns, len(got[r])))
+        for j, a in enumerate(got[r]):
+            p[j] = a[:nC].reshape(vnC, order='F')
+            m[:, j] = a[nC:]
+        per_rank.append((p, m))
+    return combine_survey_gradient(per_rank, len(freqs))
+
+
 def gather_fields(local, group=None, device=None):
     """All-gather equally sized 1-D field arrays (complex128/float64).
 

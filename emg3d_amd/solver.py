@@ -216,6 +216,31 @@ class DeviceMG:
                    "emg3d_mg_gradient")
         return out
 
+    # ---- survey gradient: the gradients of all systems of a batch, summed on the device (optimize.survey_gradient) ----
+    def grad_acc_reset(self):
+        """Zero the handle's gradient accumulator (``nC`` doubles of its own, allocated on first use; cycles, ``set_smu0`` and
+        ``set_mask`` leave it alone)."""
+        _lib.check(self._lib.emg3d_mg_grad_acc_reset(self._h), "emg3d_mg_grad_acc_reset")
+
+    def grad_acc_add(self, fwd_bvec, smu0, use):
+        """``acc = (((acc + g_0) + g_1) + ...)`` over the systems ``b`` with ``use[b] != 0`` in ascending order, in one launch:
+        ``g_b`` is bit for bit ``gradient()`` of system ``b`` -- forward field = slice ``b`` of the batched vector ``fwd_bvec``
+        (``bvec_copy(fwd_bvec, EFIELD)``; not the live field), back-propagated field = system ``b``'s field."""
+        a = complex(smu0)
+        u = np.ascontiguousarray(use, dtype=np.int32)
+        if u.size != self.nsys:
+            raise ValueError(f"grad_acc_add: {u.size} flags for {self.nsys} systems.")
+        st = self._lib.emg3d_mg_grad_acc_add(self._h, int(fwd_bvec), a.real, a.imag, _lib.ptr(u))
+        if st == -2:
+            raise ValueError(f"grad_acc_add: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy).")
+        _lib.check(st, "emg3d_mg_grad_acc_add")
+
+    def grad_acc_get(self):
+        """The accumulator: ``nC`` doubles, F-ordered."""
+        out = np.empty(self.nC, dtype=np.float64)
+        _lib.check(self._lib.emg3d_mg_grad_acc_get(self._h, _lib.ptr(out)), "emg3d_mg_grad_acc_get")
+        return out
+
     def jvec_source(self, efield_vec, smu0, vx, vy, vz):
         """Source of the selected system <- ``s mu_0 C(v) E`` (``emg3d_mg_jvec_source``): ``E`` = workspace vector
         ``efield_vec``, ``vx, vy, vz`` conductivity perturbations per direction (``nC`` values, F-ordered; ``None``: none)."""

@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 107
+#define EMG3D_HIP_ABI_VERSION 108
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -235,6 +235,21 @@ int emg3d_mg_gradient(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu
  * emg3d_mg_gradient's result bit for bit.                                                                               */
 int emg3d_mg_gradient3(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, double* grad_x, double* grad_y,
                        double* grad_z);
+
+/* Survey gradient (optimize.survey_gradient): the gradients of ALL systems of a batched handle, summed on the device.  The
+ * accumulator is a buffer of nC doubles of the handle's own (NOT the residual buffer emg3d_mg_gradient stages in): allocated on
+ * first use, counted by emg3d_mg_device_bytes, freed with the handle; cycles, emg3d_mg_set_smu0 and emg3d_mg_set_mask leave it alone.
+ *   grad_acc_reset: allocates the accumulator if need be and zeroes it.
+ *   grad_acc_add  : acc = (((acc + g_0) + g_1) + ...) over the systems b = 0 .. nsys-1 in ascending order with use[b] != 0
+ *                   (use: nsys flags), in ONE launch, one read and one write of acc per cell, no atomics; g_b is bit for bit what
+ *                   emg3d_mg_gradient returns for system b -- forward field = slice b of the batched vector `fwd_bvec` (saved with
+ *                   emg3d_mg_bvec_copy(id, -2); -2 for a bad id or fwd_bvec < 0: a saved copy, not the live field, as
+ *                   emg3d_mg_gradient asks), back-propagated field = slice b of the level-0 field array.  Works on handles
+ *                   with one system too.
+ *   grad_acc_get  : the accumulator, nC doubles, F-ordered.                                                             */
+int emg3d_mg_grad_acc_reset(emg3d_mg_t* mg);
+int emg3d_mg_grad_acc_add(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use);
+int emg3d_mg_grad_acc_get(emg3d_mg_t* mg, double* out);
 
 /* ---- sensitivity products (optimize.Jacobian) --------------------------------------------------------------------
  * The reference (v0.17.0) has the gradient only; these are the pieces of J v and J^T w with J = d(data) / d(conductivity) for
