@@ -22,7 +22,7 @@ c_double = ctypes.c_double
 c_dp = ctypes.POINTER(ctypes.c_double)
 
 # include/emg3d_hip.h: EMG3D_HIP_ABI_VERSION -- a library built from another header version is refused at load
-ABI_VERSION = 108
+ABI_VERSION = 109
 
 # name -> (restype, argtypes); mirrors include/emg3d_hip.h one to one.
 SIGNATURES = {
@@ -79,12 +79,17 @@ SIGNATURES = {
     "emg3d_mg_grad_acc_reset": (c_int, [c_vp]),
     "emg3d_mg_grad_acc_add": (c_int, [c_vp, c_int, c_double, c_double, c_vp]),
     "emg3d_mg_grad_acc_get": (c_int, [c_vp, c_vp]),
+    "emg3d_mg_grad_acc3_reset": (c_int, [c_vp]),
+    "emg3d_mg_grad_acc3_add": (c_int, [c_vp, c_int, c_double, c_double, c_vp]),
+    "emg3d_mg_grad_acc3_get": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "emg3d_cells2edges": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "emg3d_mg_jvec_source": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_vp]),
+    "emg3d_mg_jvec_source_b": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_vp, c_vp]),
     "emg3d_mg_get_receiver_response_linear": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "emg3d_mg_set_receiver_adjoint": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_int]),
     "emg3d_mg_get_receiver_response_linear_h": (c_int, [c_vp, c_double, c_double, c_i64, c_vp, c_vp, c_vp]),
     "emg3d_mg_set_receiver_adjoint_ex": (c_int, [c_vp, c_int, c_int, c_double, c_double, c_i64, c_vp, c_vp, c_vp, c_int]),
+    "emg3d_mg_set_receiver_adjoint_b": (c_int, [c_vp, c_int, c_int, c_double, c_double, c_i64, c_vp, c_vp, c_vp, c_vp, c_int]),
     "emg3d_receiver_adjoint": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_double, c_double,
                                        c_i64, c_vp, c_vp, c_vp, c_vp]),
     "emg3d_volume_average_weights": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -539,6 +539,26 @@ static int sweep_plan_impl(i64 nx, i64 ny, i64 nz, int dir, int order, int nsys,
     return 0;
 }
 
+// the perturbations (up to 3 nC doubles) are staged in the residual buffer (3 nC * 8 < nE * sizeof(T)); the same host array for
+// several directions is uploaded once
+template <class T>
+static int jvec_stage(MG<T>* m, const double* const hv[3], const double* dv[3]) {
+    Level<T>& L = *m->lv0;
+    double* stage = reinterpret_cast<double*>(L.r);
+    const i64 n = L.nCells;
+    int used = 0;
+    for (int c = 0; c < 3; ++c) {
+        dv[c] = nullptr;
+        if (!hv[c]) continue;
+        for (int q = 0; q < c; ++q) if (hv[q] == hv[c]) dv[c] = dv[q];
+        if (dv[c]) continue;
+        double* d = stage + (i64)used++ * n;
+        HIP_TRY(hipMemcpyAsync(d, hv[c], (size_t)n * sizeof(double), hipMemcpyHostToDevice, m->stream));
+        dv[c] = d;
+    }
+    return 0;
+}
+
 template <class T>
 static int jvec_source_impl(MG<T>* m, int efield_vec, double smu0_re, double smu0_im, const double* vx, const double* vy,
                             const double* vz) {
@@ -547,21 +567,9 @@ static int jvec_source_impl(MG<T>* m, int efield_vec, double smu0_re, double smu
     Level<T>& L = *m->lv0;
     const T* fwd = m->vec(efield_vec);
     if (!fwd || efield_vec < 0) return -2;             // a workspace vector: the source of the selected system is written
-    // the perturbations (up to 3 nC doubles) are staged in the residual buffer (3 nC * 8 < nE * sizeof(T)); the same host
-    // array for several directions is uploaded once
-    double* stage = reinterpret_cast<double*>(L.r);
     const double* hv[3] = {vx, vy, vz};
-    const double* dv[3] = {nullptr, nullptr, nullptr};
-    const i64 n = L.nCells;
-    int used = 0;
-    for (int c = 0; c < 3; ++c) {
-        if (!hv[c]) continue;
-        for (int q = 0; q < c; ++q) if (hv[q] == hv[c]) dv[c] = dv[q];
-        if (dv[c]) continue;
-        double* d = stage + (i64)used++ * n;
-        HIP_TRY(hipMemcpyAsync(d, hv[c], (size_t)n * sizeof(double), hipMemcpyHostToDevice, m->stream));
-        dv[c] = d;
-    }
+    const double* dv[3];
+    { const int st = jvec_stage<T>(m, hv, dv); if (st) return st; }
     T* s = m->sel_s();
     if (m->broken) return (int)hipErrorOutOfMemory;
     hipLaunchKernelGGL(k_jvec_source<T>, dim3((unsigned)((L.nE + 255) / 256)), dim3(256), 0, m->stream, L.nC[0], L.nC[1], L.nC[2],
@@ -571,6 +579,31 @@ static int jvec_source_impl(MG<T>* m, int efield_vec, double smu0_re, double smu
     m->lv0->s_dense = true;         // (every line carries a source: no point in scanning it for zeros)
     m->check_launch();
     return finish(m);               // (synchronises: the host arrays have been read)
+}
+
+// emg3d_mg_jvec_source_b: one launch writes the sources of all systems with use[b] != 0 (forward fields: the batched vector fwd_bvec)
+template <class T>
+static int jvec_source_b_impl(MG<T>* m, int fwd_bvec, double smu0_re, double smu0_im, const double* vx, const double* vy,
+                              const double* vz, const int32_t* use) {
+    if (sizeof(T) == 8 && smu0_im != 0.0) return -2;
+    HIP_TRY(hipSetDevice(m->device));
+    Level<T>& L = *m->lv0;
+    if (fwd_bvec < 0 || fwd_bvec >= (int)m->bvecs.size()) return -2;       // a saved copy, as grad_acc_add asks
+    const T* fwd = m->bvecs[(size_t)fwd_bvec];
+    unsigned long long bits = 0;
+    for (int b = 0; b < m->nsys; ++b) if (use[b]) bits |= 1ull << b;
+    if (!bits) return 0;
+    const double* hv[3] = {vx, vy, vz};
+    const double* dv[3];
+    { const int st = jvec_stage<T>(m, hv, dv); if (st) return st; }
+    if (m->broken) return (int)hipErrorOutOfMemory;
+    hipLaunchKernelGGL(k_jvec_source_b<T>, dim3((unsigned)((L.nE + 255) / 256)), dim3(256), 0, m->stream, L.nC[0], L.nC[1], L.nC[2],
+                       L.fl, fwd, m->nsys, bits, smu0_re, smu0_im, dv[0], dv[1], dv[2], (const double*)L.h[0], (const double*)L.h[1],
+                       (const double*)L.h[2], L.s, L.nE);
+    m->source_changed();
+    m->lv0->s_dense = true;
+    m->check_launch();
+    return finish(m);
 }
 
 // one output (gy == gz == NULL: grad = (g_x + g_y) + g_z) or the three components
@@ -632,28 +665,29 @@ static int cells2edges_impl(const i64 nC[3], const void* const v[3], const doubl
     return 0;
 }
 
-// s of the selected system (+)= P^T w: emg3d_mg_set_receiver_adjoint_ex (include/emg3d_hip.h)
+// The transposed receiver operator of a handle's level 0 (emg3d_mg_set_receiver_adjoint_ex / _b, include/emg3d_hip.h): the tables
+// are built once (build), then `apply` issues the kernels that add P^T w to a source array s for a device-resident data vector --
+// electric: straight into s; magnetic: P_faces^T w on the face arrays [hx | hy | hz] in the residual buffer (scratch between calls,
+// nH < nE), then the transposed curl into s.  No host work and no synchronisation in apply.
 template <class T>
-int receiver_adjoint_impl(MG<T>* m, int method, int magnetic, double sr, double si, i64 n, const double* xyz, const double* fac,
-                          const T* w, int accumulate) {
-    HIP_TRY(hipSetDevice(m->device));
-    auto& L = *m->lv0;
-    if (L.nC[0] < 3 || L.nC[1] < 3 || L.nC[2] < 3) return -2;
-    if (magnetic && sizeof(T) == 8 && si != 0.0) return -2;
-    if (method == 1 && !m->scratch_field) m->scratch_field = m->template dalloc<T>(L.nE);
-    if (m->broken) return (int)hipErrorOutOfMemory;
-    if (!accumulate) HIP_TRY(hipMemsetAsync(m->sel_s(), 0, (size_t)L.nE * sizeof(T), m->stream));
-    m->source_changed();
-    RcvComp<T> comp[3];
-    int rc;
-    if (!magnetic) {
-        receiver_components<T>(L.nodes, L.centers, L.nC, true, m->sel_s(), comp);
-        rc = method ? receiver_adjoint_cubic_device<T>(m->stream, comp, L.fl, n, xyz, fac, w, m->scratch_field, m->sel_s())
-                    : receiver_adjoint_device<T>(m->stream, comp, L.fl, n, xyz, fac, w, m->sel_s());
-    } else {
-        // P_faces^T w on the face arrays [hx | hy | hz] in the residual buffer (scratch between calls, nH < nE), then C^T
-        T* faces = L.r;
-        HIP_TRY(hipMemsetAsync(faces, 0, (size_t)hfield_size(L.nC) * sizeof(T), m->stream));
+struct MgRcvAdjoint {
+    RcvAdjPlan<T> plan;
+    bool magnetic = false;
+    HFieldAdjArgs<T> ha;
+    unsigned hblocks = 0;
+    T* faces = nullptr;
+    size_t faces_bytes = 0;
+
+    int build(MG<T>* m, int method, int mag, double sr, double si, i64 n, const double* xyz, const double* fac) {
+        auto& L = *m->lv0;
+        magnetic = mag != 0;
+        RcvComp<T> comp[3];
+        if (!magnetic) {
+            receiver_components<T>(L.nodes, L.centers, L.nC, true, L.s, comp);
+            return plan.build(m->stream, method, comp, L.fl, n, xyz, fac);
+        }
+        faces = L.r;
+        faces_bytes = (size_t)hfield_size(L.nC) * sizeof(T);
         receiver_components<T>(L.nodes, L.centers, L.nC, false, faces, comp);
         FieldLayout hl;
         i64 o = 0;
@@ -662,25 +696,59 @@ int receiver_adjoint_impl(MG<T>* m, int method, int magnetic, double sr, double 
             hl.st[c][0] = 1; hl.st[c][1] = comp[c].n[0]; hl.st[c][2] = comp[c].n[0] * comp[c].n[1];
             o += comp[c].n[0] * comp[c].n[1] * comp[c].n[2];
         }
-        rc = method ? receiver_adjoint_cubic_device<T>(m->stream, comp, hl, n, xyz, fac, w, m->scratch_field, faces)
-                    : receiver_adjoint_device<T>(m->stream, comp, hl, n, xyz, fac, w, faces);
-        if (rc == 0) {
-            HFieldAdjArgs<T> a;
-            i64 big = 0;
-            for (int q = 0; q < 3; ++q) {
-                a.nC[q] = L.nC[q]; a.ih[q] = L.ih[q];
-                i64 sz = 1;
-                for (int d = 0; d < 3; ++d) sz *= (d == q) ? L.nC[d] : L.nC[d] + 1;
-                big = std::max(big, sz);
-            }
-            a.fl = L.fl; a.f = faces; a.s = m->sel_s();
-            a.scl = -recip(scalar_of<T>(sr, si));
-            hipLaunchKernelGGL(k_hfield_adjoint<T>, dim3((unsigned)((big + EMG_BLOCK - 1) / EMG_BLOCK), 3), dim3(EMG_BLOCK), 0,
-                               m->stream, a);
-            m->check_launch();
+        i64 big = 0;
+        for (int q = 0; q < 3; ++q) {
+            ha.nC[q] = L.nC[q]; ha.ih[q] = L.ih[q];
+            i64 sz = 1;
+            for (int d = 0; d < 3; ++d) sz *= (d == q) ? L.nC[d] : L.nC[d] + 1;
+            big = std::max(big, sz);
         }
+        ha.fl = L.fl; ha.f = faces; ha.s = nullptr;
+        ha.scl = -recip(scalar_of<T>(sr, si));
+        hblocks = (unsigned)((big + EMG_BLOCK - 1) / EMG_BLOCK);
+        return plan.build(m->stream, method, comp, hl, n, xyz, fac);
     }
-    const int st = finish(m);
+
+    void apply(MG<T>* m, const T* dw, T* s) {
+        if (!magnetic) { plan.apply(m->stream, dw, m->scratch_field, s); return; }
+        hipMemsetAsync(faces, 0, faces_bytes, m->stream);
+        plan.apply(m->stream, dw, m->scratch_field, faces);
+        HFieldAdjArgs<T> a = ha;
+        a.s = s;
+        hipLaunchKernelGGL(k_hfield_adjoint<T>, dim3(hblocks, 3), dim3(EMG_BLOCK), 0, m->stream, a);
+    }
+};
+
+// s of the systems with use[b] != 0 (+)= P^T w_b, w = [nsys][n]; use == NULL: the selected system, w = [n]
+template <class T>
+int receiver_adjoint_impl(MG<T>* m, int method, int magnetic, double sr, double si, i64 n, const double* xyz, const double* fac,
+                          const T* w, const int32_t* use, int accumulate) {
+    HIP_TRY(hipSetDevice(m->device));
+    auto& L = *m->lv0;
+    if (L.nC[0] < 3 || L.nC[1] < 3 || L.nC[2] < 3) return -2;
+    if (magnetic && sizeof(T) == 8 && si != 0.0) return -2;
+    const int first = use ? 0 : m->cur, last = use ? m->nsys : m->cur + 1;
+    bool any = false;
+    for (int b = first; b < last; ++b) any = any || !use || use[b];
+    if (!any) return 0;
+    if (method == 1 && !m->scratch_field) m->scratch_field = m->template dalloc<T>(L.nE);
+    if (m->broken) return (int)hipErrorOutOfMemory;
+    const size_t nrows = use ? (size_t)m->nsys : 1;
+    T* dw = nullptr;
+    DEV_ALLOC(dw, nrows * (size_t)n * sizeof(T));
+    m->source_changed();
+    MgRcvAdjoint<T> adj;
+    int rc = adj.build(m, method, magnetic, sr, si, n, xyz, fac);
+    if (rc == 0 && hipMemcpyAsync(dw, w, nrows * (size_t)n * sizeof(T), hipMemcpyHostToDevice, m->stream) != hipSuccess)
+        rc = (int)hipGetLastError();
+    for (int b = first; b < last && rc == 0; ++b) {
+        if (use && !use[b]) continue;
+        T* s = L.s + (i64)b * L.nE;
+        if (!accumulate) hipMemsetAsync(s, 0, (size_t)L.nE * sizeof(T), m->stream);
+        adj.apply(m, dw + (use ? (size_t)b * (size_t)n : 0), s);
+    }
+    m->check_launch();
+    const int st = finish(m);           // (synchronises: the host tables and the device blocks go out of scope)
     return rc ? rc : st;
 }
 
@@ -1041,6 +1109,43 @@ int emg3d_mg_grad_acc_get(emg3d_mg_t* mg, double* out) {
     });
 }
 
+int emg3d_mg_grad_acc3_reset(emg3d_mg_t* mg) {
+    if (!mg) return -2;
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        const int st = m->grad_acc3_reset();
+        return st ? st : finish(m);
+    });
+}
+
+int emg3d_mg_grad_acc3_add(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use) {
+    if (!mg || !use) return -2;
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        const int st = m->grad_acc3_add(fwd_bvec, smu0_re, smu0_im, use);
+        return st ? st : finish(m);
+    });
+}
+
+int emg3d_mg_grad_acc3_get(emg3d_mg_t* mg, double* out_x, double* out_y, double* out_z) {
+    if (!mg || !out_x || !out_y || !out_z) return -2;
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        if (!m->grad_acc3) { const int st = m->grad_acc3_reset(); if (st) return st; }
+        const i64 n = m->lv0->nCells;
+        HIP_TRY(m->d2h(out_x, m->grad_acc3, (size_t)n * sizeof(double)));
+        HIP_TRY(m->d2h(out_y, m->grad_acc3 + n, (size_t)n * sizeof(double)));
+        HIP_TRY(m->d2h(out_z, m->grad_acc3 + 2 * n, (size_t)n * sizeof(double)));
+        return finish(m);
+    });
+}
+
+int emg3d_mg_jvec_source_b(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const double* vx, const double* vy,
+                           const double* vz, const int32_t* use) {
+    if (!mg || !use) return -2;
+    DISPATCH(mg, return jvec_source_b_impl<T>(m, fwd_bvec, smu0_re, smu0_im, vx, vy, vz, use));
+}
+
 int emg3d_mg_jvec_source(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, const double* vx, const double* vy,
                          const double* vz) {
     if (!mg) return -2;
@@ -1051,7 +1156,14 @@ int emg3d_mg_set_receiver_adjoint_ex(emg3d_mg_t* mg, int method, int magnetic, d
                                      const double* xyz, const double* factors, const void* w, int accumulate) {
     if (!mg || n < 1 || !xyz || !factors || !w || method < 0 || method > 1) return -2;
     if (magnetic && smu0_re == 0.0 && smu0_im == 0.0) return -2;
-    DISPATCH(mg, return receiver_adjoint_impl<T>(m, method, magnetic, smu0_re, smu0_im, n, xyz, factors, (const T*)w, accumulate));
+    DISPATCH(mg, return receiver_adjoint_impl<T>(m, method, magnetic, smu0_re, smu0_im, n, xyz, factors, (const T*)w, nullptr, accumulate));
+}
+
+int emg3d_mg_set_receiver_adjoint_b(emg3d_mg_t* mg, int method, int magnetic, double smu0_re, double smu0_im, int64_t n,
+                                    const double* xyz, const double* factors, const void* w, const int32_t* use, int accumulate) {
+    if (!mg || n < 1 || !xyz || !factors || !w || !use || method < 0 || method > 1) return -2;
+    if (magnetic && smu0_re == 0.0 && smu0_im == 0.0) return -2;
+    DISPATCH(mg, return receiver_adjoint_impl<T>(m, method, magnetic, smu0_re, smu0_im, n, xyz, factors, (const T*)w, use, accumulate));
 }
 
 int emg3d_mg_set_receiver_adjoint(emg3d_mg_t* mg, int64_t n, const double* xyz, const double* factors, const void* w,

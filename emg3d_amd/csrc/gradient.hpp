@@ -102,23 +102,29 @@ __global__ void k_gradient(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* e, c
 // whose bit is set in `use`, g_b = what k_gradient<T, false> gives for the forward field e + b * nE (slice b of a batched vector) and
 // the back-propagated field bk + b * nE (slice b of the level-0 field array).  One thread per cell, one read and one write of acc, no
 // atomics: the order of the sum is fixed.  Per active system the two fields are read once (2 nE sizeof(T) bytes).
-template <class T>
+// SPLIT (optimize.SurveyJacobian, components=True): three accumulators, acc_c += g_c,b with g_c,b what k_gradient<T, true> gives --
+// the same grad_cell, its three results kept apart instead of added.
+template <class T, bool SPLIT>
 __global__ void k_gradient_acc(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* e, const T* bk, i64 nE, int nsys, unsigned long long use,
-                               double sr, double si, const double* h0, const double* h1, const double* h2, double* acc) {
+                               double sr, double si, const double* h0, const double* h1, const double* h2, double* acc, double* acc1,
+                               double* acc2) {
     const i64 nC[3] = {n0, n1, n2};
     const i64 n = n0 * n1 * n2;
     const i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
     const i64 j[3] = {idx % n0, (idx / n0) % n1, idx / (n0 * n1)};
     const double vol = (h0[j[0]] * h1[j[1]]) * h2[j[2]];
-    double run = acc[idx];
+    double run = acc[idx], run1 = 0.0, run2 = 0.0;
+    if (SPLIT) { run1 = acc1[idx]; run2 = acc2[idx]; }
     for (int b = 0; b < nsys; ++b) {
         if (!((use >> b) & 1ull)) continue;
         double g[3];
         grad_cell<T>(j, nC, vol, fl, e + (i64)b * nE, bk + (i64)b * nE, sr, si, g);
-        run += (g[0] + g[1]) + g[2];
+        if (SPLIT) { run += g[0]; run1 += g[1]; run2 += g[2]; }
+        else run += (g[0] + g[1]) + g[2];
     }
     acc[idx] = run;
+    if (SPLIT) { acc1[idx] = run1; acc2[idx] = run2; }
 }
 
 // ---- the transpose: cells -> edges (J v of optimize.Jacobian) ---------------------------------------------------------------
@@ -189,23 +195,77 @@ __device__ __forceinline__ c128 jvec_prod(double cv, c128 e, double sr, double s
 // Right-hand side of the J v solve: s[edge] = s mu_0 * C(v)[edge] * E[edge], C(v) = 1/4 sum of V_c v_c over the four cells around
 // the edge with that component's perturbation (v[c] == nullptr: none, the component's source is zero); PEC boundary edges are written
 // as exact zeros.  V = (hx*hy)*hz as in k_gradient.  Per edge 16 B of E are read and 16 B written (c128); the cell reads hit the cache.
+// jvec_edge: the part that does not depend on the field -- the edge's offset `o` in a field array and C(v)[edge]; false: the edge's
+// source is zero (PEC boundary, or no perturbation of its component).  One body for k_jvec_source and k_jvec_source_b, so that both
+// round (and contract) alike.
+__device__ __forceinline__ bool jvec_edge(i64 idx, const i64 nC[3], const FieldLayout& fl, const double* v0, const double* v1,
+                                          const double* v2, const double* h0, const double* h1, const double* h2, i64& o, double& cv) {
+    i64 e[3];
+    const int c = edge_of(idx, nC, e);
+    const int t1 = (c == 0) ? 1 : 0, t2 = (c == 2) ? 1 : 2;
+    o = fl.off[c] + e[0] * fl.st[c][0] + e[1] * fl.st[c][1] + e[2] * fl.st[c][2];
+    const double* v = c == 0 ? v0 : (c == 1 ? v1 : v2);
+    cv = 0.0;
+    if (!(v && e[t1] > 0 && e[t1] < nC[t1] && e[t2] > 0 && e[t2] < nC[t2])) return false;
+    const i64 n0 = nC[0], n1 = nC[1];
+    cv = c2e_gather<double>(c, e, nC, [&](i64 j0, i64 j1, i64 j2) {
+        return ((h0[j0] * h1[j1]) * h2[j2]) * v[j0 + n0 * (j1 + n1 * j2)];
+    });
+    return true;
+}
+
 template <class T>
 __global__ void k_jvec_source(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* efield, double sr, double si, const double* v0,
                               const double* v1, const double* v2, const double* h0, const double* h1, const double* h2, T* s, i64 nE) {
     const i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= nE) return;
     const i64 nC[3] = {n0, n1, n2};
-    i64 e[3];
-    const int c = edge_of(idx, nC, e);
-    const int t1 = (c == 0) ? 1 : 0, t2 = (c == 2) ? 1 : 2;
-    const i64 o = fl.off[c] + e[0] * fl.st[c][0] + e[1] * fl.st[c][1] + e[2] * fl.st[c][2];
-    const double* v = c == 0 ? v0 : (c == 1 ? v1 : v2);
+    i64 o;
+    double cv;
     T val = Zero<T>::v();
-    if (v && e[t1] > 0 && e[t1] < nC[t1] && e[t2] > 0 && e[t2] < nC[t2]) {
-        const double cv = c2e_gather<double>(c, e, nC, [&](i64 j0, i64 j1, i64 j2) {
-            return ((h0[j0] * h1[j1]) * h2[j2]) * v[j0 + n0 * (j1 + n1 * j2)];
-        });
-        val = jvec_prod(cv, efield[o], sr, si);
-    }
+    if (jvec_edge(idx, nC, fl, v0, v1, v2, h0, h1, h2, o, cv)) val = jvec_prod(cv, efield[o], sr, si);
     s[o] = val;
+}
+
+// The same for the systems of a batch that share ONE perturbation but have a forward field each (optimize.SurveyJacobian.jvec):
+// the thread forms C(v)[edge] once, then s_b[edge] = s mu_0 C(v)[edge] E_b[edge] for the systems b = 0 .. nsys-1 whose bit is set in
+// `use`, E_b = slice b of the batched vector `efield`, s_b = slice b of the level-0 source array; the other systems' slices are not
+// touched.  Slice b is bit for bit what k_jvec_source writes for system b.  Per edge and active system sizeof(T) bytes are read and
+// sizeof(T) written, consecutive threads consecutive edges (x fastest); the loads of up to JVEC_GROUP active systems are issued
+// together, before the first product.
+#define JVEC_GROUP 4
+template <class T>
+__global__ void k_jvec_source_b(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* efield, int nsys, unsigned long long use, double sr,
+                                double si, const double* v0, const double* v1, const double* v2, const double* h0, const double* h1,
+                                const double* h2, T* s, i64 nE) {
+    const i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= nE) return;
+    const i64 nC[3] = {n0, n1, n2};
+    i64 o;
+    double cv;
+    const bool live = jvec_edge(idx, nC, fl, v0, v1, v2, h0, h1, h2, o, cv);
+    if (nsys < 64) use &= (1ull << nsys) - 1ull;
+    if (!live) {
+        for (int b = 0; b < nsys && b < 64; ++b)      // (never a shift by 64: nsys = 64 with bit 63 set is a valid batch)
+            if ((use >> b) & 1ull) s[(i64)b * nE + o] = Zero<T>::v();
+        return;
+    }
+    while (use) {                       // (wave-uniform: `use` is a kernel argument)
+        int bs[JVEC_GROUP];
+        T ev[JVEC_GROUP];
+        int k = 0;
+#pragma unroll
+        for (int q = 0; q < JVEC_GROUP; ++q) {
+            bs[q] = -1;
+            if (use) {
+                bs[q] = __builtin_ctzll(use);
+                use &= use - 1ull;
+                ev[q] = efield[(i64)bs[q] * nE + o];
+                ++k;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < JVEC_GROUP; ++q)
+            if (q < k) s[(i64)bs[q] * nE + o] = jvec_prod(cv, ev[q], sr, si);
+    }
 }

@@ -905,8 +905,34 @@ struct MG : emg3d_mg {
         e_to_ref(L);
         const T* bwd = L.e;
         const unsigned blocks = (unsigned)((L.nCells + 255) / 256);
-        MG_LAUNCH(k_gradient_acc<T>, dim3(blocks), dim3(256), 0, stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd, bwd, L.nE, nsys, bits,
-                  sr, si, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], grad_acc);
+        MG_LAUNCH((k_gradient_acc<T, false>), dim3(blocks), dim3(256), 0, stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd, bwd, L.nE, nsys,
+                  bits, sr, si, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], grad_acc, (double*)nullptr,
+                  (double*)nullptr);
+        check_launch();
+        return err;
+    }
+    // The same per direction (emg3d_mg_grad_acc3_*, optimize.SurveyJacobian): three accumulators [acc_x | acc_y | acc_z] of nC doubles
+    // each in one block of the handle's own, independent of grad_acc; acc_c += g_c,b, g_c,b bit for bit emg3d_mg_gradient3's.
+    double* grad_acc3 = nullptr;
+    int grad_acc3_reset() {
+        if (!grad_acc3) grad_acc3 = dalloc<double>(3 * lv0->nCells);
+        if (!grad_acc3) return err ? err : (int)hipErrorOutOfMemory;
+        hipMemsetAsync(grad_acc3, 0, (size_t)(3 * lv0->nCells) * sizeof(double), stream);
+        return 0;
+    }
+    int grad_acc3_add(int fwd_bvec, double sr, double si, const int32_t* use) {
+        if (fwd_bvec < 0 || fwd_bvec >= (int)bvecs.size()) return -2;
+        if (!grad_acc3) { const int st = grad_acc3_reset(); if (st) return st; }
+        Level<T>& L = *lv0;
+        unsigned long long bits = 0;
+        for (int b = 0; b < nsys; ++b) if (use[b]) bits |= 1ull << b;
+        const T* fwd = bvecs[(size_t)fwd_bvec];
+        e_to_ref(L);
+        const T* bwd = L.e;
+        const unsigned blocks = (unsigned)((L.nCells + 255) / 256);
+        MG_LAUNCH((k_gradient_acc<T, true>), dim3(blocks), dim3(256), 0, stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd, bwd, L.nE, nsys,
+                  bits, sr, si, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], grad_acc3, grad_acc3 + L.nCells,
+                  grad_acc3 + 2 * L.nCells);
         check_launch();
         return err;
     }

@@ -518,156 +518,201 @@ void linear_adjoint_entries(const RcvComp<T>& C, const FieldLayout& tl, int c, i
     }
 }
 
-// CSR by target index of `ent` (stable: the entries of one index keep their order), uploaded with w; then one thread per touched
-// index: ASSIGN ? k_spline_eval_adjoint (dst[idx] = sum) : k_receiver_adjoint (dst[idx] += sum).  Synchronises the stream.
-template <class T, bool ASSIGN>
-int csr_adjoint_launch(hipStream_t st, std::vector<AdjEntry>& ent, i64 npts, const T* w_host, T* dst) {
+// CSR by target index of `ent` (stable: the entries of one index keep their order) on the device; the host arrays stay alive with
+// the table (the uploads are asynchronous).
+struct AdjCsr {
+    DevBlock blk;
+    std::vector<i64> edges;
+    std::vector<int> ptr, rcv;
+    std::vector<double> wgt;
+    i64* dedges = nullptr;
+    double* dwgt = nullptr;
+    int* dptr = nullptr;
+    int* drcv = nullptr;
+    i64 ne = 0;
+};
+
+inline int csr_adjoint_build(hipStream_t st, std::vector<AdjEntry>& ent, AdjCsr& t) {
+    t.ne = 0;
     if (ent.empty()) return 0;
     std::stable_sort(ent.begin(), ent.end(), [](const AdjEntry& a, const AdjEntry& b) { return a.idx < b.idx; });
-    std::vector<i64> edges;
-    std::vector<int> ptr, rcv(ent.size());
-    std::vector<double> wgt(ent.size());
+    t.rcv.resize(ent.size());
+    t.wgt.resize(ent.size());
     for (size_t q = 0; q < ent.size(); ++q) {
-        if (q == 0 || ent[q].idx != ent[q - 1].idx) { edges.push_back(ent[q].idx); ptr.push_back((int)q); }
-        rcv[q] = ent[q].r; wgt[q] = ent[q].w;
+        if (q == 0 || ent[q].idx != ent[q - 1].idx) { t.edges.push_back(ent[q].idx); t.ptr.push_back((int)q); }
+        t.rcv[q] = ent[q].r; t.wgt[q] = ent[q].w;
     }
-    ptr.push_back((int)ent.size());
-    const size_t ne = edges.size(), nq = ent.size();
-    char* base = nullptr;
-    DEV_ALLOC(base, ne * 8 + nq * 8 + (size_t)npts * sizeof(T) + (ne + 1 + nq) * 4 + 64);
-    i64* dedges = (i64*)base;
-    double* dwgt = (double*)(dedges + ne);
-    T* dw = (T*)(dwgt + nq);
-    int* dptr = (int*)(dw + npts);
-    int* drcv = dptr + ne + 1;
-    HIP_TRY(hipMemcpyAsync(dedges, edges.data(), ne * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dwgt, wgt.data(), nq * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dw, w_host, (size_t)npts * sizeof(T), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(dptr, ptr.data(), (ne + 1) * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(drcv, rcv.data(), nq * 4, hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)((ne + EMG_RCV_BLOCK - 1) / EMG_RCV_BLOCK));
-    if (ASSIGN)
-        hipLaunchKernelGGL(k_spline_eval_adjoint<T>, grid, dim3(EMG_RCV_BLOCK), 0, st, dst, (const i64*)dedges, (const int*)dptr,
-                           (const int*)drcv, (const double*)dwgt, (const T*)dw, (i64)ne);
-    else
-        hipLaunchKernelGGL(k_receiver_adjoint<T>, grid, dim3(EMG_RCV_BLOCK), 0, st, dst, (const i64*)dedges, (const int*)dptr,
-                           (const int*)drcv, (const double*)dwgt, (const T*)dw, (i64)ne);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);             // (the host tables and the device block go out of scope)
-    if (e != hipSuccess) { fprintf(stderr, "[emg3d_hip] receiver adjoint: %s\n", hipGetErrorString(e)); return (int)e; }
+    t.ptr.push_back((int)ent.size());
+    const size_t ne = t.edges.size(), nq = ent.size();
+    HIP_TRY(t.blk.alloc(ne * 8 + nq * 8 + (ne + 1 + nq) * 4 + 64));
+    t.dedges = t.blk.get<i64>();
+    t.dwgt = (double*)(t.dedges + ne);
+    t.dptr = (int*)(t.dwgt + nq);
+    t.drcv = t.dptr + ne + 1;
+    HIP_TRY(hipMemcpyAsync(t.dedges, t.edges.data(), ne * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(t.dwgt, t.wgt.data(), nq * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(t.dptr, t.ptr.data(), (ne + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(t.drcv, t.rcv.data(), nq * 4, hipMemcpyHostToDevice, st));
+    t.ne = (i64)ne;
     return 0;
 }
 
-// s (+)= P^T w, P the operator of receiver_response_device(method 0) on the components comp (only n / pts are used; electric
-// edges or magnetic faces), fl the layout of s.  Host: 8 weights per receiver and active component, O(npts log npts); CSR by
-// edge.  A receiver outside the trimmed points of an active component (its datum is NaN) contributes nothing.
+// One thread per touched index of the table: ASSIGN ? k_spline_eval_adjoint (dst[idx] = sum) : k_receiver_adjoint (dst[idx] += sum),
+// with the device-resident data vector w.  Does not synchronise.
+template <class T, bool ASSIGN>
+void csr_adjoint_apply(hipStream_t st, const AdjCsr& t, const T* dw, T* dst) {
+    if (!t.ne) return;
+    const dim3 grid((unsigned)((t.ne + EMG_RCV_BLOCK - 1) / EMG_RCV_BLOCK));
+    if (ASSIGN)
+        hipLaunchKernelGGL(k_spline_eval_adjoint<T>, grid, dim3(EMG_RCV_BLOCK), 0, st, dst, (const i64*)t.dedges, (const int*)t.dptr,
+                           (const int*)t.drcv, (const double*)t.dwgt, dw, t.ne);
+    else
+        hipLaunchKernelGGL(k_receiver_adjoint<T>, grid, dim3(EMG_RCV_BLOCK), 0, st, dst, (const i64*)t.dedges, (const int*)t.dptr,
+                           (const int*)t.drcv, (const double*)t.dwgt, dw, t.ne);
+}
+
+// The transpose P^T of a receiver operator as device tables -- everything that depends on the grid and the receivers only, built
+// ONCE (build) and then applied to any number of data vectors (apply: kernels only, no host work).
+//   method 0: P the operator of receiver_response_device(method 0) on the components comp (only n / pts are used; electric edges or
+//   magnetic faces), fl the layout of the target.  Host: 8 weights per receiver and active component, O(npts log npts); CSR by edge.
+//   A receiver outside the trimmed points of an active component (its datum is NaN) contributes nothing.
+//   method 1: P the operator of receiver_response_device(method 1): per active component
+//       P = R Eval(xi) F_2 F_1 F_0 Trim,       P^T w = Trim^T F_0^T F_1^T F_2^T Eval^T R^T w
+//   with the 64 weights fac w0 w1 w2 per receiver gathered into the zeroed coefficient array `coef` (k_spline_eval_adjoint), the
+//   transposed prefilter per axis (k_line_ends_scale, k_spline_filter_axis, k_line_ends_scale) and k_trim_add into the target.  The
+//   rules of the forward operator: a component with fewer than four trimmed points along an axis is linear with fill value 0 (a
+//   receiver outside ITS points adds nothing for that component); a receiver whose index coordinates leave [0, n - 1] on an axis of
+//   a cubic component has a NaN datum and contributes nothing at all.
+template <class T>
+struct RcvAdjPlan {
+    AdjCsr lin;              // the linear components, straight into the target
+    AdjCsr cub[3];           // per cubic component: coefficient -> contributions
+    i64 m[3][3];
+    FieldLayout fl;
+
+    int build(hipStream_t st, int method, const RcvComp<T> comp[3], const FieldLayout& tl, i64 npts, const double* xyz, const double* fac) {
+        if (npts < 1) return -2;
+        fl = tl;
+        bool active[3], cubic[3];
+        std::vector<double> co[3];
+        std::vector<char> dead((size_t)npts, 0);
+        for (int c = 0; c < 3; ++c) {
+            active[c] = false; cubic[c] = false;
+            for (i64 r = 0; r < npts; ++r) if (std::fabs(fac[c * npts + r]) > 1e-10) { active[c] = true; break; }
+            if (!active[c]) continue;
+            cubic[c] = method != 0;
+            for (int a = 0; a < 3; ++a) {
+                if (comp[c].n[a] < 3) return -2;
+                m[c][a] = comp[c].n[a] - 2;
+                if (m[c][a] < 4) cubic[c] = false;              // maps.py:238-240
+            }
+            if (!method) {          // linear receivers: outside ANY active component's points -> NaN datum
+                for (int a = 0; a < 3; ++a) {
+                    const double* g = comp[c].pts[a].data() + 1;
+                    for (i64 r = 0; r < npts; ++r) if (!(xyz[a * npts + r] >= g[0] && xyz[a * npts + r] <= g[m[c][a] - 1])) dead[r] = 1;
+                }
+                continue;
+            }
+            if (!cubic[c]) continue;
+            co[c].resize((size_t)3 * npts);
+            for (int a = 0; a < 3; ++a) {
+                notaknot_index_coords(comp[c].pts[a].data() + 1, m[c][a], xyz + a * npts, npts, co[c].data() + a * npts);
+                for (i64 r = 0; r < npts; ++r) {
+                    const double cc = co[c][a * npts + r];
+                    if (!(cc >= 0.0 && cc <= (double)(m[c][a] - 1))) dead[r] = 1;
+                }
+            }
+        }
+        std::vector<AdjEntry> ent;
+        for (int c = 0; c < 3; ++c) {
+            if (!active[c] || cubic[c]) continue;
+            std::vector<char> skip(dead);
+            if (method)             // the linear fallback of a cubic operator: fill value 0 outside ITS points
+                for (int a = 0; a < 3; ++a) {
+                    const double* g = comp[c].pts[a].data() + 1;
+                    for (i64 r = 0; r < npts; ++r) if (!(xyz[a * npts + r] >= g[0] && xyz[a * npts + r] <= g[m[c][a] - 1])) skip[r] = 1;
+                }
+            linear_adjoint_entries<T>(comp[c], fl, c, npts, xyz, fac, skip, ent);
+        }
+        int rc = csr_adjoint_build(st, ent, lin);
+        for (int c = 0; c < 3 && rc == 0; ++c) {
+            if (!active[c] || !cubic[c]) continue;
+            const i64 m0 = m[c][0], m1 = m[c][1];
+            ent.clear();
+            for (i64 r = 0; r < npts; ++r) {
+                if (dead[r]) continue;
+                i64 idx[3][4];
+                double wt[3][4];
+                for (int a = 0; a < 3; ++a) {           // as spline_point, edge 0
+                    const double cc = co[c][a * npts + r];
+                    const double flr = std::floor(cc);
+                    bspline3_weights_host(cc - flr, wt[a]);
+                    const i64 start = (i64)flr - 1;
+                    for (int l = 0; l < 4; ++l) idx[a][l] = mirror_index_host(start + l, m[c][a]);
+                }
+                for (int a0 = 0; a0 < 4; ++a0)
+                    for (int a1 = 0; a1 < 4; ++a1)
+                        for (int a2 = 0; a2 < 4; ++a2)
+                            ent.push_back({idx[0][a0] + m0 * (idx[1][a1] + m1 * idx[2][a2]), (int)r,
+                                           fac[c * npts + r] * (wt[0][a0] * wt[1][a1] * wt[2][a2])});
+            }
+            rc = csr_adjoint_build(st, ent, cub[c]);
+        }
+        return rc;
+    }
+
+    // s += P^T w for the device-resident data vector dw (npts values); coef: scratch, >= the largest trimmed component (cubic only)
+    void apply(hipStream_t st, const T* dw, T* coef, T* s) const {
+        csr_adjoint_apply<T, false>(st, lin, dw, s);
+        for (int c = 0; c < 3; ++c) {
+            if (!cub[c].ne) continue;
+            const i64 m0 = m[c][0], m1 = m[c][1], m2 = m[c][2], tot = m0 * m1 * m2;
+            hipMemsetAsync(coef, 0, (size_t)tot * sizeof(T), st);
+            csr_adjoint_apply<T, true>(st, cub[c], dw, coef);
+            for (int a = 2; a >= 0; --a) {
+                const i64 nl = tot / m[c][a];
+                const dim3 grid((unsigned)((nl + 63) / 64));
+                hipLaunchKernelGGL(k_line_ends_scale<T>, grid, dim3(64), 0, st, coef, m0, m1, m2, a, 2.0);
+                hipLaunchKernelGGL(k_spline_filter_axis<T>, grid, dim3(64), 0, st, coef, m0, m1, m2, a, 0);
+                hipLaunchKernelGGL(k_line_ends_scale<T>, grid, dim3(64), 0, st, coef, m0, m1, m2, a, 0.5);
+            }
+            hipLaunchKernelGGL(k_trim_add<T>, dim3((unsigned)std::min<i64>((tot + 255) / 256, 8192)), dim3(256), 0, st, s, (const T*)coef,
+                               m0, m1, m2, fl.off[c], fl.st[c][0], fl.st[c][1], fl.st[c][2]);
+        }
+    }
+};
+
+inline int rcv_adjoint_sync(hipStream_t st, const char* what) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);             // (the host tables and the device blocks go out of scope)
+    if (e != hipSuccess) { fprintf(stderr, "[emg3d_hip] %s: %s\n", what, hipGetErrorString(e)); return (int)e; }
+    return 0;
+}
+
+// s (+)= P^T w for ONE host data vector: the plan, built and applied once (method 0 / 1 as RcvAdjPlan).  Synchronises the stream.
+template <class T>
+int receiver_adjoint_any_device(hipStream_t st, int method, const RcvComp<T> comp[3], const FieldLayout& fl, i64 npts, const double* xyz,
+                                const double* fac, const T* w_host, T* coef, T* s) {
+    if (npts < 1) return -2;
+    T* dw = nullptr;
+    DEV_ALLOC(dw, (size_t)npts * sizeof(T));            // (before the plan: no early return while its uploads are in flight)
+    RcvAdjPlan<T> plan;
+    int rc = plan.build(st, method, comp, fl, npts, xyz, fac);
+    if (rc == 0 && hipMemcpyAsync(dw, w_host, (size_t)npts * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess)
+        rc = (int)hipGetLastError();
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    plan.apply(st, dw, coef, s);
+    return rcv_adjoint_sync(st, method ? "cubic receiver adjoint" : "receiver adjoint");
+}
+
 template <class T>
 int receiver_adjoint_device(hipStream_t st, const RcvComp<T> comp[3], const FieldLayout& fl, i64 npts, const double* xyz,
                             const double* fac, const T* w_host, T* s) {
-    if (npts < 1) return -2;
-    std::vector<AdjEntry> ent;
-    std::vector<char> outside((size_t)npts, 0);
-    bool active[3];
-    for (int c = 0; c < 3; ++c) {
-        active[c] = false;
-        for (i64 r = 0; r < npts; ++r) if (std::fabs(fac[c * npts + r]) > 1e-10) { active[c] = true; break; }
-        if (!active[c]) continue;
-        for (int a = 0; a < 3; ++a) {
-            if (comp[c].n[a] < 3) return -2;
-            const double* g = comp[c].pts[a].data() + 1;
-            const i64 m = comp[c].n[a] - 2;
-            for (i64 r = 0; r < npts; ++r) if (!(xyz[a * npts + r] >= g[0] && xyz[a * npts + r] <= g[m - 1])) outside[r] = 1;
-        }
-    }
-    for (int c = 0; c < 3; ++c)
-        if (active[c]) linear_adjoint_entries<T>(comp[c], fl, c, npts, xyz, fac, outside, ent);
-    return csr_adjoint_launch<T, false>(st, ent, npts, w_host, s);
+    return receiver_adjoint_any_device<T>(st, 0, comp, fl, npts, xyz, fac, w_host, (T*)nullptr, s);
 }
 
-// s (+)= P^T w, P the operator of receiver_response_device(method 1): per active component
-//     P = R Eval(xi) F_2 F_1 F_0 Trim,       P^T w = Trim^T F_0^T F_1^T F_2^T Eval^T R^T w
-// with the 64 weights fac w0 w1 w2 per receiver scattered into the zeroed coefficient array `coef` (k_spline_eval_adjoint), the
-// transposed prefilter per axis (k_line_ends_scale, k_spline_filter_axis, k_line_ends_scale) and k_trim_add into s.  The rules of
-// the forward operator: a component with fewer than four trimmed points along an axis is linear with fill value 0 (a receiver
-// outside ITS points adds nothing for that component); a receiver whose index coordinates leave [0, n - 1] on an axis of a cubic
-// component has a NaN datum and contributes nothing at all.  coef: >= the largest trimmed component.
 template <class T>
 int receiver_adjoint_cubic_device(hipStream_t st, const RcvComp<T> comp[3], const FieldLayout& fl, i64 npts, const double* xyz,
                                   const double* fac, const T* w_host, T* coef, T* s) {
-    if (npts < 1) return -2;
-    bool active[3], cubic[3];
-    i64 m[3][3];
-    std::vector<double> co[3];
-    std::vector<char> dead((size_t)npts, 0);
-    for (int c = 0; c < 3; ++c) {
-        active[c] = false;
-        for (i64 r = 0; r < npts; ++r) if (std::fabs(fac[c * npts + r]) > 1e-10) { active[c] = true; break; }
-        if (!active[c]) continue;
-        cubic[c] = true;
-        for (int a = 0; a < 3; ++a) {
-            if (comp[c].n[a] < 3) return -2;
-            m[c][a] = comp[c].n[a] - 2;
-            if (m[c][a] < 4) cubic[c] = false;              // maps.py:238-240
-        }
-        if (!cubic[c]) continue;
-        co[c].resize((size_t)3 * npts);
-        for (int a = 0; a < 3; ++a) {
-            notaknot_index_coords(comp[c].pts[a].data() + 1, m[c][a], xyz + a * npts, npts, co[c].data() + a * npts);
-            for (i64 r = 0; r < npts; ++r) {
-                const double cc = co[c][a * npts + r];
-                if (!(cc >= 0.0 && cc <= (double)(m[c][a] - 1))) dead[r] = 1;
-            }
-        }
-    }
-    // linear components, straight into s
-    std::vector<AdjEntry> ent;
-    for (int c = 0; c < 3; ++c) {
-        if (!active[c] || cubic[c]) continue;
-        std::vector<char> skip(dead);
-        for (int a = 0; a < 3; ++a) {
-            const double* g = comp[c].pts[a].data() + 1;
-            for (i64 r = 0; r < npts; ++r) if (!(xyz[a * npts + r] >= g[0] && xyz[a * npts + r] <= g[m[c][a] - 1])) skip[r] = 1;
-        }
-        linear_adjoint_entries<T>(comp[c], fl, c, npts, xyz, fac, skip, ent);
-    }
-    int rc = csr_adjoint_launch<T, false>(st, ent, npts, w_host, s);
-    for (int c = 0; c < 3 && rc == 0; ++c) {
-        if (!active[c] || !cubic[c]) continue;
-        const i64 m0 = m[c][0], m1 = m[c][1], m2 = m[c][2], tot = m0 * m1 * m2;
-        ent.clear();
-        for (i64 r = 0; r < npts; ++r) {
-            if (dead[r]) continue;
-            i64 idx[3][4];
-            double wt[3][4];
-            for (int a = 0; a < 3; ++a) {           // as spline_point, edge 0
-                const double cc = co[c][a * npts + r];
-                const double flr = std::floor(cc);
-                bspline3_weights_host(cc - flr, wt[a]);
-                const i64 start = (i64)flr - 1;
-                for (int l = 0; l < 4; ++l) idx[a][l] = mirror_index_host(start + l, m[c][a]);
-            }
-            for (int a0 = 0; a0 < 4; ++a0)
-                for (int a1 = 0; a1 < 4; ++a1)
-                    for (int a2 = 0; a2 < 4; ++a2)
-                        ent.push_back({idx[0][a0] + m0 * (idx[1][a1] + m1 * idx[2][a2]), (int)r,
-                                       fac[c * npts + r] * (wt[0][a0] * wt[1][a1] * wt[2][a2])});
-        }
-        if (ent.empty()) continue;
-        HIP_TRY(hipMemsetAsync(coef, 0, (size_t)tot * sizeof(T), st));
-        rc = csr_adjoint_launch<T, true>(st, ent, npts, w_host, coef);
-        if (rc) break;
-        for (int a = 2; a >= 0; --a) {
-            const i64 nl = tot / m[c][a];
-            const dim3 grid((unsigned)((nl + 63) / 64));
-            hipLaunchKernelGGL(k_line_ends_scale<T>, grid, dim3(64), 0, st, coef, m0, m1, m2, a, 2.0);
-            hipLaunchKernelGGL(k_spline_filter_axis<T>, grid, dim3(64), 0, st, coef, m0, m1, m2, a, 0);
-            hipLaunchKernelGGL(k_line_ends_scale<T>, grid, dim3(64), 0, st, coef, m0, m1, m2, a, 0.5);
-        }
-        hipLaunchKernelGGL(k_trim_add<T>, dim3((unsigned)std::min<i64>((tot + 255) / 256, 8192)), dim3(256), 0, st, s, (const T*)coef,
-                           m0, m1, m2, fl.off[c], fl.st[c][0], fl.st[c][1], fl.st[c][2]);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { fprintf(stderr, "[emg3d_hip] cubic receiver adjoint: %s\n", hipGetErrorString(e)); rc = (int)e; }
-    }
-    return rc;
+    return receiver_adjoint_any_device<T>(st, 1, comp, fl, npts, xyz, fac, w_host, coef, s);
 }

@@ -12,13 +12,15 @@ of the pair, ``J v`` and ``J^T w``, one multigrid solve each on the operator the
 v0.17.0 has the gradient only).
 
 ``survey_gradient`` sums the gradient over the (source, frequency) pairs of a survey: batched forward and back-propagation solves
-on one handle per dtype, the sum over the sources formed on the device (``DeviceMG.grad_acc_add``).  ``model_gradient(...,
+on one handle per dtype, the sum over the sources formed on the device (``DeviceMG.grad_acc_add``).  ``SurveyJacobian`` keeps those
+handles and the forward fields of ALL pairs in HBM and gives ``J v``, ``J^T w`` and the Gauss-Newton product ``J^T W J v`` of the
+survey, every solve batched over the sources.  ``model_gradient(...,
 model_grid=)`` maps the gradient to the model grid as the reference does (``maps.grid2grid(grid, -grad, model_grid,
 'cubic')``, optimize.py:201-211) and applies the chain rule there.
 """
 import numpy as np
 
-from . import fields, maps, models, solver
+from . import _lib, fields, maps, models, solver
 
 
 def misfit(synthetic, observed, weights):
@@ -310,6 +312,43 @@ def model_gradient(grid, model, grad, model_grid=None):
     raise NotImplementedError(f"model_gradient: property map {mapping!r} (apply its derivative_chain to -grad).")
 
 
+def _perturbations(v, vnC):
+    """Conductivity perturbations on a grid of ``vnC`` cells, as ``Jacobian.jvec`` and ``SurveyJacobian.jvec`` take them
+    -> (list of (vx, vy, vz) with F-raveled float64 arrays or None, single)"""
+    dirs = list(v) if isinstance(v, (tuple, list)) and len(v) == 3 and not np.isscalar(v[0]) else None
+    if isinstance(v, (tuple, list)) and dirs is None:
+        raise ValueError("`v` must be an array of shape grid.vnC (or (k,) + grid.vnC), or a 3-tuple (v_x, v_y, v_z) of them.")
+    same = dirs is None
+    arrs = [np.asarray(v)] * 3 if same else [None if d is None else np.asarray(d) for d in dirs]
+    if all(a is None for a in arrs):
+        raise ValueError("`v`: at least one of (v_x, v_y, v_z) must be given.")
+    nd = {a.ndim for a in arrs if a is not None}
+    for a in arrs:
+        if a is None:
+            continue
+        if np.iscomplexobj(a):
+            raise TypeError("`v` must be real (a conductivity perturbation).")
+        if a.ndim not in (3, 4) or a.shape[-3:] != vnC or len(nd) != 1:
+            raise ValueError(f"`v` must have shape {vnC} or (k,) + {vnC}; provided: {a.shape}.")
+    single = nd == {3}
+    k = 1 if single else {a.shape[0] for a in arrs if a is not None}
+    if not single:
+        if len(k) != 1 or min(k) < 1:
+            raise ValueError("`v`: (v_x, v_y, v_z) must hold the same number of vectors (at least one).")
+        k = k.pop()
+
+    def flat(a, i):
+        return np.ascontiguousarray((a if single else a[i]).astype(np.float64, copy=False).ravel(order='F'))
+    out = []
+    for i in range(k):
+        if same:
+            f = flat(arrs[0], i)
+            out.append((f, f, f))
+        else:
+            out.append(tuple(None if a is None else flat(a, i) for a in arrs))
+    return out, single
+
+
 class Jacobian:
     """Products with the sensitivity matrix ``J = d(data) / d(conductivity)`` of ONE (source, frequency) pair on its
     computational grid, on one device handle::
@@ -433,44 +472,9 @@ class Jacobian:
         return self._dev
 
     # ---- J v ----------------------------------------------------------------------------------------------------------
-    def _perturbations(self, v):
-        """-> (list of (vx, vy, vz) with F-raveled float64 arrays or None, single)"""
-        dirs = list(v) if isinstance(v, (tuple, list)) and len(v) == 3 and not np.isscalar(v[0]) else None
-        if isinstance(v, (tuple, list)) and dirs is None:
-            raise ValueError("`v` must be an array of shape grid.vnC (or (k,) + grid.vnC), or a 3-tuple (v_x, v_y, v_z) of them.")
-        same = dirs is None
-        arrs = [np.asarray(v)] * 3 if same else [None if d is None else np.asarray(d) for d in dirs]
-        if all(a is None for a in arrs):
-            raise ValueError("`v`: at least one of (v_x, v_y, v_z) must be given.")
-        nd = {a.ndim for a in arrs if a is not None}
-        for a in arrs:
-            if a is None:
-                continue
-            if np.iscomplexobj(a):
-                raise TypeError("`v` must be real (a conductivity perturbation).")
-            if a.ndim not in (3, 4) or a.shape[-3:] != self._vnC or len(nd) != 1:
-                raise ValueError(f"`v` must have shape {self._vnC} or (k,) + {self._vnC}; provided: {a.shape}.")
-        single = nd == {3}
-        k = 1 if single else {a.shape[0] for a in arrs if a is not None}
-        if not single:
-            if len(k) != 1 or min(k) < 1:
-                raise ValueError("`v`: (v_x, v_y, v_z) must hold the same number of vectors (at least one).")
-            k = k.pop()
-
-        def flat(a, i):
-            return np.ascontiguousarray((a if single else a[i]).astype(np.float64, copy=False).ravel(order='F'))
-        out = []
-        for i in range(k):
-            if same:
-                f = flat(arrs[0], i)
-                out.append((f, f, f))
-            else:
-                out.append(tuple(None if a is None else flat(a, i) for a in arrs))
-        return out, single
-
     def jvec(self, v):
         """``J v``: the data change per unit of the conductivity perturbation ``v`` (see the class docstring)."""
-        vecs, single = self._perturbations(v)
+        vecs, single = _perturbations(v, self._vnC)
         dev = self._require_open()
         smu0 = self._spec.smu0
         out = np.empty((len(vecs), self.n_rec), dtype=self._spec.dtype)
@@ -550,6 +554,314 @@ class Jacobian:
         if components:
             return tuple(np.stack([o[c] for o in outs]) for c in range(3))
         return np.stack(outs)
+
+
+class SurveyJacobian:
+    """Products with the sensitivity matrix of a SURVEY -- every source of ``sources`` at every entry of ``freqs`` (values < 0 are
+    Laplace-domain, and may be mixed with frequencies) -- on the computational grid: the rows of ``Jacobian(src_i, freq_j)`` for all
+    pairs ``(i, j)`` stacked, without a handle, a hierarchy, a forward solve and an ``nC``-sized download per pair::
+
+        with SurveyJacobian(grid, model, sources, freqs, rec, batch=8, tol=1e-8, ...) as sj:
+            sj.synthetic                      # (n_src, n_freq, n_rec)
+            dd = sj.jvec(v)                   # v: vnC array or (v_x, v_y, v_z)  ->  (n_src, n_freq, n_rec)
+            g = sj.jtvec(w)                   # w: (n_src, n_freq, n_rec) -> vnC;  components=True -> (g_x, g_y, g_z)
+            hv = sj.gauss_newton(v, weights)  # == sj.jtvec(weights * sj.jvec(v)), bit for bit
+            sj.partial                        # the last jtvec's per-frequency sums G_f
+
+    One handle per dtype carries ``min(batch, n_src)`` systems and is re-targeted from entry to entry of ``freqs``
+    (``DeviceMG.set_smu0``), as in ``survey_gradient``.  ``open()`` solves all pairs forward, the sources in chunks of that size
+    (built in HBM), extracts the data and parks the forward fields of every (frequency, chunk) in a batched vector of its own:
+    ``n_freq * n_chunks * min(batch, n_src) * nE`` field values stay in HBM (sized and allocated before the first solve; a
+    workspace that does not fit raises ``HipLibraryError`` with the bytes needed and free) and never cross PCIe.
+
+    * ``jvec(v)``: per frequency and chunk ONE ``jvec_source_b`` (``s mu_0 C(v) E_b`` for all systems of the chunk), one batched
+      solve, the data per system.
+    * ``jtvec(w)``: per frequency the accumulator is reset; per chunk ONE ``set_receiver_adjoint_b`` (``adjoint='reference'`` with
+      cubic receivers: the per-system ``set_source`` loop of ``Jacobian``), one batched solve, ONE ``grad_acc_add`` (or
+      ``grad_acc3_add``) with the chunk's parked fields.  NaN entries of ``w`` count as zero.  A pair whose row is all zero is
+      not solved for: its system stays in the batch of its chunk with a zero source, which ``solve_sources`` freezes at entry
+      (zero field, no cycle), it is not accumulated (``use = 0``) and its info is ``None``; a chunk whose rows are all zero is
+      skipped altogether.  One ``nC``-sized array (three with ``components=True``) comes back per frequency.
+    * ``gauss_newton(v, weights)``: both products chunk by chunk -- ``jvec_source_b``, solve, data, ``set_receiver_adjoint_b`` with
+      ``conj(weights * data)``, solve, ``grad_acc_add`` -- so that every chunk's forward fields are visited once.  ``weights`` are
+      real and broadcast to the data shape; a NaN in ``weights`` or in the data means "no datum".
+
+    SUMMATION ORDER (part of the contract): ``G_f`` is the sequential sum of the pairs' gradients (``DeviceMG.gradient`` of the
+    pair, i.e. ``-Jacobian.jtvec``) over the sources in ascending order starting from zero, formed by the kernel; the result is
+    ``-(((0 + G_0) + G_1) + ...)`` in the order of ``freqs``, formed on the host (``_sum_survey``).  ``partial`` holds the ``G_f``
+    with shape ``(n_freq,) + vnC`` (``(3, n_freq) + vnC`` with ``components=True``): what ``shard.combine_survey_gradient`` takes,
+    whose result is then ``-jtvec``.  Every system goes through the arithmetic of a solve of its own: all results, cycle counts and
+    norms are independent of ``batch``, bit for bit.
+
+    Models, ``rec``, ``receiver_interpolation``, ``adjoint``, ``electric`` and the ``solver_opts`` (multigrid only) are those of
+    ``Jacobian`` (tri-axial models included, without ``mu_r`` / ``epsilon_r``; ``electric=False`` needs ``adjoint='exact'``), with
+    the defaults ``'cubic'`` and ``'exact'``: the pair ``jvec`` / ``jtvec`` is then an adjoint pair, and ``gauss_newton`` symmetric
+    positive semi-definite, to the accuracy of the solves.  ``forward_info[i][j]`` and, after a product, ``info[i][j]`` (the last
+    solve of the pair; ``jvec_info`` the J v solve of ``gauss_newton``) are the solver info dicts."""
+
+    def __init__(self, grid, model, sources, freqs, rec, batch=8, receiver_interpolation='cubic', adjoint='exact', electric=True,
+                 strength=0, device=0, **solver_opts):
+        if receiver_interpolation not in ('linear', 'cubic'):
+            raise ValueError(f"`receiver_interpolation` must be 'linear' or 'cubic'; provided: {receiver_interpolation!r}.")
+        if adjoint not in ('reference', 'exact'):
+            raise ValueError(f"`adjoint` must be 'reference' or 'exact'; provided: {adjoint!r}.")
+        if not electric and adjoint != 'exact':
+            raise NotImplementedError("Jacobian: magnetic receivers are implemented with adjoint='exact' only (the reference's "
+                                      "rule, loop sources, is not).")
+        if getattr(model, 'mu_r', None) is not None or getattr(model, 'epsilon_r', None) is not None:
+            raise NotImplementedError("Jacobian not implemented for el. permittivity / magn. permeability.")
+        if int(batch) != batch or not 1 <= int(batch) <= 64:
+            raise ValueError(f"`batch` must be an integer from 1 to 64; provided: {batch!r}.")
+        if len(rec) != 5:
+            raise ValueError("`rec` needs to be in the form (x, y, z, azimuth, dip).\n"
+                             f"Length of provided `rec`: {len(rec)}.")
+        if solver_opts.get('sslsolver'):
+            raise NotImplementedError("SurveyJacobian: the products are multigrid solves; Krylov solvers are not implemented.")
+        self.sources = list(sources)
+        self.freqs = [float(f) for f in np.atleast_1d(freqs)]
+        if len(self.sources) < 1 or len(self.freqs) < 1:
+            raise ValueError("SurveyJacobian: no sources or no frequencies.")
+        self.grid, self.model = grid, model
+        self.n_src, self.n_freq = len(self.sources), len(self.freqs)
+        self.n_rec = max(np.atleast_1d(c).size for c in rec)
+        self.rec = tuple(np.broadcast_to(np.asarray(c, dtype=np.float64), (self.n_rec,)) for c in rec)
+        self.receiver_interpolation = receiver_interpolation
+        self.adjoint, self.electric = adjoint, bool(electric)
+        self.batch, self.strength, self.device = int(batch), strength, device
+        self._opts = {k: v for k, v in solver_opts.items() if k not in ('return_info', 'sslsolver')}
+        self._specs = [fields.FrequencySpec(f) for f in self.freqs]
+        self._vnC = tuple(int(n) for n in grid.vnC)
+        self._nb = min(self.batch, self.n_src)
+        self._chunks = [(i0, min(self._nb, self.n_src - i0)) for i0 in range(0, self.n_src, self._nb)]
+        cplx = any(sp.dtype.kind == 'c' for sp in self._specs)
+        self.dtype = np.dtype(np.complex128 if cplx else np.float64)
+        self._handles = None
+        self.synthetic = self.forward_info = self.info = self.jvec_info = self.partial = None
+
+    # ---- handles ------------------------------------------------------------------------------------------------------
+    def open(self):
+        """Create the handles, size and allocate the parked fields, solve all pairs forward (chunk by chunk), extract the data."""
+        if self._handles is not None:
+            return self
+        ns, nf, nb = self.n_src, self.n_freq, self._nb
+        parts = models.model_parts(self.grid, self.model, raw=True)
+        handles, self._slot, nslots = {}, {}, {}
+        try:
+            for j, spec in enumerate(self._specs):
+                key = spec.dtype.str
+                if key not in handles:
+                    dev = handles[key] = solver.DeviceMG.from_model_parts(self.grid, *parts, smu0=spec.smu0, device=self.device)
+                    if nb > 1:
+                        dev.set_batch(nb)
+                    dev._smu0 = spec.smu0
+                    nslots[key] = 0
+                self._slot[j] = nslots[key]                     # first batched vector of frequency j on its handle
+                nslots[key] += len(self._chunks)
+            # the parked forward fields: one batched vector per (frequency, chunk), sized and allocated before the first solve
+            need = sum(nslots[key] * nb * dev.nE * dev.dtype.itemsize for key, dev in handles.items())
+            mi = _lib.mem_info(self.device)
+            free = mi['free'] + mi['pooled_on_device']
+            if need >= 0.92 * free:
+                raise _lib.HipLibraryError(
+                    f"SurveyJacobian: the forward fields of {ns} sources x {nf} frequencies need {need} bytes of device memory, "
+                    f"{free} bytes are free; use fewer sources or frequencies per SurveyJacobian (frequency shards).")
+            for key, dev in handles.items():
+                dev.bvec_alloc(nslots[key])
+            self.synthetic = np.full((ns, nf, self.n_rec), np.nan, dtype=self.dtype)
+            self.forward_info = [[None] * nf for _ in range(ns)]
+            for j in range(nf):
+                dev, smu0 = self._target(handles, j)
+                for c, (i0, n) in enumerate(self._chunks):
+                    for b in range(n):
+                        dev.select(b)
+                        dev.set_source(self.sources[i0 + b], smu0, strength=self.strength)
+                    infos = self._solve(dev, j, n)
+                    for b in range(n):
+                        self.forward_info[i0 + b][j] = infos[b]
+                        dev.select(b)
+                        self.synthetic[i0 + b, j] = self._data(dev, smu0)
+                    # park the chunk's forward fields (the solve has left all but the last system to finish frozen)
+                    dev.set_mask(self._flags(n))
+                    dev.bvec_copy(self._slot[j] + c, dev.EFIELD)
+        except BaseException:
+            for dev in handles.values():
+                dev.close()
+            raise
+        self._handles = handles
+        return self
+
+    def close(self):
+        if self._handles is not None:
+            for dev in self._handles.values():
+                dev.close()
+            self._handles = None
+
+    def __enter__(self):
+        return self.open()
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def device_bytes(self):
+        """Device memory of the handles, parked forward fields and accumulators included."""
+        return sum(dev.device_bytes for dev in self._require_open().values())
+
+    def _require_open(self):
+        if self._handles is None:
+            raise RuntimeError("SurveyJacobian: the handles are closed (use it inside its `with` block, or call open()).")
+        return self._handles
+
+    def _target(self, handles, j):
+        """The handle of frequency j, re-targeted to it if need be, and its s mu_0."""
+        spec = self._specs[j]
+        dev = handles[spec.dtype.str]
+        if dev._smu0 != spec.smu0:
+            dev.set_smu0(spec.smu0, sval=spec.sval)
+            dev._smu0 = spec.smu0
+        return dev, spec.smu0
+
+    def _flags(self, n):
+        f = np.zeros(self._nb, dtype=np.int32)
+        f[:n] = 1
+        return f
+
+    def _solve(self, dev, j, n):
+        _, infos = solver.solve_sources(self.grid, None, None, self.freqs[j], handle=dev, resident=n, download=False, **self._opts)
+        return infos
+
+    def _data(self, dev, smu0):
+        if self.electric:
+            return dev.get_receiver_response(self.rec, method=self.receiver_interpolation)
+        return dev.get_receiver_response(self.rec, magnetic=True, smu0=smu0, method=self.receiver_interpolation)
+
+    # ---- arguments ----------------------------------------------------------------------------------------------------
+    def _perturbation(self, v):
+        vecs, single = _perturbations(v, self._vnC)
+        if not single:
+            raise ValueError(f"`v` must have shape {self._vnC} (or be a 3-tuple of such arrays): one perturbation per product.")
+        return vecs[0]
+
+    def _data_array(self, w, name):
+        shape = (self.n_src, self.n_freq, self.n_rec)
+        w = np.asarray(w)
+        if w.shape != shape:
+            raise ValueError(f"`{name}` must have shape (n_src, n_freq, n_rec) = {shape}; provided: {w.shape}.")
+        if np.iscomplexobj(w):
+            for j, spec in enumerate(self._specs):
+                if spec.dtype.kind != 'c' and np.any(np.nan_to_num(w[:, j].imag) != 0):
+                    raise TypeError(f"`{name}` must be real for the Laplace-domain entries of `freqs`.")
+        return w
+
+    def _weights(self, weights):
+        shape = (self.n_src, self.n_freq, self.n_rec)
+        if weights is None:
+            return np.ones(shape)
+        if np.iscomplexobj(weights):
+            raise TypeError("`weights` must be real.")
+        try:
+            return np.broadcast_to(np.asarray(weights, dtype=np.float64), shape)
+        except ValueError:
+            raise ValueError(f"`weights` must be broadcastable to the data shape {shape}; provided: {np.shape(weights)}.") from None
+
+    # ---- the products -------------------------------------------------------------------------------------------------
+    def _adjoint_sources(self, dev, smu0, cw, n):
+        """Sources of the systems 0 .. n-1 <- P^T cw[b] (an all-zero row: a zero source)."""
+        if self.receiver_interpolation == 'linear' or self.adjoint == 'exact':
+            rows = np.zeros((self._nb, self.n_rec), dtype=dev.dtype)
+            rows[:n] = cw
+            dev.set_receiver_adjoint_b(self.rec, rows, self._flags(n), method=self.receiver_interpolation,
+                                       magnetic=not self.electric, smu0=smu0)
+            return
+        # 'cubic' receivers with the reference's rule: per system as Jacobian builds it
+        for b in range(n):
+            dev.select(b)
+            first = True
+            for k in range(self.n_rec):
+                if cw[b, k] == 0:
+                    continue
+                dev.set_source([c[k] for c in self.rec], smu0, strength=cw[b, k] / smu0, accumulate=not first)
+                first = False
+            if first:
+                dev.vec_scale(dev.SFIELD, 0.0)
+
+    def _sweep(self, vec, w, weights, components):
+        """Frequency by frequency and chunk by chunk: [J v: source, solve, data] then [J^T w: source, solve, accumulate], the rows
+        ``w`` given or ``weights * (J v)``."""
+        handles = self._require_open()
+        ns, nf, nb = self.n_src, self.n_freq, self._nb
+        adj = w is not None or weights is not None
+        dd = np.full((ns, nf, self.n_rec), np.nan, dtype=self.dtype) if vec is not None else None
+        jinfo = [[None] * nf for _ in range(ns)]
+        binfo = [[None] * nf for _ in range(ns)]
+        nacc = 3 if components else 1
+        partial = np.zeros((nacc, nf) + self._vnC[::-1]).transpose(0, 1, 4, 3, 2) if adj else None     # every G_f F-ordered
+        for j in range(nf):
+            dev, smu0 = self._target(handles, j)
+            real = dev.dtype.kind != 'c'
+            if adj:
+                dev.grad_acc3_reset() if components else dev.grad_acc_reset()
+            for c, (i0, n) in enumerate(self._chunks):
+                slot = self._slot[j] + c
+                if vec is not None:
+                    dev.jvec_source_b(slot, smu0, *vec, self._flags(n))
+                    infos = self._solve(dev, j, n)
+                    for b in range(n):
+                        jinfo[i0 + b][j] = infos[b]
+                        dev.select(b)
+                        dd[i0 + b, j] = self._data(dev, smu0)
+                if not adj:
+                    continue
+                rows = w[i0:i0 + n, j] if w is not None else weights[i0:i0 + n, j] * dd[i0:i0 + n, j]
+                if real:
+                    rows = rows.real
+                cw = np.where(np.isnan(rows), 0, np.conj(rows))         # NaN (no datum) counts as zero
+                live = np.any(cw != 0, axis=1)
+                if not live.any():
+                    continue
+                self._adjoint_sources(dev, smu0, cw, n)
+                infos = self._solve(dev, j, n)
+                use = np.zeros(nb, dtype=np.int32)
+                use[:n] = live
+                for b in range(n):
+                    if live[b]:
+                        binfo[i0 + b][j] = infos[b]
+                if components:
+                    dev.grad_acc3_add(slot, smu0, use)
+                else:
+                    dev.grad_acc_add(slot, smu0, use)
+            if adj:
+                got = dev.grad_acc3_get() if components else (dev.grad_acc_get(),)
+                for q in range(nacc):
+                    partial[q, j] = got[q].reshape(self._vnC, order='F')
+        return dd, jinfo, partial, binfo
+
+    def _result(self, partial, components):
+        """``-(((0 + G_0) + G_1) + ...)`` per accumulator."""
+        zeros = np.zeros((self.n_src, self.n_freq))
+        out = tuple(-_sum_survey(p, zeros, self._vnC)[1] for p in partial)
+        self.partial = partial if components else partial[0]
+        return out if components else out[0]
+
+    def jvec(self, v):
+        """``J v`` for all pairs: ``(n_src, n_freq, n_rec)``; ``v`` as for ``Jacobian.jvec`` (one perturbation)."""
+        vec = self._perturbation(v)
+        dd, self.info, _, _ = self._sweep(vec, None, None, False)
+        return dd
+
+    def jtvec(self, w, components=False):
+        """``J^T w = sum over the pairs of Jacobian.jtvec(w[i, j])`` in the defined order: a real cell array of shape ``grid.vnC``
+        (F-ordered), or the three terms ``(g_x, g_y, g_z)`` of sigma_x, sigma_y, sigma_z with ``components=True``."""
+        w = self._data_array(w, 'w')
+        _, _, partial, self.info = self._sweep(None, w, None, components)
+        return self._result(partial, components)
+
+    def gauss_newton(self, v, weights=None, components=False):
+        """``J^T W J v``, bit for bit ``jtvec(weights * jvec(v), components)``, the two products run chunk by chunk."""
+        vec = self._perturbation(v)
+        weights = self._weights(weights)
+        _, self.jvec_info, partial, self.info = self._sweep(vec, None, weights, components)
+        return self._result(partial, components)
 
 
 def jvec(grid, model, src, freq, rec, v, **kwargs):

@@ -241,6 +241,76 @@ class DeviceMG:
         _lib.check(self._lib.emg3d_mg_grad_acc_get(self._h, _lib.ptr(out)), "emg3d_mg_grad_acc_get")
         return out
 
+    def _use_flags(self, use, what):
+        u = np.ascontiguousarray(use, dtype=np.int32)
+        if u.size != self.nsys:
+            raise ValueError(f"{what}: {u.size} flags for {self.nsys} systems.")
+        return u
+
+    # ---- the same per direction: three accumulators, independent of the one above (optimize.SurveyJacobian) ----
+    def grad_acc3_reset(self):
+        """Zero the handle's three per-direction gradient accumulators (``nC`` doubles each, allocated on first use)."""
+        _lib.check(self._lib.emg3d_mg_grad_acc3_reset(self._h), "emg3d_mg_grad_acc3_reset")
+
+    def grad_acc3_add(self, fwd_bvec, smu0, use):
+        """``acc_c = (((acc_c + g_c,0) + g_c,1) + ...)`` for ``c = x, y, z`` over the systems with ``use[b] != 0`` in ascending
+        order, in one launch: ``g_c,b`` is bit for bit ``gradient(components=True)`` of system ``b`` (fields as ``grad_acc_add``)."""
+        a = complex(smu0)
+        u = self._use_flags(use, "grad_acc3_add")
+        st = self._lib.emg3d_mg_grad_acc3_add(self._h, int(fwd_bvec), a.real, a.imag, _lib.ptr(u))
+        if st == -2:
+            raise ValueError(f"grad_acc3_add: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy).")
+        _lib.check(st, "emg3d_mg_grad_acc3_add")
+
+    def grad_acc3_get(self):
+        """The three accumulators ``(acc_x, acc_y, acc_z)``: ``nC`` doubles each, F-ordered."""
+        outs = [np.empty(self.nC, dtype=np.float64) for _ in range(3)]
+        _lib.check(self._lib.emg3d_mg_grad_acc3_get(self._h, *(_lib.ptr(o) for o in outs)), "emg3d_mg_grad_acc3_get")
+        return tuple(outs)
+
+    def _perturbation_ptrs(self, vs, what):
+        held, ptrs = [], []
+        for v in vs:
+            if v is None:
+                ptrs.append(ctypes.c_void_p(None))
+                continue
+            same = [h for src, h in held if src is v]
+            arr = same[0] if same else np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel(order='F'))
+            if arr.size != self.nC:
+                raise ValueError(f"{what}: {arr.size} values for {self.nC} cells.")
+            held.append((v, arr))
+            ptrs.append(_lib.ptr(arr))
+        return held, ptrs
+
+    def jvec_source_b(self, fwd_bvec, smu0, vx, vy, vz, use):
+        """Sources of the systems with ``use[b] != 0`` <- ``s mu_0 C(v) E_b`` in one launch (``emg3d_mg_jvec_source_b``): ``E_b`` =
+        slice ``b`` of the batched vector ``fwd_bvec``, one perturbation ``vx, vy, vz`` (as ``jvec_source``) for all of them.  Per
+        system bit for bit ``jvec_source``; the sources of the other systems are not touched."""
+        a = complex(smu0)
+        u = self._use_flags(use, "jvec_source_b")
+        held, ptrs = self._perturbation_ptrs((vx, vy, vz), "jvec_source_b")
+        st = self._lib.emg3d_mg_jvec_source_b(self._h, int(fwd_bvec), a.real, a.imag, *ptrs, _lib.ptr(u))
+        if st == -2:
+            raise ValueError(f"jvec_source_b: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy), "
+                             "or a complex s*mu_0 on a float64 handle.")
+        _lib.check(st, "emg3d_mg_jvec_source_b")
+
+    def set_receiver_adjoint_b(self, rec, w, use, accumulate=False, method='linear', magnetic=False, smu0=None):
+        """``set_receiver_adjoint`` for the systems with ``use[b] != 0`` in one call (``emg3d_mg_set_receiver_adjoint_b``): ``w`` has
+        shape ``(nsys, n_rec)``, row ``b`` belongs to system ``b``.  The tables that depend on grid and receivers are built once;
+        per system bit for bit ``set_receiver_adjoint``; the sources of the other systems are not touched."""
+        if method not in ('cubic', 'linear'):
+            raise ValueError(f"`method` must be 'cubic' or 'linear'; provided: {method!r}.")
+        if magnetic and smu0 is None:
+            raise ValueError("magnetic receivers need `smu0` (field.smu0).")
+        n, xyz, fac = fields._receiver_args(rec)
+        u = self._use_flags(use, "set_receiver_adjoint_b")
+        wv = np.ascontiguousarray(np.broadcast_to(np.asarray(w), (self.nsys, n)), dtype=self.dtype)
+        a = complex(smu0) if magnetic else 0j
+        _lib.check(self._lib.emg3d_mg_set_receiver_adjoint_b(self._h, int(method == 'cubic'), int(bool(magnetic)), a.real, a.imag,
+                                                             n, _lib.ptr(xyz), _lib.ptr(fac), _lib.ptr(wv), _lib.ptr(u),
+                                                             int(bool(accumulate))), "emg3d_mg_set_receiver_adjoint_b")
+
     def jvec_source(self, efield_vec, smu0, vx, vy, vz):
         """Source of the selected system <- ``s mu_0 C(v) E`` (``emg3d_mg_jvec_source``): ``E`` = workspace vector
         ``efield_vec``, ``vx, vy, vz`` conductivity perturbations per direction (``nC`` values, F-ordered; ``None``: none)."""

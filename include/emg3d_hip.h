@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 108
+#define EMG3D_HIP_ABI_VERSION 109
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -250,6 +250,14 @@ int emg3d_mg_gradient3(emg3d_mg_t* mg, int efield_vec, double smu0_re, double sm
 int emg3d_mg_grad_acc_reset(emg3d_mg_t* mg);
 int emg3d_mg_grad_acc_add(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use);
 int emg3d_mg_grad_acc_get(emg3d_mg_t* mg, double* out);
+/* The same per direction (optimize.SurveyJacobian, components=True): three accumulators of nC doubles each, of the handle's own like
+ * the one above and independent of it (allocated on first use, counted by emg3d_mg_device_bytes, freed with the handle).
+ *   grad_acc3_add: acc_c = (((acc_c + g_c,0) + g_c,1) + ...) for c = x, y, z over the used systems in ascending order, ONE launch;
+ *                  g_c,b is bit for bit what emg3d_mg_gradient3 returns for system b (fields as for grad_acc_add, -2 likewise).
+ *   grad_acc3_get: the three accumulators, nC doubles each, F-ordered.                                                      */
+int emg3d_mg_grad_acc3_reset(emg3d_mg_t* mg);
+int emg3d_mg_grad_acc3_add(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use);
+int emg3d_mg_grad_acc3_get(emg3d_mg_t* mg, double* out_x, double* out_y, double* out_z);
 
 /* ---- sensitivity products (optimize.Jacobian) --------------------------------------------------------------------
  * The reference (v0.17.0) has the gradient only; these are the pieces of J v and J^T w with J = d(data) / d(conductivity) for
@@ -268,6 +276,15 @@ int emg3d_cells2edges(int dtype, int64_t nx, int64_t ny, int64_t nz, const void*
  * four cells: deterministic.  Overwrites the residual buffer.                                                          */
 int emg3d_mg_jvec_source(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, const double* vx, const double* vy,
                          const double* vz);
+/* The same for the systems of a batched handle that share ONE perturbation and have a forward field each (optimize.SurveyJacobian):
+ * source of every system b with use[b] != 0 (use: nsys flags) <- s mu_0 C(v) o E_b, E_b = slice b of the batched vector `fwd_bvec`
+ * (saved with emg3d_mg_bvec_copy(id, -2); -2 for a bad id or fwd_bvec < 0: a saved copy, not the live field), in ONE launch: a thread
+ * forms C(v) of its edge once and loops over the used systems.  Slice b of the source array is bit for bit what emg3d_mg_jvec_source
+ * writes for the selected system b with the same field; PEC boundary edges of the used systems are exact zeros; the sources of the
+ * other systems are not touched.  v is uploaded once per call.  Per edge and used system sizeof(dtype) bytes are read and
+ * sizeof(dtype) written.  Overwrites the residual buffer.                                                                    */
+int emg3d_mg_jvec_source_b(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const double* vx, const double* vy,
+                           const double* vz, const int32_t* use);
 /* Linear receivers: resp[r] = sum_c factors[c][r] * (trilinear interpolation of component c of the selected system's field on
  * the trimmed points of emg3d_get_receiver_response), NaN outside them; xyz / factors as there.  This is the receiver
  * operator P whose transpose the next call applies.                                                                    */
@@ -294,6 +311,15 @@ int emg3d_mg_get_receiver_response_linear_h(emg3d_mg_t* mg, double smu0_re, doub
  * atomics: results repeat bit for bit; PEC boundary edges stay exact zeros.                                                  */
 int emg3d_mg_set_receiver_adjoint_ex(emg3d_mg_t* mg, int method, int magnetic, double smu0_re, double smu0_im, int64_t n,
                                      const double* xyz, const double* factors, const void* w, int accumulate);
+/* The same for all systems of a batched handle in one call: source of every system b with use[b] != 0 (+)= P^T w_b, w = [nsys][n]
+ * values of dtype (row b belongs to system b; the rows of unused systems are not read as data).  The tables that depend on the grid
+ * and the receivers only (edge -> contributions, coefficient -> contributions, with the fractional indices and stencil weights) are
+ * built and uploaded ONCE, w is uploaded once; per system only kernels are issued (gather with that system's row, transposed
+ * prefilter, trim-add, transposed curl for magnetic receivers).  Slice b of the source array is bit for bit what
+ * emg3d_mg_set_receiver_adjoint_ex gives on the selected system b with row b; a used system whose row is all zero gets a zero source
+ * (accumulate == 0); the sources of the other systems are not touched.                                                        */
+int emg3d_mg_set_receiver_adjoint_b(emg3d_mg_t* mg, int method, int magnetic, double smu0_re, double smu0_im, int64_t n,
+                                    const double* xyz, const double* factors, const void* w, const int32_t* use, int accumulate);
 /* The same without a handle (mirrors emg3d_get_receiver_response): field (host, nE values of dtype, [fx|fy|fz]) = P^T w for the
  * electric (is_electric != 0) or magnetic (needs smu0) component set on the grid (hx, hy, hz, origin).                       */
 int emg3d_receiver_adjoint(int dtype, int64_t nx, int64_t ny, int64_t nz, const double* hx, const double* hy, const double* hz,
