@@ -22,7 +22,7 @@ c_double = ctypes.c_double
 c_dp = ctypes.POINTER(ctypes.c_double)
 
 # include/emg3d_hip.h: EMG3D_HIP_ABI_VERSION -- a library built from another header version is refused at load
-ABI_VERSION = 109
+ABI_VERSION = 110
 
 # name -> (restype, argtypes); mirrors include/emg3d_hip.h one to one.
 SIGNATURES = {
@@ -46,6 +46,8 @@ SIGNATURES = {
     "emg3d_prolongation": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
     "emg3d_restrict_model": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_int]),
     "emg3d_sweep_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, ctypes.c_char_p, ctypes.POINTER(c_i64)]),
+    "emg3d_sweep_fuse_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, ctypes.POINTER(c_i64),
+                                      ctypes.POINTER(c_i64), c_i64]),
     "emg3d_mg_create": (c_int, [ctypes.POINTER(c_vp), c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp,
                                 c_vp, c_vp, c_vp, c_vp, c_int]),
     "emg3d_mg_destroy": (None, [c_vp]),
@@ -245,3 +247,25 @@ def sweep_plan(vnC, direction, dtype=np.complex128, ordering='colour', nsys=1, c
                                   1 if ordering == 'colour' else 0, int(nsys), int(cu_count), name, info), "emg3d_sweep_plan")
     return {"kernel": name.value.decode(), "lines_per_colour": info[0], "lines_per_wave": info[1], "rounds": info[2],
             "factor_kind": info[3], "split": bool(info[4]), "big_offsets": bool(info[5])}
+
+
+def sweep_fuse_plan(vnC, direction, npass, dtype=np.complex128, ordering='colour', nsys=1, cu_count=0, own=0, max_seg=0, budget=0):
+    """How the library issues a smoothing call of ``npass`` colour passes along ``direction`` (1, 2, 3) on a level of ``vnC`` cells
+    -- ``emg3d_sweep_fuse_plan``: per-pass launches (``fused`` False) or all passes in one launch on private slab copies.  Shape
+    logic only.  ``slabs``: per slab the own line nodes ``own`` = (x0, x1), the owned edge indices ``edges`` = (a, b), both half
+    open, and per pass the live nodes (lo, hi), inclusive."""
+    info = (c_i64 * 8)()
+    cap = (4 + 2 * max(int(npass), 0)) * (max(vnC) + 1)
+    ranges = (c_i64 * cap)()
+    check(load().emg3d_sweep_fuse_plan(dtype_code(dtype), int(vnC[0]), int(vnC[1]), int(vnC[2]), int(direction),
+                                       1 if ordering == 'colour' else 0, int(nsys), int(cu_count), int(npass), int(own), int(max_seg), int(budget),
+                                       info, ranges, cap), "emg3d_sweep_fuse_plan")
+    out = {"fused": bool(info[0]), "axis": info[1], "nX": info[2], "own": info[3], "nslabs": info[4], "npass": info[5],
+           "waves": info[6], "scratch_bytes": info[7], "slabs": []}
+    if out["fused"]:
+        per = 4 + 2 * int(npass)
+        for k in range(info[4]):
+            r = ranges[per * k:per * (k + 1)]
+            out["slabs"].append({"own": (r[0], r[1]), "edges": (r[2], r[3]),
+                                 "live": [(r[4 + 2 * p], r[5 + 2 * p]) for p in range(int(npass))]})
+    return out

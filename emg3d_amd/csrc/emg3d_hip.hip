@@ -539,6 +539,38 @@ static int sweep_plan_impl(i64 nx, i64 ny, i64 nz, int dir, int order, int nsys,
     return 0;
 }
 
+// emg3d_sweep_fuse_plan: plan_fuse of sweep_plan.hpp on a bare shape, and its per-slab ranges
+template <class T>
+static int fuse_plan_impl(i64 nx, i64 ny, i64 nz, int dir, int order, int nsys, int cu_count, int npass, int own, int max_seg, i64 budget, int64_t* info,
+                          int64_t* ranges, i64 nranges) {
+    SweepKnobs K;
+    if (cu_count > 0) K.simds = 4 * (i64)cu_count;
+    else sweep_device_knobs<T>(K, current_device());
+    K.order = order; K.nsys = nsys;
+    if (own > 0) K.fuse_own = own;
+    if (max_seg > 0) K.fuse_max_seg = max_seg;
+    if (budget > 0) K.fuse_max_bytes = budget;
+    const SweepShape G{{nx, ny, nz}, (int)sizeof(T)};
+    const FusePlan f = plan_fuse(K, G, dir - 1, npass);
+    int P, Q;
+    sweep_axes(dir - 1, P, Q);
+    info[0] = f.fused ? 1 : 0; info[1] = f.axis ? Q : P; info[2] = f.g.nX; info[3] = f.g.own; info[4] = f.g.nslabs; info[5] = f.g.npass;
+    info[6] = f.nw; info[7] = f.scratch_bytes;
+    if (!f.fused || !ranges) return 0;
+    const i64 per = 4 + 2 * (i64)npass;
+    if (nranges < per * f.g.nslabs) return -2;
+    for (int k = 0; k < f.g.nslabs; ++k) {
+        int64_t* r = ranges + per * k;
+        r[0] = fuse_x0(f.g, k); r[1] = fuse_x1(f.g, k);
+        // the indices (nodes 0 .. nX, cells 0 .. nX - 1) the slab owns: [r[2], r[3]) -- by the same function the scatter uses
+        i64 a = -1, b = -1;
+        for (int j = 0; j <= f.g.nX; ++j) if (fuse_owner(f.g, j) == k) { if (a < 0) a = j; b = j + 1; }
+        r[2] = a; r[3] = b;
+        for (int p = 0; p < npass; ++p) { r[4 + 2 * p] = fuse_lo(f.g, k, p); r[5 + 2 * p] = fuse_hi(f.g, k, p); }
+    }
+    return 0;
+}
+
 // the perturbations (up to 3 nC doubles) are staged in the residual buffer (3 nC * 8 < nE * sizeof(T)); the same host array for
 // several directions is uploaded once
 template <class T>
@@ -879,6 +911,13 @@ int emg3d_sweep_plan(int dtype, int64_t nx, int64_t ny, int64_t nz, int dir, int
     if (nx < 2 || ny < 2 || nz < 2 || dir < 1 || dir > 3 || order < 0 || order > 1 || nsys < 1 || nsys > 64 || !name || !info) return -2;
     return dtype ? sweep_plan_impl<c128>(nx, ny, nz, dir, order, nsys, cu_count, name, info)
                  : sweep_plan_impl<double>(nx, ny, nz, dir, order, nsys, cu_count, name, info);
+}
+
+int emg3d_sweep_fuse_plan(int dtype, int64_t nx, int64_t ny, int64_t nz, int dir, int order, int nsys, int cu_count, int npass, int own,
+                          int max_seg, int64_t budget, int64_t* info, int64_t* ranges, int64_t nranges) {
+    if (nx < 2 || ny < 2 || nz < 2 || dir < 1 || dir > 3 || order < 0 || order > 1 || nsys < 1 || nsys > 64 || npass < 0 || !info) return -2;
+    return dtype ? fuse_plan_impl<c128>(nx, ny, nz, dir, order, nsys, cu_count, npass, own, max_seg, budget, info, ranges, nranges)
+                 : fuse_plan_impl<double>(nx, ny, nz, dir, order, nsys, cu_count, npass, own, max_seg, budget, info, ranges, nranges);
 }
 
 int emg3d_mg_create(emg3d_mg_t** out, int dtype, int64_t nx, int64_t ny, int64_t nz, const double* hx,

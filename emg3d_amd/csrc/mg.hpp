@@ -67,6 +67,13 @@ struct Level {
     // per-lane launch descriptors of the scan kernel's colour launches (LineArgs::qd; smooth_qpl.hpp DM): [direction][colour]
     void* qd[3][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
     unsigned qdn[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    // private slab copies of the fused smoothing calls (MG::ensure_fuse): [system][slab][nE], elements allocated
+    T* fz[3] = {nullptr, nullptr, nullptr};
+    i64 fz_n[3] = {0, 0, 0};
+    // how a smoothing call of fuse_key = nu * 256 + order + 2 * systems is issued (MG::ensure_fuse; -1: not yet), and the colours of its passes
+    FusePlan fuse[3];
+    int fuse_key[3] = {-1, -1, -1};
+    std::vector<int> passes[3];
     i64 fac_lines[3] = {0, 0, 0};
     i64 fac_mid[3] = {0, 0, 0};   // middle block of the (two-sided) factorisation
     int fac_kind[3] = {0, 0, 0};  // 0: one-sided, 15 numbers per block (k_line_sweep_rp / _qpl, k_line_sweep); 3: mirrored
@@ -1163,6 +1170,8 @@ struct MG : emg3d_mg {
             }
         }
         a.qd = nullptr; a.qdn = 0;
+        a.fe = nullptr; a.fnE = 0; a.fax = a.fnX = a.fown = a.fns = a.fnp = 0; a.fseq = 0;
+        for (int c = 0; c < 4; ++c) { a.fqd[c] = nullptr; a.fqdn[c] = 0; }
         a.qpl = P.NW; a.qM = P.M; a.seg = P.seg; a.qlpw = 0;
         a.tha = P.helpers;
         a.mode = 0; a.cP = a.cQ = 0; a.cntA = a.cntB = 0; a.t = a.jQ0 = a.cnt = 0;
@@ -1476,11 +1485,88 @@ struct MG : emg3d_mg {
         check_launch();
     }
 
+    // The colours c = cP + 2 cQ of the passes of a call of nu sweeps in colour order -- THE list: the per-pass launches and the fused
+    // launch both run it.  The first sweep runs backward (core.py:552, 569).  A line update is a projection: re-solving a colour
+    // whose neighbours (all of other colours) have not changed since its last update reproduces the same values; a backward sweep
+    // ends with the colour the next forward sweep starts with, so the repeated colour at each turn-around is skipped (identical
+    // result up to rounding).  Colours without a line are left out.
+    void colour_passes(Level<T>& L, int dir, int nu, std::vector<int>& seq) {
+        int Pa, Qa;
+        sweep_axes(dir, Pa, Qa);
+        const i64 nP = L.nC[Pa], nQ = L.nC[Qa];
+        int iback = 0, last_c = -1;
+        seq.clear();
+        for (int it = 0; it < nu; ++it) {
+            iback = 1 - iback;
+            for (int ch = 0; ch < 4; ++ch) {
+                const int c = iback ? colour_perm_b[ch] : colour_perm[ch];
+                if (skip_idempotent && c == last_c) continue;
+                last_c = c;
+                if (((nP - (c & 1)) / 2) * ((nQ - (c >> 1)) / 2) <= 0) continue;
+                seq.push_back(c);
+            }
+        }
+    }
+    // How a call of nu sweeps along dir is issued (sweep_plan.hpp plan_fuse), decided once per (level, direction, nu): fused only with
+    // the descriptor tables of its colours and the private copies in hand (optional memory, asked for here -- also in the dry run
+    // before a capture; a refusal keeps the per-pass launches).  Level::passes[dir] holds the call's colours afterwards.
+    const FusePlan& ensure_fuse(Level<T>& L, int dir, int nu) {
+        const int key = nu * 256 + order + 2 * nsys;
+        if (L.fuse_key[dir] == key) return L.fuse[dir];
+        FusePlan& F = L.fuse[dir];
+        F = FusePlan();
+        L.fuse_key[dir] = key;
+        L.passes[dir].clear();
+        if (order != 1) return F;
+        colour_passes(L, dir, nu, L.passes[dir]);
+        const std::vector<int>& seq = L.passes[dir];
+        plan(L, dir);
+        F = plan_fuse(knobs, SweepShape{{L.nC[0], L.nC[1], L.nC[2]}, (int)sizeof(T)}, dir, (int)seq.size());
+        if (!F.fused) return F;
+        for (int c : seq) if (!L.qd[dir][c]) { F.fused = false; return F; }
+        const i64 need = (i64)nsys * F.g.nslabs * L.nE;
+        if (L.fz_n[dir] < need) {
+            T* z = try_alloc<T>(need);
+            if (!z) { F.fused = false; return F; }
+            // (the systems of a handle change only before its first cycle, emg3d_mg_set_batch: no captured launch holds the smaller block)
+            if (L.fz[dir]) release(L.fz[dir]);
+            L.fz[dir] = z; L.fz_n[dir] = need;
+        }
+        return F;
+    }
+    // all colour passes of the call in one launch on private slab copies, then every edge from its owner's copy
+    void smooth_fused(Level<T>& L, int dir, const SweepPlan& P, const FusePlan& F, const std::vector<int>& seq, const LineArgs<T>& a) {
+        LineArgs<T> b = a;
+        b.mode = 0; b.xcd = 0;
+        b.fe = L.fz[dir]; b.fnE = L.nE; b.fax = F.axis;
+        b.fnX = F.g.nX; b.fown = F.g.own; b.fns = F.g.nslabs; b.fnp = F.g.npass;
+        b.fseq = 0;
+        for (int p = 0; p < F.g.npass; ++p) b.fseq |= (unsigned long long)seq[(size_t)p] << (4 * p);
+        for (int c = 0; c < 4; ++c) { b.fqd[c] = L.qd[dir][c]; b.fqdn[c] = L.qd[dir][c] ? L.qdn[dir][c] : 0u; }
+        if (log_launches) fprintf(stderr, "[sweep] nC %lld %lld %lld L %d lines %lld kernel %s split %d fused passes %d slabs %d own %d\n", (long long)a.nC[0],
+                                  (long long)a.nC[1], (long long)a.nC[2], a.L, (long long)a.nLinesTot, P.name, a.split, F.g.npass, F.g.nslabs, F.g.own);
+        memcpy(sweep_name, P.name, sizeof sweep_name);
+        if (broken) return;
+        qpl_fused_launch<T>(P.family == SweepFamily::qpl_chain, bgrid((unsigned)F.g.nslabs), stream, b);
+        ScatterArgs sa;
+        sa.nE = L.nE; sa.g = F.g;
+        int Pa, Qa;
+        sweep_axes(dir, Pa, Qa);
+        sa.ax = F.axis ? Qa : Pa;
+        for (int c = 0; c < 3; ++c) {
+            sa.off[c] = L.fl.off[c];
+            sa.d0[c] = (unsigned)((c == 0) ? L.nC[0] : L.nC[0] + 1); sa.d1[c] = (unsigned)((c == 1) ? L.nC[1] : L.nC[1] + 1);
+        }
+        hipLaunchKernelGGL(k_scatter_slabs<T>, dim3((unsigned)((L.nE + EMG_BLOCK - 1) / EMG_BLOCK), (unsigned)nsys), dim3(EMG_BLOCK), 0, stream,
+                           a.e, (const T*)L.fz[dir], sa, a.bt);
+    }
+
     // nu sweeps along `dir`; conv_in / conv_out: convert e to / from the working copy
     void smooth_line(Level<T>& L, int dir, int nu, bool conv_in = true, bool conv_out = true) {
         if (nu <= 0) return;
         ensure_factor(L, dir);
         ensure_qdesc(L, dir);
+        const FusePlan& F = ensure_fuse(L, dir, nu);
         if (dry) { prepare_work(L, dir); return; }
         if (conv_in) to_work(L, dir);
         ensure_sflags(L, dir);          // (valid already inside a captured sequence: refresh_level0_source)
@@ -1489,30 +1575,21 @@ struct MG : emg3d_mg {
         const SweepPlan& P = plan(L, dir);
         const i64 nP = L.nC[a.P], nQ = L.nC[a.Q];
         const i64 nB[2] = {(nQ - 0) / 2, (nQ - 1) / 2};
+        if (order == 1) {
+            if (F.fused) smooth_fused(L, dir, P, F, L.passes[dir], a);
+            else for (int c : L.passes[dir]) {
+                a.mode = 0; a.cP = c & 1; a.cQ = c >> 1;
+                a.cntA = a.nA[a.cP]; a.cntB = nB[a.cQ];
+                a.rs.slot0 = (unsigned)a.base[c];
+                a.qd = L.qd[dir][c]; a.qdn = (L.qd[dir][c] ? L.qdn[dir][c] : 0u);
+                launch_sweep(P, a, a.cntA * a.cntB);
+            }
+            nu = 0;
+        }
         int iback = 0;
-        int last_c = -1;
-        for (int it = 0; it < nu; ++it) {
+        for (int it = 0; it < nu; ++it) {      // lexicographic order
             iback = 1 - iback;   // first sweep runs backward (core.py:552, 569)
-            if (order == 1) {
-                for (int ch = 0; ch < 4; ++ch) {
-                    const int c = iback ? colour_perm_b[ch] : colour_perm[ch];
-                    // A line update is a projection: re-solving a colour whose
-                    // neighbours (all of other colours) have not changed since
-                    // its last update reproduces the same values.  A backward sweep
-                    // ends with the colour the next forward sweep starts with: the
-                    // repeated colour at each turn-around is skipped (identical
-                    // result up to rounding).
-                    if (skip_idempotent && c == last_c) continue;
-                    last_c = c;
-                    a.mode = 0; a.cP = c & 1; a.cQ = c >> 1;
-                    a.cntA = a.nA[a.cP]; a.cntB = nB[a.cQ];
-                    a.rs.slot0 = (unsigned)a.base[c];
-                    a.qd = L.qd[dir][c]; a.qdn = (L.qd[dir][c] ? L.qdn[dir][c] : 0u);
-                    const i64 n = a.cntA * a.cntB;
-                    if (n <= 0) continue;
-                    launch_sweep(P, a, n);
-                }
-            } else {
+            {
                 const i64 tmin = 3, tmax = (nP - 1) + 2 * (nQ - 1);
                 if (lex_loop && a.qpl && a.qM == 1 && a.seg <= 16) {
                     // short lines: ONE workgroup per system loops over the hyperplanes (k_line_sweep_qpl mode 2) --
@@ -1838,7 +1915,7 @@ struct MG : emg3d_mg {
         // (the launch descriptors carry factor offsets of the layout they were generated for: they go with the factor)
         auto clear = [](Level<T>& L) {
             for (int d = 0; d < 3; ++d) {
-                L.fac[d] = nullptr; L.fac_kind[d] = 0; L.plan_key[d] = -1;
+                L.fac[d] = nullptr; L.fac_kind[d] = 0; L.plan_key[d] = -1; L.fuse_key[d] = -1;
                 for (int c = 0; c < 4; ++c) { L.qd[d][c] = nullptr; L.qdn[d][c] = 0; }
             }
         };

@@ -79,6 +79,15 @@ struct LineArgs {
     // model only), written once by the kernel's generating mode; [item][qdn threads]; nullptr: the kernel computes them
     const void* qd;
     unsigned qdn;
+    // fused colour passes (k_line_sweep_qpl FZ; sweep_plan.hpp plan_fuse): private copies [system][slab][fnE] with the level's strides,
+    // slab axis (0: P, 1: Q), FuseGeom (cells along the axis, own lines per slab, slabs, passes), the colour of pass p in bits
+    // 4 p .. 4 p + 1 of fseq, and the descriptor table of each colour
+    T* fe;
+    i64 fnE;
+    int fax, fnX, fown, fns, fnp;
+    unsigned long long fseq;
+    const void* fqd[4];
+    unsigned fqdn[4];
     i64 nLinesTot;
     i64 base[4];   // first slot of colour c = cP + 2 cQ
     i64 nA[2];     // lines per colour row: number of jP with parity cP

@@ -25,6 +25,7 @@
 // Factor layout (k_line_factor with LineArgs::qpl set, one-sided): [line][entry][M * SEG block slots].
 #pragma once
 #include "smooth.hpp"
+#include "sweep_plan.hpp"
 
 
 // broadcast lane K of every quad (DPP quad_perm, no LDS)
@@ -86,10 +87,15 @@ __device__ __forceinline__ void qpl_args_burst(const LineArgs<T>& a) {
 // takes z[1..4] of quad q - 1 from four lanes below (DPP row shift on 4-block lines, lane shuffles on 8-block lines), broadcasts the
 // four numbers inside the quad and applies its own row of the block map (4 complex multiply-adds), seg - 1 times; no LDS, no
 // barrier, 20 instead of 80 FP64 instructions per step.  Every quad runs every step (its value is final after step q and stays).
-template <class T, int NW, int M, bool HL = false, int DM = 0, bool CH = false>      // HL: hyperplane loop (mode 2, lexicographic order)
+// FZ (fused colour passes, sweep_plan.hpp plan_fuse): a workgroup = one slab of one system runs ALL colour passes of a smoothing call on
+// its private copy of the field (LineArgs::fe), a workgroup barrier between passes and no other synchronisation; the per-line body
+// one() is the unfused launch's, fed with the descriptor index the unfused launch would have given the line.  It never writes the
+// level's e (other slabs may still be copying in): k_scatter_slabs does, in a launch of its own.
+template <class T, int NW, int M, bool HL = false, int DM = 0, bool CH = false, bool FZ = false>      // HL: hyperplane loop (mode 2, lexicographic order)
 __global__ __launch_bounds__(64 * NW) void k_line_sweep_qpl(LineArgs<T> a) {
-    static_assert(DM == 0 || (!HL && NW == 1), "descriptors: one wave per workgroup, colour order");
-    static_assert(!CH || (NW == 1 && M == 1 && !HL), "chain form: lines inside one wave, one block per quad");
+    static_assert(DM == 0 || (!HL && (NW == 1 || FZ)), "descriptors: one wave per workgroup, colour order");
+    static_assert(!CH || ((NW == 1 || FZ) && M == 1 && !HL), "chain form: lines inside one wave, one block per quad");
+    static_assert(!FZ || (DM == 2 && M == 1 && !HL), "fused passes: descriptors, one block per quad, colour order");
     constexpr int NQ = 16 * NW;                 // quads per workgroup; a quad owns M consecutive blocks
 #ifdef EMG3D_LAB
     // lab: cycle-counter stamps of workgroup 0 (EMG3D_Q_TILE=512): entry, arguments in, loads issued, loads in, forward scan done,
@@ -113,7 +119,12 @@ __global__ __launch_bounds__(64 * NW) void k_line_sweep_qpl(LineArgs<T> a) {
     typedef unsigned int u32;
     EMG_SWEEP_WG(a)
     // ---- exchange buffer: per quad the four rows of its map, five numbers each; double buffered --
-    __shared__ T xb[2][NQ][4][5];
+    __shared__ T xb[2][(FZ && CH) ? 1 : NQ][4][5];     // (the chain form does not use it)
+    // the field the lines work on: the level's (FZ: the slab's private copy, same strides); the descriptors of the colour
+    T* const ebase = FZ ? a.fe + ((i64)bsys_ * a.fns + wg) * a.fnE : a.e + boff_;
+    const void* qd_ = a.qd;
+    u32 qdn_ = a.qdn;
+    u32 tix = (u32)wg * (64u * NW) + (u32)tid;  // descriptor of this thread (DM != 0): [item][qdn threads], thread = logical workgroup x 64 + lane
     // One pass over the lines gline = 0 .. nlines-1 of a colour (mode 0) or of the hyperplane jP + 2 jQ = t_ (jQ from jQ0_)
     auto one = [&](const u32 gline, const u32 nlines, const u32 t_, const u32 jQ0_) {
     const bool live = gline < nlines;
@@ -122,7 +133,7 @@ __global__ __launch_bounds__(64 * NW) void k_line_sweep_qpl(LineArgs<T> a) {
     // 64-bit address pair per load
     auto ld_d = [](const double* base, u32 idx) -> double { return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + idx * 8u); };
     auto ld_t = [](const T* base, u32 idx) -> T { return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + idx * (u32)sizeof(T)); };
-    const T* __restrict__ e = (a.e + boff_);
+    const T* __restrict__ e = ebase;
     const T* __restrict__ s = (a.s + boff_);
     // ---- what the scans and the stores take from the prologue ----
     T Wr[M][5], W0[M][5];       // rows r+1 and 0 of the cached inverse
@@ -130,21 +141,19 @@ __global__ __launch_bounds__(64 * NW) void k_line_sweep_qpl(LineArgs<T> a) {
     double av[M][4], dv[M][4];  // A_i: row 0 = a_k, diagonal = d_k
     bool lastb[M], inl[M];
     u32 dS[M], dS0[M];          // element offsets of the row's own edge and of the edge along the line (source load = result store)
-    // descriptor of this thread (DM != 0): [item][LineArgs::qdn threads], thread = logical workgroup x 64 + lane
-    const u32 tix = (u32)wg * (64u * NW) + (u32)tid;
     constexpr int QD_U4 = 3, QD_D2 = 8;         // per block: 3 x uint4 (11 offsets / flags) + 8 x double2 (15 coefficient products)
     if constexpr (DM == 2) {
         // ================= descriptors loaded: offsets and coefficient products come from the table =================
-        const uint4* const q4 = reinterpret_cast<const uint4*>(a.qd);
-        const emg_d2* const c2 = reinterpret_cast<const emg_d2*>(q4 + (size_t)(QD_U4 * M) * a.qdn);
+        const uint4* const q4 = reinterpret_cast<const uint4*>(qd_);
+        const emg_d2* const c2 = reinterpret_cast<const emg_d2*>(q4 + (size_t)(QD_U4 * M) * qdn_);
         uint4 u[M][QD_U4];
         emg_d2 cf[M][QD_D2];
 #pragma unroll
         for (int j = 0; j < M; ++j) {
 #pragma unroll
-            for (int k = 0; k < QD_U4; ++k) u[j][k] = q4[(u32)(QD_U4 * j + k) * a.qdn + tix];
+            for (int k = 0; k < QD_U4; ++k) u[j][k] = q4[(u32)(QD_U4 * j + k) * qdn_ + tix];
 #pragma unroll
-            for (int k = 0; k < QD_D2; ++k) cf[j][k] = c2[(u32)(QD_D2 * j + k) * a.qdn + tix];
+            for (int k = 0; k < QD_D2; ++k) cf[j][k] = c2[(u32)(QD_D2 * j + k) * qdn_ + tix];
         }
         QPL_TS(2);
         T E[M][6], S[M], E0[M], S0[M];
@@ -362,7 +371,7 @@ __global__ __launch_bounds__(64 * NW) void k_line_sweep_qpl(LineArgs<T> a) {
 
     QPL_TS(3);
     // (lines of <= 16 quads live in one wave whatever the workgroup's size: a wave-level barrier suffices)
-    auto sync = [&]() { if (NW > 1 && (HL || seg > 16)) __syncthreads(); else __builtin_amdgcn_wave_barrier(); };
+    auto sync = [&]() { if (!FZ && NW > 1 && (HL || seg > 16)) __syncthreads(); else __builtin_amdgcn_wave_barrier(); };
     T mc, mG[4];        // my row of the chunk map: u -> mc + mG . u
     auto publish = [&](int p) {
         xb[p][quad][r][0] = mc;
@@ -545,7 +554,7 @@ __global__ __launch_bounds__(64 * NW) void k_line_sweep_qpl(LineArgs<T> a) {
     }
     QPL_TS(5);
     // x_i = z_i - W_i v
-    T* eo = (a.e + boff_);
+    T* eo = ebase;
 #pragma unroll
     for (int j = M - 1; j >= 0; --j) {
         T x0 = z0[j], xr = zr[j];
@@ -567,7 +576,65 @@ __global__ __launch_bounds__(64 * NW) void k_line_sweep_qpl(LineArgs<T> a) {
     QPL_TS(6);
     };      // one
 
-    if constexpr (!HL) {
+    if constexpr (FZ) {
+        const FuseGeom g{a.fnX, a.fown, a.fns, a.fnp};
+        const int k = (int)wg;
+        // ---- copy-in: every edge of the three components whose index along the slab axis X lies in [lo(0) - 1, hi(0) + 1] (cooperative;
+        //      components and axes in (L, P, Q) order, a component has cells along its own axis and nodes along the others) ----
+        {
+            T* __restrict__ dst = ebase;
+            const T* __restrict__ src = a.e + boff_;
+            const int ra = fuse_lo(g, k, 0) - 1, rb = fuse_hi(g, k, 0) + 1;
+            const int X = a.fax ? 2 : 1;
+            const u32 nO = a.fax ? a.rs.nP : a.rs.nQ;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const u32 dL = a.rs.nL + (c != 0 ? 1u : 0u), dX = (u32)g.nX + (c != X ? 1u : 0u), dO = nO + ((c == 0 || c == X) ? 1u : 0u);
+                const int rbc = rb < (int)dX - 1 ? rb : (int)dX - 1;
+                if (rbc < ra) continue;
+                const u32 w = (u32)(rbc - ra + 1);
+                const u32 stL = a.rs.st[c][0], stX = a.fax ? a.rs.st[c][2] : a.rs.st[c][1], stO = a.fax ? a.rs.st[c][1] : a.rs.st[c][2];
+                const bool xf = stX < stL;              // the faster of the two axes first
+                const u32 n0 = xf ? w : dL, n1 = xf ? dL : w, tot = n0 * n1 * dO;
+                for (u32 idx = (u32)tid; idx < tot; idx += 64u * NW) {
+                    const u32 t = idx / n0, i0 = idx - t * n0, i2 = t / n1, i1 = t - i2 * n1;
+                    const u32 iX = (u32)ra + (xf ? i0 : i1), iL = xf ? i1 : i0;
+                    const u32 off = a.rs.off[c] + iL * stL + iX * stX + i2 * stO;
+                    dst[off] = src[off];
+                }
+            }
+        }
+        __threadfence_block();
+        __syncthreads();
+        // ---- the passes: colour (fseq >> 4 p) & 3 on the lines of the live range of pass p, in rounds of the workgroup's lines (the
+        //      lines of a colour are independent: no barrier between rounds); see sweep_plan.hpp for the invariant ----
+        const u32 lslot = (u32)(quad >> lseg), wslot0 = (u32)(((tid >> 6) * 16) >> lseg);
+        for (int p = 0; p < g.npass; ++p) {
+            const int c = (int)((a.fseq >> (4 * p)) & 3ull);
+            const int cP = c & 1, cQ = c >> 1;
+            const u32 cA = (u32)a.nA[cP], cB = (u32)a.nB2[cQ];
+            const int cX = a.fax ? cQ : cP;
+            const u32 qa = (u32)(fuse_lo(g, k, p) - cX) >> 1, qb = (u32)(fuse_hi(g, k, p) + 1 - cX) >> 1;   // colour indices along X
+            const u32 nx = qb > qa ? qb - qa : 0u;
+            const u32 nloc = nx * (a.fax ? cA : cB);
+            qd_ = a.fqd[c]; qdn_ = a.fqdn[c];
+            for (u32 base = 0; base < nloc; base += (u32)lpg) {
+                if (base + wslot0 < nloc) {             // (wave-uniform: a wave without a line of this round skips it)
+                    const u32 m = base + lslot;
+                    const bool lv = m < nloc;
+                    const u32 mm = lv ? m : base + wslot0;      // dead slots work on a line of their wave (no stores)
+                    u32 qq, bq;
+                    if (a.fax == 0) { bq = mm / nx; qq = qa + (mm - bq * nx); }
+                    else { const u32 t = mm / cA; qq = mm - t * cA; bq = qa + t; }
+                    const u32 gl = bq * cA + qq;        // the line's index in its colour, and the thread the unfused launch gives it
+                    tix = ((gl >> (4 - lseg)) << 6) + ((((gl & ((16u >> lseg) - 1u)) << lseg) + (u32)ch) << 2) + (u32)r;
+                    one(lv ? 0u : 1u, 1u, 0u, 0u);
+                }
+            }
+            __threadfence_block();
+            __syncthreads();
+        }
+    } else if constexpr (!HL) {
         one((u32)wg * (u32)lpg + (u32)(quad >> lseg), (u32)((a.mode == 0) ? a.cntA * a.cntB : a.cnt), (u32)a.t, (u32)a.jQ0);
 #ifdef EMG3D_LAB
         if ((a.tile & 512) && blockIdx.x == 0 && threadIdx.x == 0) {

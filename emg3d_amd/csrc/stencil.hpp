@@ -4,6 +4,7 @@
 // lanes so that every global access of a wave is a contiguous run.
 #pragma once
 #include "common.hpp"
+#include "sweep_plan.hpp"
 // (the few kernels below that are not templates are `static`: this header is included by several translation units)
 
 #define EMG_BLOCK 256
@@ -966,4 +967,24 @@ __global__ __launch_bounds__(EMG_BLOCK) void k_split0(U* __restrict__ dst, const
         if (DIR > 0) dst[row * n0 + psplit(i, n0)] = src[t];
         else dst[t] = src[row * n0 + psplit(i, n0)];
     }
+}
+
+// Second launch of a fused smoothing call (k_line_sweep_qpl FZ, sweep_plan.hpp plan_fuse): every edge of the level's field from the
+// private copy of the slab that owns it.  Reference layout (x fastest); ax: the slab axis (0, 1, 2 = x, y, z); d0, d1: the extents of a
+// component along x and y.  Thread per edge (these levels have a few thousand); frozen systems keep their field.
+struct ScatterArgs {
+    i64 nE, off[3];
+    unsigned d0[3], d1[3];
+    int ax;
+    FuseGeom g;
+};
+template <class T>
+__global__ __launch_bounds__(EMG_BLOCK) void k_scatter_slabs(T* __restrict__ e, const T* __restrict__ fe, ScatterArgs a, Batch bt) {
+    EMG_BATCH(y, bt);
+    const i64 idx = (i64)blockIdx.x * EMG_BLOCK + threadIdx.x;
+    if (idx >= a.nE) return;
+    const int c = idx >= a.off[2] ? 2 : idx >= a.off[1] ? 1 : 0;
+    const unsigned l = (unsigned)(idx - a.off[c]), q = l / a.d0[c], i0 = l - q * a.d0[c], i2 = q / a.d1[c], i1 = q - i2 * a.d1[c];
+    const int k = fuse_owner(a.g, (int)(a.ax == 0 ? i0 : a.ax == 1 ? i1 : i2));
+    e[boff_ + idx] = fe[((i64)b_ * a.g.nslabs + k) * a.nE + idx];
 }

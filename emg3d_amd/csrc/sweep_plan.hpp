@@ -120,6 +120,12 @@ struct SweepKnobs {
     // In-kernel stamps at 128 x 4 x 4: 8330 -> 7500 cycles.
     int use_qdesc = (int)LAB_ENV("EMG3D_QDESC", 1);
     i64 qdesc_max_threads_env = LAB_ENV("EMG3D_QDESC_MAX", 0);
+    // Fused colour passes of a smoothing call on the levels of short lines (plan_fuse below): lines of at most fuse_max_seg quads (0:
+    // never); own lines per slab (0: 2); bytes of private copies a
+    // (level, direction) may take
+    int fuse_max_seg = (int)LAB_ENV("EMG3D_QPL_FUSE", 4);
+    i64 fuse_own = LAB_ENV("EMG3D_QPL_FUSE_W", 0);
+    i64 fuse_max_bytes = LAB_ENV("EMG3D_QPL_FUSE_BYTES", (i64)64 << 20);
     // k_line_sweep_tha on the mid levels the scan kernel served: colour order, no split copies, lines of tha_min_nl .. tha_mid_nl
     // (33..64) blocks, at least tha_min_lines lines per colour.  Measured per launch (profiles/r04_rs_shapes.txt, r04_tha_ab.txt):
     // the launch is as long as its chain wave's work (~7 us + 0.6 us per step: 25 us at 64 blocks, 19 us at 40) whatever the
@@ -362,4 +368,68 @@ inline SweepPlan plan_sweep(const SweepKnobs& K, const SweepShape& G, int dir) {
     }
     sweep_kernel_name(p.name, sizeof p.name, p.family, G.tsize, p1, p2);
     return p;
+}
+
+// ---- fused colour passes: how MG::smooth_line ISSUES a call on a level of short lines -----------------------------------------------
+// The colour passes of one smoothing call (7 for nu = 2: 4 nu less the colours repeated at the backward -> forward turn-arounds) are dependent launches of a
+// few microseconds each.  Where the plan below says so, ONE launch of the same scan kernel (smooth_qpl.hpp, FZ) runs all of them:
+// a workgroup owns a SLAB of `own` consecutive line nodes along the longer transverse axis X (P or Q), works on a private copy of
+// the part of the field it touches, and recomputes a halo of neighbouring lines that shrinks by one node per pass.  A second launch
+// (k_scatter_slabs) writes every edge of the level from its owner's private copy.  The kernel selection (SweepPlan) is untouched.
+//
+// Geometry along X (nX cells: lines at the nodes 1 .. nX - 1; node-type edges -- those along L and along the other transverse axis --
+// sit at nodes 0 .. nX, X-directed edges at cells 0 .. nX - 1, cell c between the nodes c and c + 1):
+//   slab k owns the line nodes [x0, x1) = [1 + k own, min(1 + (k + 1) own, nX));
+//   pass p of n is LIVE on the nodes [max(1, x0 - h), min(nX - 1, x1 + h)], h = n - 1 - p  (one node wider at the upper end than
+//     the own range: an X-directed edge at cell c is written by the lines c and c + 1, and the owner of cell c needs both);
+//   a line at node j reads node-type edges at j - 1 .. j + 1 and X-directed edges at the cells j - 1, j, and writes node-type edges
+//     at j and the cells j - 1, j.  INVARIANT: everything the live lines of pass p + 1 read is exact after pass p, because every
+//     line that writes it in pass p is live in pass p (its own inputs exact by the same argument, the copied-in region covering
+//     pass 0).  After the last pass the nodes [x0, x1] and the cells [x0 - 1, x1 - 1] are exact;
+//   owner of index j (a node or a cell): slab (j - 1) / own, index 0 with slab 0, the indices past the last own range with the last
+//     slab: every edge has exactly one owner, and the owner's copy of it is exact;
+//   copied in: the indices [lo(0) - 1, hi(0) + 1] of every component.
+constexpr int SWEEP_FUSE_MAX_PASSES = 16;      // (LineArgs::fseq: four bits per pass; nu = 2: 7 passes, nu = 3: 11, nu = 4: 14)
+#if defined(__HIPCC__)
+#define SWEEP_HD __host__ __device__
+#else
+#define SWEEP_HD
+#endif
+struct FuseGeom { int nX, own, nslabs, npass; };
+SWEEP_HD inline int fuse_x0(const FuseGeom& g, int k) { return 1 + k * g.own; }
+SWEEP_HD inline int fuse_x1(const FuseGeom& g, int k) { const int x = 1 + (k + 1) * g.own; return (k == g.nslabs - 1 || x > g.nX) ? g.nX : x; }
+SWEEP_HD inline int fuse_lo(const FuseGeom& g, int k, int p) { const int v = fuse_x0(g, k) - (g.npass - 1 - p); return v < 1 ? 1 : v; }
+SWEEP_HD inline int fuse_hi(const FuseGeom& g, int k, int p) { const int v = fuse_x1(g, k) + (g.npass - 1 - p); return v > g.nX - 1 ? g.nX - 1 : v; }
+SWEEP_HD inline int fuse_owner(const FuseGeom& g, int j) { const int k = j <= 0 ? 0 : (j - 1) / g.own; return k > g.nslabs - 1 ? g.nslabs - 1 : k; }
+
+struct FusePlan {
+    bool fused = false;
+    int axis = 0;               // slabs along 0: P, 1: Q (the longer one; P on a tie)
+    int nw = 0;                 // waves per workgroup
+    FuseGeom g = {0, 0, 0, 0};
+    i64 scratch_bytes = 0;      // private copies: systems x slabs x edges of the level
+};
+// transverse axes of a line direction (MG::line_args)
+inline void sweep_axes(int dir, int& P, int& Q) { P = dir == 0 ? 1 : 0; Q = dir == 2 ? 1 : 2; }
+inline FusePlan plan_fuse(const SweepKnobs& K, const SweepShape& G, int dir, int npass) {
+    FusePlan f;
+    const SweepPlan p = plan_sweep(K, G, dir);
+    // the scan kernel, one wave per line, descriptors (the fused loop indexes the per-colour tables of MG::ensure_qdesc)
+    if (K.order != 1 || (p.family != SweepFamily::qpl && p.family != SweepFamily::qpl_chain) || p.NW != 1 || p.M != 1 || !p.qdesc) return f;
+    if (p.seg > K.fuse_max_seg || p.seg > 8 || npass < 3 || npass > SWEEP_FUSE_MAX_PASSES) return f;
+#ifndef EMG3D_LAB
+    if (p.family != SweepFamily::qpl_chain) return f;      // (the scan form of the fused loop lost its A/B: lab build only)
+#endif
+    int P, Q;
+    sweep_axes(dir, P, Q);
+    f.axis = G.nC[Q] > G.nC[P] ? 1 : 0;
+    const i64 nX = G.nC[f.axis ? Q : P];
+    if (nX < 2 || nX > (1 << 20)) return f;
+    i64 own = K.fuse_own > 0 ? K.fuse_own : 2;
+    own = std::min<i64>(own, nX - 1);
+    f.g.nX = (int)nX; f.g.own = (int)own; f.g.nslabs = (int)((nX - 1 + own - 1) / own); f.g.npass = npass;
+    f.nw = p.family == SweepFamily::qpl_chain ? 8 : 4;     // (8 waves: a pass of a 4-block slab is one round; 4 at 4 waves per round lost)
+    f.scratch_bytes = (i64)K.nsys * f.g.nslabs * G.edges() * (i64)G.tsize;
+    f.fused = f.scratch_bytes <= K.fuse_max_bytes;
+    return f;
 }

@@ -40,9 +40,19 @@ void qpl_launch(int nw, int m, bool hl, int dm, bool chain, dim3 grid, hipStream
     } else if (m == 2) qpl_launch_m<T, 2>(nw, dm, false, grid, st, a);
     else qpl_launch_m<T, 1>(nw, dm, chain, grid, st, a);
 }
+template <class T>
+void qpl_fused_launch(bool chain, dim3 grid, hipStream_t st, const LineArgs<T>& a) {
+#ifdef EMG3D_LAB
+    // (lab: the scan form too -- 8-block lines, EMG3D_QPL_FUSE=8, which lose; 4 waves: the scans' exchange buffer stays within 64 KB)
+    if (!chain) { hipLaunchKernelGGL((k_line_sweep_qpl<T, 4, 1, false, 2, false, true>), grid, dim3(256), 0, st, a); return; }
+#endif
+    hipLaunchKernelGGL((k_line_sweep_qpl<T, 8, 1, false, 2, true, true>), grid, dim3(512), 0, st, a);
+}
 #if EMG3D_UNIT_T != 1
 template void qpl_launch<double>(int, int, bool, int, bool, dim3, hipStream_t, const LineArgs<double>&);
+template void qpl_fused_launch<double>(bool, dim3, hipStream_t, const LineArgs<double>&);
 #endif
 #if EMG3D_UNIT_T != 0
 template void qpl_launch<c128>(int, int, bool, int, bool, dim3, hipStream_t, const LineArgs<c128>&);
+template void qpl_fused_launch<c128>(bool, dim3, hipStream_t, const LineArgs<c128>&);
 #endif

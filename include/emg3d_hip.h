@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 109
+#define EMG3D_HIP_ABI_VERSION 110
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -118,6 +118,18 @@ int emg3d_restrict_model(int is_complex, int64_t nx, int64_t ny, int64_t nz, voi
  * numbers per block, 3 mirrored two-sided, 4 compact 11 numbers), parity-split working copies (0 / 1), 64-bit field offsets (0 / 1). */
 int emg3d_sweep_plan(int dtype, int64_t nx, int64_t ny, int64_t nz, int dir, int order, int nsys, int cu_count, char* name,
                      int64_t* info);
+
+/* How a smoothing call of npass colour passes along dir is ISSUED on such a level (csrc/sweep_plan.hpp, plan_fuse): one launch per
+ * pass, or -- levels of short lines that the scan kernel serves -- all passes in one launch of that kernel, a workgroup per slab of
+ * line nodes along the longer transverse axis working on a private copy, plus one launch that writes every edge from its owner's copy.
+ * The kernel selection (emg3d_sweep_plan) is the same either way.  own > 0: own line nodes per slab instead of the default;
+ * max_seg > 0: fused up to lines of that many blocks (a power of two) instead of the default (8-block lines: lab build only); budget > 0: bytes the private copies may take instead of the default.  Shape logic only, callable without a GPU when cu_count > 0.
+ * info[8]: fused (0 / 1), slab axis (0, 1, 2 = x, y, z), cells nX along it (lines at the nodes 1 .. nX - 1), own nodes per slab, slabs,
+ * passes, waves per workgroup, bytes of private copies.  ranges (may be NULL; nranges = its capacity, >= slabs * (4 + 2 npass)), per
+ * slab: own nodes [x0, x1), owned edge indices [a, b) along the axis (nodes 0 .. nX and cells 0 .. nX - 1 alike), then per pass the
+ * live nodes lo, hi (inclusive).  Written only when fused.                                                                        */
+int emg3d_sweep_fuse_plan(int dtype, int64_t nx, int64_t ny, int64_t nz, int dir, int order, int nsys, int cu_count, int npass, int own,
+                          int max_seg, int64_t budget, int64_t* info, int64_t* ranges, int64_t nranges);
 
 /* ---- Tier 2: device-resident multigrid handle --------------------------- */
 typedef struct emg3d_mg emg3d_mg_t;
