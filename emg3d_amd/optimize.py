@@ -17,7 +17,14 @@ handles and the forward fields of ALL pairs in HBM and gives ``J v``, ``J^T w`` 
 survey, every solve batched over the sources.  ``model_gradient(...,
 model_grid=)`` maps the gradient to the model grid as the reference does (``maps.grid2grid(grid, -grad, model_grid,
 'cubic')``, optimize.py:201-211) and applies the chain rule there.
+
+What the four entry points share is written once: the argument checks (``_check_arguments``), the receivers (``_receivers``), the
+residual / adjoint source of one system (``_adjoint_source``, the reference's rule included), the flags of a short chunk
+(``_first``) and, for the two Jacobians, ``_JacobianBase``; the per-dtype handles of the survey-level entry points, re-targeted
+from frequency to frequency, are a ``solver.FrequencyHandles`` (``DeviceMG.retarget``).
 """
+import time
+
 import numpy as np
 
 from . import _lib, fields, maps, models, solver
@@ -29,6 +36,62 @@ def misfit(synthetic, observed, weights):
     residual = np.asarray(synthetic) - np.asarray(observed)
     # (the reference sums xarray DataArrays, which skip NaN entries -- receivers outside the grid or missing data)
     return float(np.nansum(weights * (residual.conj() * residual)).real / 2), residual
+
+
+def _check_arguments(who, model, adjoint, electric=True, interpolation=None, krylov=None, count=None):
+    """The argument checks of ``gradient`` / ``survey_gradient`` (``who='Gradient'``: isotropic models) and of the two Jacobians
+    (``who='Jacobian'``: ``interpolation`` of the receivers; magnetic receivers with the exact adjoint only).  ``krylov``: the
+    start of the message that refuses ``sslsolver`` (None: not asked for); ``count = (name, value)``: ``batch`` resp. ``nvec``."""
+    if who == 'Jacobian' and interpolation not in ('linear', 'cubic'):
+        raise ValueError(f"`receiver_interpolation` must be 'linear' or 'cubic'; provided: {interpolation!r}.")
+    if adjoint not in ('reference', 'exact'):
+        raise ValueError(f"`adjoint` must be 'reference' or 'exact'; provided: {adjoint!r}.")
+    if who == 'Jacobian' and not electric and adjoint != 'exact':
+        raise NotImplementedError(f"{who}: magnetic receivers are implemented with adjoint='exact' only (the reference's "
+                                  "rule, loop sources, is not).")
+    if who == 'Gradient' and getattr(model, 'case', 0) != 0:
+        raise NotImplementedError(f"{who} only implemented for isotropic models.")
+    if getattr(model, 'mu_r', None) is not None or getattr(model, 'epsilon_r', None) is not None:
+        raise NotImplementedError(f"{who} not implemented for el. permittivity / magn. permeability.")
+    if krylov:
+        raise NotImplementedError(f"{krylov}; Krylov solvers are not implemented.")
+    if count is not None and (int(count[1]) != count[1] or not 1 <= int(count[1]) <= 64):
+        raise ValueError(f"`{count[0]}` must be an integer from 1 to 64; provided: {count[1]!r}.")
+
+
+def _receivers(rec):
+    """``(n_rec, rec)`` with the five entries of ``rec = (x, y, z, azimuth, dip)`` as float64 arrays broadcast to ``n_rec``."""
+    n = fields._receiver_args(rec)[0]               # (refuses a `rec` of another form)
+    return n, tuple(np.broadcast_to(np.asarray(c, dtype=np.float64), (n,)) for c in rec)
+
+
+def _first(n, nb):
+    """``nb`` int32 flags, the first ``n`` set: the systems of a chunk on a handle that carries ``nb``."""
+    f = np.zeros(nb, dtype=np.int32)
+    f[:n] = 1
+    return f
+
+
+def _adjoint_source(dev, rec, smu0, cw, *, method, exact, electric):
+    """Residual / adjoint source of the selected system of ``dev`` from ``cw = conj(weights * residual)`` (resp. ``conj(w)``; NaN
+    already replaced by 0), one value per receiver.  Returns whether a source was set -- if not, the source is left as it was.
+
+    ``exact`` or ``method='linear'``: ``P^T cw`` with the exact transpose of the receiver operator the data came through (one
+    ``set_receiver_adjoint``).  Otherwise the reference's rule (simulations.py:1181-1197): every receiver with a datum becomes a
+    1 m dipole source of strength ``cw / s mu_0``; magnetic receivers: a loop source, ``/ s mu_0`` once more."""
+    if exact or method == 'linear':
+        if np.any(cw != 0):
+            dev.set_receiver_adjoint(rec, cw, method=method, magnetic=not electric, smu0=smu0)
+            return True
+        return False
+    done = False
+    for k in range(len(cw)):
+        strength = cw[k] / smu0 if electric else cw[k] / smu0 / smu0
+        if strength == 0:
+            continue
+        dev.set_source([c[k] for c in rec], smu0, strength=strength, accumulate=done, electric=electric)
+        done = True
+    return done
 
 
 def gradient(grid, model, src, freq, rec, observed, weights=None, strength=0, device=0, electric=True, adjoint='reference',
@@ -55,12 +118,7 @@ def gradient(grid, model, src, freq, rec, observed, weights=None, strength=0, de
     derivative of the misfit only approximately.  ``adjoint='exact'``: one ``DeviceMG.set_receiver_adjoint(rec, conj(weights *
     residual), method='cubic')`` builds ``P^T conj(W r)`` with the exact transpose of the receiver operator (electric or
     magnetic): ``-grad`` is then the derivative of the misfit to the accuracy of the two solves."""
-    if adjoint not in ('reference', 'exact'):
-        raise ValueError(f"`adjoint` must be 'reference' or 'exact'; provided: {adjoint!r}.")
-    if getattr(model, 'case', 0) != 0:
-        raise NotImplementedError("Gradient only implemented for isotropic models.")
-    if getattr(model, 'mu_r', None) is not None or getattr(model, 'epsilon_r', None) is not None:
-        raise NotImplementedError("Gradient not implemented for el. permittivity / magn. permeability.")
+    _check_arguments('Gradient', model, adjoint)
     observed = np.asarray(observed)
     n = observed.size
     weights = np.ones(n) if weights is None else np.broadcast_to(np.asarray(weights), (n,))
@@ -78,29 +136,11 @@ def gradient(grid, model, src, freq, rec, observed, weights=None, strength=0, de
         phi, residual = misfit(synthetic, observed, weights)
         dev.vec_alloc(1)
         dev.vec_copy(0, dev.EFIELD)                         # keep the forward field
-        # residual source: every receiver becomes a source of strength conj(residual) conj(weight) / s mu_0
-        # (simulations.py:1184-1188); magnetic receivers: / s mu_0 once more, loop sources (1190-1197)
+        # residual source (receivers without a datum, NaN, are skipped)
         rec = [np.broadcast_to(np.asarray(c, dtype=np.float64), (n,)) for c in rec]
-        first = True
-        if adjoint == 'exact':
-            # P^T conj(W r) with the exact transpose of the receiver operator the data came through
-            cw = np.conj(weights * residual)
-            cw = np.where(np.isnan(cw), 0, cw)
-            if np.any(cw != 0):
-                dev.set_receiver_adjoint(rec, cw, method='cubic', magnetic=not electric, smu0=smu0)
-                first = False
-        else:
-            for i in range(n):
-                if np.isnan(residual[i]):
-                    continue
-                st = residual[i].conj() * np.conj(weights[i]) / smu0
-                if not electric:
-                    st = st / smu0
-                if st == 0:
-                    continue
-                dev.set_source([c[i] for c in rec], smu0, strength=st, accumulate=not first, electric=electric)
-                first = False
-        if first:
+        cw = np.conj(weights * residual)
+        if not _adjoint_source(dev, rec, smu0, np.where(np.isnan(cw), 0, cw), method='cubic', exact=adjoint == 'exact',
+                               electric=electric):
             return phi, np.zeros(grid.vnC, order='F'), dict(synthetic=synthetic, forward=finfo, backward=None)
         rfield = fields.SourceField(grid, freq=freq)
         _, binfo = solver.solve(grid, None, rfield, handle=dev, return_info=True, source='resident',
@@ -133,7 +173,7 @@ def survey_gradient(grid, model, sources, freqs, rec, observed, weights=None, st
     ``gradient()``.  Frequencies < 0 are Laplace-domain values and may be mixed with frequencies; their data are real.
 
     One handle per dtype carries ``min(batch, n_src)`` systems and is re-targeted from frequency to frequency
-    (``DeviceMG.set_smu0``).  Per frequency the sources go through in chunks of that size (a shorter last chunk with the surplus
+    (``FrequencyHandles``).  Per frequency the sources go through in chunks of that size (a shorter last chunk with the surplus
     systems frozen): batched forward solve, data per system, ``misfit()`` per pair on the host, the forward fields parked with one
     ``bvec_copy``, the residual source of every system built as ``gradient()`` builds it, batched back-propagation solve, then ONE
     ``grad_acc_add`` adds the chunk's gradients on the device.  A pair without a usable datum gets no adjoint solve (its
@@ -150,28 +190,14 @@ def survey_gradient(grid, model, sources, freqs, rec, observed, weights=None, st
     vnC`` (F-ordered; the unit of exchange of ``shard.gather_survey_gradient``), ``forward[i][j]`` / ``backward[i][j]`` the solver
     info dicts, ``phases`` host seconds spent in the forward solves, the data, the adjoint sources, the backward solves and the
     accumulation."""
-    import time
-    if adjoint not in ('reference', 'exact'):
-        raise ValueError(f"`adjoint` must be 'reference' or 'exact'; provided: {adjoint!r}.")
-    if getattr(model, 'case', 0) != 0:
-        raise NotImplementedError("Gradient only implemented for isotropic models.")
-    if getattr(model, 'mu_r', None) is not None or getattr(model, 'epsilon_r', None) is not None:
-        raise NotImplementedError("Gradient not implemented for el. permittivity / magn. permeability.")
-    if solver_opts.get('sslsolver'):
-        raise NotImplementedError("survey_gradient: resident sources are solved by multigrid only; Krylov solvers are not "
-                                  "implemented.")
-    if int(batch) != batch or not 1 <= int(batch) <= 64:
-        raise ValueError(f"`batch` must be an integer from 1 to 64; provided: {batch!r}.")
-    if len(rec) != 5:
-        raise ValueError("`rec` needs to be in the form (x, y, z, azimuth, dip).\n"
-                         f"Length of provided `rec`: {len(rec)}.")
+    _check_arguments('Gradient', model, adjoint, count=('batch', batch), krylov=solver_opts.get('sslsolver')
+                     and "survey_gradient: resident sources are solved by multigrid only")
+    nrec, rec = _receivers(rec)
     sources = list(sources)
     freqs = [float(f) for f in freqs]
     ns, nf = len(sources), len(freqs)
     if ns < 1:
         raise ValueError("survey_gradient: no sources.")
-    nrec = max(np.atleast_1d(c).size for c in rec)
-    rec = tuple(np.broadcast_to(np.asarray(c, dtype=np.float64), (nrec,)) for c in rec)
     observed = np.asarray(observed)
     if observed.shape != (ns, nf, nrec):
         raise ValueError(f"`observed` must have shape (n_src, n_freq, n_rec) = {(ns, nf, nrec)}; provided: {observed.shape}.")
@@ -198,21 +224,10 @@ def survey_gradient(grid, model, sources, freqs, rec, observed, weights=None, st
         return t1
 
     parts = models.model_parts(grid, model, raw=True)
-    handles = {}
-    try:
+    with solver.FrequencyHandles(grid, parts, device, nsys=nb, bvecs=1) as handles:
         for j, spec in enumerate(specs):
             smu0 = spec.smu0
-            key = spec.dtype.str
-            dev = handles.get(key)
-            if dev is None:
-                dev = handles[key] = solver.DeviceMG.from_model_parts(grid, *parts, smu0=smu0, device=device)
-                if nb > 1:
-                    dev.set_batch(nb)
-                dev.bvec_alloc(1)
-                dev._smu0 = smu0
-            elif dev._smu0 != smu0:
-                dev.set_smu0(smu0, sval=spec.sval)
-                dev._smu0 = smu0
+            dev = handles.target(spec)
             real = spec.dtype.kind != 'c'
             dev.grad_acc_reset()
             for i0 in range(0, ns, nb):
@@ -236,37 +251,18 @@ def survey_gradient(grid, model, sources, freqs, rec, observed, weights=None, st
                     residuals.append(r)
                 t = lap('data', t)
                 # 4. park the forward fields of the chunk (the solve has left all but the last system to finish frozen)
-                mask = np.zeros(nb, dtype=np.int32)
-                mask[:n] = 1
-                dev.set_mask(mask)
+                dev.set_mask(_first(n, nb))
                 dev.bvec_copy(0, dev.EFIELD)
                 # 5. residual sources, per system exactly as gradient() builds them
-                use = np.zeros(nb, dtype=np.int32)
+                use = _first(0, nb)
                 for b in range(n):
                     dev.select(b)
-                    w, r = weights[i0 + b, j], residuals[b]
-                    first = True
-                    if adjoint == 'exact':
-                        cw = np.conj(w * r)
-                        cw = np.where(np.isnan(cw), 0, cw)
-                        if np.any(cw != 0):
-                            dev.set_receiver_adjoint(rec, cw, method='cubic', magnetic=not electric, smu0=smu0)
-                            first = False
-                    else:
-                        for k in range(nrec):
-                            if np.isnan(r[k]):
-                                continue
-                            st = r[k].conj() * np.conj(w[k]) / smu0
-                            if not electric:
-                                st = st / smu0
-                            if st == 0:
-                                continue
-                            dev.set_source([c[k] for c in rec], smu0, strength=st, accumulate=not first, electric=electric)
-                            first = False
-                    if first:
-                        dev.vec_scale(dev.SFIELD, 0.0)          # no usable datum: a zero source, frozen by the solve
-                    else:
+                    cw = np.conj(weights[i0 + b, j] * residuals[b])
+                    if _adjoint_source(dev, rec, smu0, np.where(np.isnan(cw), 0, cw), method='cubic', exact=adjoint == 'exact',
+                                       electric=electric):
                         use[b] = 1
+                    else:
+                        dev.vec_scale(dev.SFIELD, 0.0)          # no usable datum: a zero source, frozen by the solve
                 t = lap('adjoint_sources', t)
                 if not use.any():
                     continue
@@ -282,9 +278,6 @@ def survey_gradient(grid, model, sources, freqs, rec, observed, weights=None, st
             t = time.perf_counter()
             partial[j] = dev.grad_acc_get().reshape(vnC, order='F')
             lap('accumulate', t)
-    finally:
-        for dev in handles.values():
-            dev.close()
     phi, grad = _sum_survey(partial, misfits, vnC)
     return phi, grad, dict(synthetic=synthetic, misfit=misfits, partial=partial, forward=finfo, backward=binfo, phases=phases)
 
@@ -349,7 +342,34 @@ def _perturbations(v, vnC):
     return out, single
 
 
-class Jacobian:
+class _JacobianBase:
+    """What ``Jacobian`` and ``SurveyJacobian`` share: the ``with`` protocol, the test for the open state (``self._held``: the
+    handle resp. the handles, None when closed) and the two steps every product is made of."""
+
+    def __enter__(self):
+        return self.open()
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _require_open(self):
+        if self._held is None:
+            raise RuntimeError(self._closed)
+        return self._held
+
+    def _solve(self, dev, freq, n):
+        """Solve the systems 0 .. n-1 of the handle (at ``freq``) for the sources they hold; the fields stay in HBM."""
+        _, infos = solver.solve_sources(self.grid, None, None, freq, handle=dev, resident=n, download=False, **self._opts)
+        return infos
+
+    def _data(self, dev, smu0):
+        """Receiver responses of the selected system's field."""
+        if self.electric:
+            return dev.get_receiver_response(self.rec, method=self.receiver_interpolation)
+        return dev.get_receiver_response(self.rec, magnetic=True, smu0=smu0, method=self.receiver_interpolation)
+
+
+class Jacobian(_JacobianBase):
     """Products with the sensitivity matrix ``J = d(data) / d(conductivity)`` of ONE (source, frequency) pair on its
     computational grid, on one device handle::
 
@@ -391,39 +411,24 @@ class Jacobian:
 
     def __init__(self, grid, model, src, freq, rec, receiver_interpolation='linear', nvec=1, strength=0, device=0,
                  electric=True, adjoint='reference', **solver_opts):
-        if receiver_interpolation not in ('linear', 'cubic'):
-            raise ValueError(f"`receiver_interpolation` must be 'linear' or 'cubic'; provided: {receiver_interpolation!r}.")
-        if adjoint not in ('reference', 'exact'):
-            raise ValueError(f"`adjoint` must be 'reference' or 'exact'; provided: {adjoint!r}.")
-        if not electric and adjoint != 'exact':
-            raise NotImplementedError("Jacobian: magnetic receivers are implemented with adjoint='exact' only (the reference's "
-                                      "rule, loop sources, is not).")
-        if getattr(model, 'mu_r', None) is not None or getattr(model, 'epsilon_r', None) is not None:
-            raise NotImplementedError("Jacobian not implemented for el. permittivity / magn. permeability.")
-        if int(nvec) != nvec or not 1 <= int(nvec) <= 64:
-            raise ValueError(f"`nvec` must be an integer from 1 to 64; provided: {nvec!r}.")
-        if len(rec) != 5:
-            raise ValueError("`rec` needs to be in the form (x, y, z, azimuth, dip).\n"
-                             f"Length of provided `rec`: {len(rec)}.")
-        if solver_opts.get('sslsolver'):
-            raise NotImplementedError("Jacobian: the products are multigrid solves; Krylov solvers are not implemented.")
+        _check_arguments('Jacobian', model, adjoint, electric, receiver_interpolation, count=('nvec', nvec),
+                         krylov=solver_opts.get('sslsolver') and "Jacobian: the products are multigrid solves")
         self.grid, self.model, self.src, self.freq = grid, model, src, freq
-        self.n_rec = max(np.atleast_1d(c).size for c in rec)
-        self.rec = tuple(np.broadcast_to(np.asarray(c, dtype=np.float64), (self.n_rec,)) for c in rec)
+        self.n_rec, self.rec = _receivers(rec)
         self.receiver_interpolation = receiver_interpolation
         self.adjoint, self.electric = adjoint, bool(electric)
         self.nvec, self.strength, self.device = int(nvec), strength, device
         self._opts = {k: v for k, v in solver_opts.items() if k not in ('return_info', 'sslsolver')}
         self._spec = fields.FrequencySpec(freq)
         self._vnC = tuple(int(n) for n in grid.vnC)
-        self._dev = None
+        self._held = None
         self.synthetic = self.forward_info = self.info = None
 
     # ---- handle -------------------------------------------------------------------------------------------------------
     def open(self):
         """Create the handle, run the forward solve (system 0; the other systems of a batch frozen), extract the data and
         park the forward field."""
-        if self._dev is not None:
+        if self._held is not None:
             return self
         smu0 = self._spec.smu0
         parts = models.model_parts(self.grid, self.model, raw=True)
@@ -433,43 +438,23 @@ class Jacobian:
                 dev.set_batch(self.nvec)
             dev.select(0)
             dev.set_source(self.src, smu0, strength=self.strength)
-            self.forward_info = self._solve(dev, 1)[0]
+            self.forward_info = self._solve(dev, self.freq, 1)[0]
             dev.select(0)
-            self.synthetic = self._data(dev)
+            self.synthetic = self._data(dev, smu0)
             dev.vec_alloc(1)
             dev.vec_copy(0, dev.EFIELD)                     # keep the forward field
         except BaseException:
             dev.close()
             raise
-        self._dev = dev
+        self._held = dev
         return self
 
     def close(self):
-        if self._dev is not None:
-            self._dev.close()
-            self._dev = None
+        if self._held is not None:
+            self._held.close()
+            self._held = None
 
-    def __enter__(self):
-        return self.open()
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _solve(self, dev, n):
-        """Solve the systems 0 .. n-1 of the handle for the sources they hold; the fields stay in HBM."""
-        _, infos = solver.solve_sources(self.grid, None, None, self.freq, handle=dev, resident=n, download=False, **self._opts)
-        return infos
-
-    def _data(self, dev):
-        """Receiver responses of the selected system's field."""
-        if self.electric:
-            return dev.get_receiver_response(self.rec, method=self.receiver_interpolation)
-        return dev.get_receiver_response(self.rec, magnetic=True, smu0=self._spec.smu0, method=self.receiver_interpolation)
-
-    def _require_open(self):
-        if self._dev is None:
-            raise RuntimeError("Jacobian: the handle is closed (use it inside its `with` block, or call open()).")
-        return self._dev
+    _closed = "Jacobian: the handle is closed (use it inside its `with` block, or call open())."
 
     # ---- J v ----------------------------------------------------------------------------------------------------------
     def jvec(self, v):
@@ -484,10 +469,10 @@ class Jacobian:
             for b, (vx, vy, vz) in enumerate(group):
                 dev.select(b)
                 dev.jvec_source(0, smu0, vx, vy, vz)
-            infos += self._solve(dev, len(group))
+            infos += self._solve(dev, self.freq, len(group))
             for b in range(len(group)):
                 dev.select(b)
-                out[g0 + b] = self._data(dev)
+                out[g0 + b] = self._data(dev, smu0)
         self.info = infos[0] if single else infos
         return out[0] if single else out
 
@@ -502,22 +487,9 @@ class Jacobian:
         return np.atleast_2d(w).astype(self._spec.dtype), w.ndim == 1
 
     def _adjoint_source(self, dev, w):
-        """Source of the selected system for ``jtvec``."""
-        smu0 = self._spec.smu0
-        cw = np.where(np.isnan(w), 0, np.conj(w))           # NaN data (receivers outside, missing data) are skipped
-        if self.receiver_interpolation == 'linear' or self.adjoint == 'exact':
-            # exact transpose of the receiver operator (linear or cubic, on E or on H = C E)
-            dev.set_receiver_adjoint(self.rec, cw, method=self.receiver_interpolation, magnetic=not self.electric, smu0=smu0)
-            return
-        # 'cubic': the reference's rule, every receiver a 1 m dipole source of strength conj(w) / s mu_0
-        # (simulations.py:1171-1213), as gradient() does
-        first = True
-        for i in range(self.n_rec):
-            if cw[i] == 0:
-                continue
-            dev.set_source([c[i] for c in self.rec], smu0, strength=cw[i] / smu0, accumulate=not first)
-            first = False
-        if first:
+        """Source of the selected system for ``jtvec``: NaN data (receivers outside, missing data) are skipped."""
+        if not _adjoint_source(dev, self.rec, self._spec.smu0, np.where(np.isnan(w), 0, np.conj(w)),
+                               method=self.receiver_interpolation, exact=self.adjoint == 'exact', electric=self.electric):
             dev.vec_scale(dev.SFIELD, 0.0)
 
     def jtvec(self, w, components=False):
@@ -541,7 +513,7 @@ class Jacobian:
             for b, wv in enumerate(group):
                 dev.select(b)
                 self._adjoint_source(dev, wv)
-            infos += self._solve(dev, len(group))
+            infos += self._solve(dev, self.freq, len(group))
             for b in range(len(group)):
                 dev.select(b)
                 if components:
@@ -556,7 +528,7 @@ class Jacobian:
         return np.stack(outs)
 
 
-class SurveyJacobian:
+class SurveyJacobian(_JacobianBase):
     """Products with the sensitivity matrix of a SURVEY -- every source of ``sources`` at every entry of ``freqs`` (values < 0 are
     Laplace-domain, and may be mixed with frequencies) -- on the computational grid: the rows of ``Jacobian(src_i, freq_j)`` for all
     pairs ``(i, j)`` stacked, without a handle, a hierarchy, a forward solve and an ``nC``-sized download per pair::
@@ -569,7 +541,7 @@ class SurveyJacobian:
             sj.partial                        # the last jtvec's per-frequency sums G_f
 
     One handle per dtype carries ``min(batch, n_src)`` systems and is re-targeted from entry to entry of ``freqs``
-    (``DeviceMG.set_smu0``), as in ``survey_gradient``.  ``open()`` solves all pairs forward, the sources in chunks of that size
+    (``FrequencyHandles``), as in ``survey_gradient``.  ``open()`` solves all pairs forward, the sources in chunks of that size
     (built in HBM), extracts the data and parks the forward fields of every (frequency, chunk) in a batched vector of its own:
     ``n_freq * n_chunks * min(batch, n_src) * nE`` field values stay in HBM (sized and allocated before the first solve; a
     workspace that does not fit raises ``HipLibraryError`` with the bytes needed and free) and never cross PCIe.
@@ -601,30 +573,15 @@ class SurveyJacobian:
 
     def __init__(self, grid, model, sources, freqs, rec, batch=8, receiver_interpolation='cubic', adjoint='exact', electric=True,
                  strength=0, device=0, **solver_opts):
-        if receiver_interpolation not in ('linear', 'cubic'):
-            raise ValueError(f"`receiver_interpolation` must be 'linear' or 'cubic'; provided: {receiver_interpolation!r}.")
-        if adjoint not in ('reference', 'exact'):
-            raise ValueError(f"`adjoint` must be 'reference' or 'exact'; provided: {adjoint!r}.")
-        if not electric and adjoint != 'exact':
-            raise NotImplementedError("Jacobian: magnetic receivers are implemented with adjoint='exact' only (the reference's "
-                                      "rule, loop sources, is not).")
-        if getattr(model, 'mu_r', None) is not None or getattr(model, 'epsilon_r', None) is not None:
-            raise NotImplementedError("Jacobian not implemented for el. permittivity / magn. permeability.")
-        if int(batch) != batch or not 1 <= int(batch) <= 64:
-            raise ValueError(f"`batch` must be an integer from 1 to 64; provided: {batch!r}.")
-        if len(rec) != 5:
-            raise ValueError("`rec` needs to be in the form (x, y, z, azimuth, dip).\n"
-                             f"Length of provided `rec`: {len(rec)}.")
-        if solver_opts.get('sslsolver'):
-            raise NotImplementedError("SurveyJacobian: the products are multigrid solves; Krylov solvers are not implemented.")
+        _check_arguments('Jacobian', model, adjoint, electric, receiver_interpolation, count=('batch', batch),
+                         krylov=solver_opts.get('sslsolver') and "SurveyJacobian: the products are multigrid solves")
         self.sources = list(sources)
         self.freqs = [float(f) for f in np.atleast_1d(freqs)]
         if len(self.sources) < 1 or len(self.freqs) < 1:
             raise ValueError("SurveyJacobian: no sources or no frequencies.")
         self.grid, self.model = grid, model
         self.n_src, self.n_freq = len(self.sources), len(self.freqs)
-        self.n_rec = max(np.atleast_1d(c).size for c in rec)
-        self.rec = tuple(np.broadcast_to(np.asarray(c, dtype=np.float64), (self.n_rec,)) for c in rec)
+        self.n_rec, self.rec = _receivers(rec)
         self.receiver_interpolation = receiver_interpolation
         self.adjoint, self.electric = adjoint, bool(electric)
         self.batch, self.strength, self.device = int(batch), strength, device
@@ -635,105 +592,68 @@ class SurveyJacobian:
         self._chunks = [(i0, min(self._nb, self.n_src - i0)) for i0 in range(0, self.n_src, self._nb)]
         cplx = any(sp.dtype.kind == 'c' for sp in self._specs)
         self.dtype = np.dtype(np.complex128 if cplx else np.float64)
-        self._handles = None
+        self._held = None
         self.synthetic = self.forward_info = self.info = self.jvec_info = self.partial = None
 
     # ---- handles ------------------------------------------------------------------------------------------------------
     def open(self):
         """Create the handles, size and allocate the parked fields, solve all pairs forward (chunk by chunk), extract the data."""
-        if self._handles is not None:
+        if self._held is not None:
             return self
         ns, nf, nb = self.n_src, self.n_freq, self._nb
         parts = models.model_parts(self.grid, self.model, raw=True)
-        handles, self._slot, nslots = {}, {}, {}
+        handles = solver.FrequencyHandles(self.grid, parts, self.device, nsys=nb)
+        self._slot, first, nslots = {}, {}, {}
+        for j, spec in enumerate(self._specs):
+            key = spec.dtype.str
+            first.setdefault(key, spec)
+            self._slot[j] = nslots.get(key, 0)              # first batched vector of frequency j on its handle
+            nslots[key] = self._slot[j] + len(self._chunks)
         try:
-            for j, spec in enumerate(self._specs):
-                key = spec.dtype.str
-                if key not in handles:
-                    dev = handles[key] = solver.DeviceMG.from_model_parts(self.grid, *parts, smu0=spec.smu0, device=self.device)
-                    if nb > 1:
-                        dev.set_batch(nb)
-                    dev._smu0 = spec.smu0
-                    nslots[key] = 0
-                self._slot[j] = nslots[key]                     # first batched vector of frequency j on its handle
-                nslots[key] += len(self._chunks)
+            devs = {key: handles.target(spec) for key, spec in first.items()}
             # the parked forward fields: one batched vector per (frequency, chunk), sized and allocated before the first solve
-            need = sum(nslots[key] * nb * dev.nE * dev.dtype.itemsize for key, dev in handles.items())
+            need = sum(nslots[key] * nb * dev.nE * dev.dtype.itemsize for key, dev in devs.items())
             mi = _lib.mem_info(self.device)
             free = mi['free'] + mi['pooled_on_device']
             if need >= 0.92 * free:
                 raise _lib.HipLibraryError(
                     f"SurveyJacobian: the forward fields of {ns} sources x {nf} frequencies need {need} bytes of device memory, "
                     f"{free} bytes are free; use fewer sources or frequencies per SurveyJacobian (frequency shards).")
-            for key, dev in handles.items():
+            for key, dev in devs.items():
                 dev.bvec_alloc(nslots[key])
             self.synthetic = np.full((ns, nf, self.n_rec), np.nan, dtype=self.dtype)
             self.forward_info = [[None] * nf for _ in range(ns)]
-            for j in range(nf):
-                dev, smu0 = self._target(handles, j)
+            for j, spec in enumerate(self._specs):
+                dev, smu0 = handles.target(spec), spec.smu0
                 for c, (i0, n) in enumerate(self._chunks):
                     for b in range(n):
                         dev.select(b)
                         dev.set_source(self.sources[i0 + b], smu0, strength=self.strength)
-                    infos = self._solve(dev, j, n)
+                    infos = self._solve(dev, self.freqs[j], n)
                     for b in range(n):
                         self.forward_info[i0 + b][j] = infos[b]
                         dev.select(b)
                         self.synthetic[i0 + b, j] = self._data(dev, smu0)
                     # park the chunk's forward fields (the solve has left all but the last system to finish frozen)
-                    dev.set_mask(self._flags(n))
+                    dev.set_mask(_first(n, nb))
                     dev.bvec_copy(self._slot[j] + c, dev.EFIELD)
         except BaseException:
-            for dev in handles.values():
-                dev.close()
+            handles.close()
             raise
-        self._handles = handles
+        self._held = handles
         return self
 
     def close(self):
-        if self._handles is not None:
-            for dev in self._handles.values():
-                dev.close()
-            self._handles = None
+        if self._held is not None:
+            self._held.close()
+            self._held = None
 
-    def __enter__(self):
-        return self.open()
-
-    def __exit__(self, *exc):
-        self.close()
+    _closed = "SurveyJacobian: the handles are closed (use it inside its `with` block, or call open())."
 
     @property
     def device_bytes(self):
         """Device memory of the handles, parked forward fields and accumulators included."""
-        return sum(dev.device_bytes for dev in self._require_open().values())
-
-    def _require_open(self):
-        if self._handles is None:
-            raise RuntimeError("SurveyJacobian: the handles are closed (use it inside its `with` block, or call open()).")
-        return self._handles
-
-    def _target(self, handles, j):
-        """The handle of frequency j, re-targeted to it if need be, and its s mu_0."""
-        spec = self._specs[j]
-        dev = handles[spec.dtype.str]
-        if dev._smu0 != spec.smu0:
-            dev.set_smu0(spec.smu0, sval=spec.sval)
-            dev._smu0 = spec.smu0
-        return dev, spec.smu0
-
-    def _flags(self, n):
-        f = np.zeros(self._nb, dtype=np.int32)
-        f[:n] = 1
-        return f
-
-    def _solve(self, dev, j, n):
-        _, infos = solver.solve_sources(self.grid, None, None, self.freqs[j], handle=dev, resident=n, download=False, **self._opts)
-        return infos
-
-    def _data(self, dev, smu0):
-        if self.electric:
-            return dev.get_receiver_response(self.rec, method=self.receiver_interpolation)
-        return dev.get_receiver_response(self.rec, magnetic=True, smu0=smu0, method=self.receiver_interpolation)
+        return sum(dev.device_bytes for dev in self._require_open())
 
     # ---- arguments ----------------------------------------------------------------------------------------------------
     def _perturbation(self, v):
@@ -770,19 +690,13 @@ class SurveyJacobian:
         if self.receiver_interpolation == 'linear' or self.adjoint == 'exact':
             rows = np.zeros((self._nb, self.n_rec), dtype=dev.dtype)
             rows[:n] = cw
-            dev.set_receiver_adjoint_b(self.rec, rows, self._flags(n), method=self.receiver_interpolation,
+            dev.set_receiver_adjoint_b(self.rec, rows, _first(n, self._nb), method=self.receiver_interpolation,
                                        magnetic=not self.electric, smu0=smu0)
             return
         # 'cubic' receivers with the reference's rule: per system as Jacobian builds it
         for b in range(n):
             dev.select(b)
-            first = True
-            for k in range(self.n_rec):
-                if cw[b, k] == 0:
-                    continue
-                dev.set_source([c[k] for c in self.rec], smu0, strength=cw[b, k] / smu0, accumulate=not first)
-                first = False
-            if first:
+            if not _adjoint_source(dev, self.rec, smu0, cw[b], method='cubic', exact=False, electric=self.electric):
                 dev.vec_scale(dev.SFIELD, 0.0)
 
     def _sweep(self, vec, w, weights, components):
@@ -796,16 +710,16 @@ class SurveyJacobian:
         binfo = [[None] * nf for _ in range(ns)]
         nacc = 3 if components else 1
         partial = np.zeros((nacc, nf) + self._vnC[::-1]).transpose(0, 1, 4, 3, 2) if adj else None     # every G_f F-ordered
-        for j in range(nf):
-            dev, smu0 = self._target(handles, j)
+        for j, spec in enumerate(self._specs):
+            dev, smu0 = handles.target(spec), spec.smu0
             real = dev.dtype.kind != 'c'
             if adj:
                 dev.grad_acc3_reset() if components else dev.grad_acc_reset()
             for c, (i0, n) in enumerate(self._chunks):
                 slot = self._slot[j] + c
                 if vec is not None:
-                    dev.jvec_source_b(slot, smu0, *vec, self._flags(n))
-                    infos = self._solve(dev, j, n)
+                    dev.jvec_source_b(slot, smu0, *vec, _first(n, nb))
+                    infos = self._solve(dev, self.freqs[j], n)
                     for b in range(n):
                         jinfo[i0 + b][j] = infos[b]
                         dev.select(b)
@@ -820,8 +734,8 @@ class SurveyJacobian:
                 if not live.any():
                     continue
                 self._adjoint_sources(dev, smu0, cw, n)
-                infos = self._solve(dev, j, n)
-                use = np.zeros(nb, dtype=np.int32)
+                infos = self._solve(dev, self.freqs[j], n)
+                use = _first(0, nb)
                 use[:n] = live
                 for b in range(n):
                     if live[b]:

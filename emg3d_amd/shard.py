@@ -47,20 +47,12 @@ def solve_frequencies(grid, model, src, freqs, device=0, strength=0, concurrent=
         # device, scaled by this frequency's s mu_0): no nE-sized array is formed or uploaded on the host
         # (with a Krylov solver the host object carries the right-hand side; otherwise only the frequency)
         sfield = fields.SourceField(grid, freq=f) if solver_opts.get('sslsolver') else fields.FrequencySpec(f)
-        # frequencies solved one after the other share ONE handle per dtype: only eta and what is derived from it
-        # (coarse models, line factorisations) is recomputed (DeviceMG.set_smu0) -- the results are those of a fresh
-        # handle bit for bit; hierarchy, buffers and launch graphs are not rebuilt (15-20 ms per frequency at 128^3)
-        key = np.dtype(sfield.dtype).str
-        dev = handles.get(key) if handles is not None and parts is not None else None
-        if dev is None:
-            if parts is not None:
-                dev = solver.DeviceMG.from_model(grid, parts, sfield, device=device)
-            else:
-                dev = solver.DeviceMG(grid, models.VolumeModel(grid, model, sfield), sfield.dtype, device=device)
-            if handles is not None and parts is not None:
-                handles[key] = dev
+        if handles is not None:
+            dev = handles.target(sfield)
+        elif parts is not None:
+            dev = solver.DeviceMG.from_model(grid, parts, sfield, device=device)
         else:
-            dev.set_smu0(sfield.smu0, sval=sfield.sval)
+            dev = solver.DeviceMG(grid, models.VolumeModel(grid, model, sfield), sfield.dtype, device=device)
         try:
             # receivers only (multigrid path): the solution stays in HBM -- no nE-sized download that would be thrown away
             keep = not (rec is not None and not return_field and not solver_opts.get('sslsolver'))
@@ -74,19 +66,20 @@ def solve_frequencies(grid, model, src, freqs, device=0, strength=0, concurrent=
                 resp = dev.get_receiver_response(rec)
             return (e if return_field else None), info, resp
         finally:
-            if handles is None or parts is None:
+            if handles is None:
                 dev.close()
 
-    if int(concurrent) <= 1 or len(freqs) == 1:
-        handles = {}
-        try:
-            return [one(f, handles) for f in freqs]
-        finally:
-            for dev in handles.values():
-                dev.close()
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=min(int(concurrent), len(freqs))) as pool:
-        return list(pool.map(one, freqs))
+    if int(concurrent) > 1 and len(freqs) > 1:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=min(int(concurrent), len(freqs))) as pool:
+            return list(pool.map(one, freqs))
+    if parts is None:
+        return [one(f) for f in freqs]
+    # frequencies solved one after the other share ONE handle per dtype: only eta and what is derived from it
+    # (coarse models, line factorisations) is recomputed (DeviceMG.retarget) -- the results are those of a fresh
+    # handle bit for bit; hierarchy, buffers and launch graphs are not rebuilt (15-20 ms per frequency at 128^3)
+    with solver.FrequencyHandles(grid, parts, device) as handles:
+        return [one(f, handles) for f in freqs]
 
 
 def solve_survey(grid, model, sources, freqs, rec, device=0, strength=0, batch=8, return_fields=False, **solver_opts):
@@ -107,27 +100,17 @@ def solve_survey(grid, model, sources, freqs, rec, device=0, strength=0, batch=8
     resp = None
     infos = [[None] * nf for _ in range(ns)]
     efs = [[None] * nf for _ in range(ns)] if return_fields else None
-    # one handle per (dtype, systems per launch), re-targeted from frequency to frequency (DeviceMG.set_smu0: eta, coarse
+    # one handle per (dtype, systems per launch), re-targeted from frequency to frequency (DeviceMG.retarget: eta, coarse
     # models and line factorisations are recomputed in HBM, hierarchy / buffers / launch graphs stay); bit for bit the
     # results of solver.solve_sources with a handle of its own
     from emg3d_amd import fields, models
     parts = models.model_parts(grid, model, raw=True)
-    handles = {}
-    try:
+    with solver.FrequencyHandles(grid, parts, device) as handles:
         for jf, f in enumerate(freqs):
             spec = fields.FrequencySpec(f)
             for i0 in range(0, ns, int(batch)):
                 chunk = list(sources[i0:i0 + int(batch)])
-                dev = None
-                if parts is not None:
-                    key = (np.dtype(spec.dtype).str, len(chunk))
-                    dev = handles.get(key)
-                    if dev is None:
-                        dev = handles[key] = solver.DeviceMG.from_model(grid, parts, spec, device=device)
-                        dev._smu0 = spec.smu0
-                    elif dev._smu0 != spec.smu0:
-                        dev.set_smu0(spec.smu0, sval=spec.sval)
-                        dev._smu0 = spec.smu0
+                dev = handles.target(spec, key=(len(chunk),))
                 e, info, r = solver.solve_sources(grid, model, chunk, f, strength=strength, rec=rec, device=device,
                                                   download=return_fields, handle=dev, **solver_opts)
                 if resp is None:
@@ -139,9 +122,6 @@ def solve_survey(grid, model, sources, freqs, rec, device=0, strength=0, batch=8
                     infos[i0 + k][jf] = info[k]
                     if return_fields:
                         efs[i0 + k][jf] = e[k]
-    finally:
-        for dev in handles.values():
-            dev.close()
     if resp is None:            # this rank owns no frequency
         resp = np.zeros((ns, 0, int(max(np.size(c) for c in rec[:3]))))
     return (resp, infos, efs) if return_fields else (resp, infos)

@@ -30,7 +30,7 @@ import scipy.sparse.linalg as ssl
 from emg3d_amd import _lib, core, fields, meshes, models
 
 __all__ = ['solve', 'multigrid', 'krylov', 'smoothing', 'restriction', 'prolongation',
-           'residual', 'MGParameters', 'DeviceMG']
+           'residual', 'MGParameters', 'DeviceMG', 'FrequencyHandles']
 
 ORDERINGS = {'lex': 0, 'colour': 1, 'color': 1}
 
@@ -38,51 +38,49 @@ ORDERINGS = {'lex': 0, 'colour': 1, 'color': 1}
 # --------------------------------------------------------------------------
 # Device handle
 # --------------------------------------------------------------------------
+def _cells(a, dtype=np.float64):
+    """A cell array as the C ABI takes it: F-raveled, contiguous."""
+    return np.ascontiguousarray(np.asarray(a, dtype=dtype).ravel(order='F'))
+
+
 class DeviceMG:
     """Device-resident multigrid state (C-ABI tier 2, ``emg3d_mg_*``)."""
 
     def __init__(self, grid, vmodel, dtype, device=0):
+        hx, hy, hz, origin = self._begin(grid, dtype, device)
+        etx = _cells(vmodel.eta_x, self.dtype)
+        ety = etx if vmodel.eta_y is vmodel.eta_x else _cells(vmodel.eta_y, self.dtype)
+        etz = etx if vmodel.eta_z is vmodel.eta_x else _cells(vmodel.eta_z, self.dtype)
+        zeta = _cells(vmodel.zeta)
+        handle = ctypes.c_void_p()
+        _lib.check(self._lib.emg3d_mg_create(
+            ctypes.byref(handle), _lib.dtype_code(self.dtype), *(int(n) for n in grid.vnC), _lib.ptr(hx), _lib.ptr(hy),
+            _lib.ptr(hz), _lib.ptr(origin), _lib.ptr(etx), _lib.ptr(ety), _lib.ptr(etz),
+            _lib.ptr(zeta), int(device)), "emg3d_mg_create")
+        self._h = handle
+
+    def _begin(self, grid, dtype, device, smu0=None, sval=None):
+        """What the three constructors share: library, dtype, sizes, device and the frequency the handle stands at (``smu0``,
+        ``sval``; None for a handle made from a given eta).  Returns the contiguous ``hx, hy, hz, origin``."""
         self._lib = _lib.load()
         self.dtype = np.dtype(dtype)
         self.nE = int(grid.nE)
         self.nC = int(grid.nC)
         self.device = int(device)
-        code = _lib.dtype_code(self.dtype)
+        self._smu0, self._sval, self._eps = smu0, sval, False
         hx, hy, hz = (np.ascontiguousarray(h, dtype=np.float64) for h in grid.h)
-        origin = np.ascontiguousarray(grid.origin, dtype=np.float64)
-
-        def cells(a, dt):
-            return np.ascontiguousarray(np.asarray(a, dtype=dt).ravel(order='F'))
-        etx = cells(vmodel.eta_x, self.dtype)
-        ety = etx if vmodel.eta_y is vmodel.eta_x else cells(vmodel.eta_y, self.dtype)
-        etz = etx if vmodel.eta_z is vmodel.eta_x else cells(vmodel.eta_z, self.dtype)
-        zeta = cells(vmodel.zeta, np.float64)
-        handle = ctypes.c_void_p()
-        _lib.check(self._lib.emg3d_mg_create(
-            ctypes.byref(handle), code, *(int(n) for n in grid.vnC), _lib.ptr(hx), _lib.ptr(hy),
-            _lib.ptr(hz), _lib.ptr(origin), _lib.ptr(etx), _lib.ptr(ety), _lib.ptr(etz),
-            _lib.ptr(zeta), int(device)), "emg3d_mg_create")
-        self._h = handle
+        return hx, hy, hz, np.ascontiguousarray(grid.origin, dtype=np.float64)
 
     @classmethod
     def from_sigma_volume(cls, grid, sv_x, sv_y, sv_z, zeta, smu0, device=0):
         """Handle from the frequency-independent model (``models.sigma_volume``) and the scalar
         ``smu0 = s*mu_0``: ``eta = smu0 * sv`` is formed on the device (``emg3d_mg_create_sv``)."""
         self = cls.__new__(cls)
-        self._lib = _lib.load()
-        self.dtype = np.dtype(np.complex128 if np.iscomplexobj(smu0) else np.float64)
-        self.nE = int(grid.nE)
-        self.nC = int(grid.nC)
-        self.device = int(device)
-        hx, hy, hz = (np.ascontiguousarray(h, dtype=np.float64) for h in grid.h)
-        origin = np.ascontiguousarray(grid.origin, dtype=np.float64)
-
-        def cells(a):
-            return np.ascontiguousarray(np.asarray(a, dtype=np.float64).ravel(order='F'))
-        svx = cells(sv_x)
-        svy = svx if sv_y is sv_x else cells(sv_y)
-        svz = svx if sv_z is sv_x else cells(sv_z)
-        zt = cells(zeta)
+        hx, hy, hz, origin = self._begin(grid, np.complex128 if np.iscomplexobj(smu0) else np.float64, device, smu0)
+        svx = _cells(sv_x)
+        svy = svx if sv_y is sv_x else _cells(sv_y)
+        svz = svx if sv_z is sv_x else _cells(sv_z)
+        zt = _cells(zeta)
         handle = ctypes.c_void_p()
         a = complex(smu0)
         _lib.check(self._lib.emg3d_mg_create_sv(
@@ -105,25 +103,16 @@ class DeviceMG:
         if epsilon_r is not None and sval is None:
             raise TypeError("from_model_parts: epsilon_r needs sval (s = 2 i pi f resp. the Laplace parameter).")
         self = cls.__new__(cls)
-        self._lib = _lib.load()
-        self.dtype = np.dtype(np.complex128 if np.iscomplexobj(smu0) else np.float64)
-        self.nE = int(grid.nE)
-        self.nC = int(grid.nC)
-        self.device = int(device)
-        hx, hy, hz = (np.ascontiguousarray(h, dtype=np.float64) for h in grid.h)
-        origin = np.ascontiguousarray(grid.origin, dtype=np.float64)
-
-        def cells(a):
-            return np.ascontiguousarray(np.asarray(a, dtype=np.float64).ravel(order='F'))
-        sx = cells(sigma_x)
-        sy = sx if sigma_y is sigma_x else cells(sigma_y)
-        sz = sx if sigma_z is sigma_x else cells(sigma_z)
-        vl, zt = cells(vol), cells(zeta)
+        hx, hy, hz, origin = self._begin(grid, np.complex128 if np.iscomplexobj(smu0) else np.float64, device, smu0, sval)
+        sx = _cells(sigma_x)
+        sy = sx if sigma_y is sigma_x else _cells(sigma_y)
+        sz = sx if sigma_z is sigma_x else _cells(sigma_z)
+        vl, zt = _cells(vol), _cells(zeta)
         handle = ctypes.c_void_p()
         a = complex(smu0)
         self._eps = epsilon_r is not None
         if self._eps:
-            ep = cells(epsilon_r)
+            ep = _cells(epsilon_r)
             _lib.check(self._lib.emg3d_mg_create_vse(
                 ctypes.byref(handle), _lib.dtype_code(self.dtype), *(int(n) for n in grid.vnC), _lib.ptr(hx),
                 _lib.ptr(hy), _lib.ptr(hz), _lib.ptr(origin), _lib.ptr(sx), _lib.ptr(sy), _lib.ptr(sz), _lib.ptr(vl),
@@ -154,12 +143,19 @@ class DeviceMG:
             raise ValueError("set_smu0: a float64 (Laplace-domain) handle takes a real s*mu_0.")
         if self.dtype == np.complex128 and not np.iscomplexobj(smu0):
             raise ValueError("set_smu0: a complex128 (frequency-domain) handle takes a complex s*mu_0.")
-        if getattr(self, '_eps', False):
+        if self._eps:
             if sval is None:
                 raise TypeError("set_smu0: a handle with epsilon_r needs sval.")
             _lib.check(self._lib.emg3d_mg_set_smu0_eps(self._h, a.real, a.imag, models.seps0_of(sval)), "emg3d_mg_set_smu0_eps")
-            return
-        _lib.check(self._lib.emg3d_mg_set_smu0(self._h, a.real, a.imag), "emg3d_mg_set_smu0")
+        else:
+            _lib.check(self._lib.emg3d_mg_set_smu0(self._h, a.real, a.imag), "emg3d_mg_set_smu0")
+        self._smu0, self._sval = smu0, sval
+
+    def retarget(self, spec):
+        """``set_smu0`` to the frequency of ``spec`` (a field or ``FrequencySpec``: ``smu0``, ``sval``) unless the handle stands
+        at it already."""
+        if self._smu0 != spec.smu0:
+            self.set_smu0(spec.smu0, sval=spec.sval)
 
     def get_hfield(self, grid, smu0, mu_r=False):
         """``fields.get_h_field`` (reference fields.py:819-911) of the device-resident electric field:
@@ -227,13 +223,10 @@ class DeviceMG:
         ``g_b`` is bit for bit ``gradient()`` of system ``b`` -- forward field = slice ``b`` of the batched vector ``fwd_bvec``
         (``bvec_copy(fwd_bvec, EFIELD)``; not the live field), back-propagated field = system ``b``'s field."""
         a = complex(smu0)
-        u = np.ascontiguousarray(use, dtype=np.int32)
-        if u.size != self.nsys:
-            raise ValueError(f"grad_acc_add: {u.size} flags for {self.nsys} systems.")
+        u = self._use_flags(use, "grad_acc_add")
         st = self._lib.emg3d_mg_grad_acc_add(self._h, int(fwd_bvec), a.real, a.imag, _lib.ptr(u))
-        if st == -2:
-            raise ValueError(f"grad_acc_add: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy).")
-        _lib.check(st, "emg3d_mg_grad_acc_add")
+        self._check_bvec(st, "emg3d_mg_grad_acc_add",
+                         f"grad_acc_add: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy).")
 
     def grad_acc_get(self):
         """The accumulator: ``nC`` doubles, F-ordered."""
@@ -247,6 +240,12 @@ class DeviceMG:
             raise ValueError(f"{what}: {u.size} flags for {self.nsys} systems.")
         return u
 
+    def _check_bvec(self, st, name, message):
+        """``_lib.check`` for the calls that read a batched vector: status -2 = that vector does not exist."""
+        if st == -2:
+            raise ValueError(message)
+        _lib.check(st, name)
+
     # ---- the same per direction: three accumulators, independent of the one above (optimize.SurveyJacobian) ----
     def grad_acc3_reset(self):
         """Zero the handle's three per-direction gradient accumulators (``nC`` doubles each, allocated on first use)."""
@@ -258,9 +257,8 @@ class DeviceMG:
         a = complex(smu0)
         u = self._use_flags(use, "grad_acc3_add")
         st = self._lib.emg3d_mg_grad_acc3_add(self._h, int(fwd_bvec), a.real, a.imag, _lib.ptr(u))
-        if st == -2:
-            raise ValueError(f"grad_acc3_add: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy).")
-        _lib.check(st, "emg3d_mg_grad_acc3_add")
+        self._check_bvec(st, "emg3d_mg_grad_acc3_add",
+                         f"grad_acc3_add: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy).")
 
     def grad_acc3_get(self):
         """The three accumulators ``(acc_x, acc_y, acc_z)``: ``nC`` doubles each, F-ordered."""
@@ -290,23 +288,24 @@ class DeviceMG:
         u = self._use_flags(use, "jvec_source_b")
         held, ptrs = self._perturbation_ptrs((vx, vy, vz), "jvec_source_b")
         st = self._lib.emg3d_mg_jvec_source_b(self._h, int(fwd_bvec), a.real, a.imag, *ptrs, _lib.ptr(u))
-        if st == -2:
-            raise ValueError(f"jvec_source_b: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy), "
-                             "or a complex s*mu_0 on a float64 handle.")
-        _lib.check(st, "emg3d_mg_jvec_source_b")
+        self._check_bvec(st, "emg3d_mg_jvec_source_b", f"jvec_source_b: batched vector {fwd_bvec} does not exist (the forward "
+                         "fields must be a saved copy), or a complex s*mu_0 on a float64 handle.")
+
+    def _receiver_adjoint_args(self, rec, method, magnetic, smu0):
+        """``(n, xyz, fac, s mu_0)`` of the two receiver-adjoint calls, after their argument checks."""
+        if method not in ('cubic', 'linear'):
+            raise ValueError(f"`method` must be 'cubic' or 'linear'; provided: {method!r}.")
+        if magnetic and smu0 is None:
+            raise ValueError("magnetic receivers need `smu0` (field.smu0).")
+        return fields._receiver_args(rec) + (complex(smu0) if magnetic else 0j,)
 
     def set_receiver_adjoint_b(self, rec, w, use, accumulate=False, method='linear', magnetic=False, smu0=None):
         """``set_receiver_adjoint`` for the systems with ``use[b] != 0`` in one call (``emg3d_mg_set_receiver_adjoint_b``): ``w`` has
         shape ``(nsys, n_rec)``, row ``b`` belongs to system ``b``.  The tables that depend on grid and receivers are built once;
         per system bit for bit ``set_receiver_adjoint``; the sources of the other systems are not touched."""
-        if method not in ('cubic', 'linear'):
-            raise ValueError(f"`method` must be 'cubic' or 'linear'; provided: {method!r}.")
-        if magnetic and smu0 is None:
-            raise ValueError("magnetic receivers need `smu0` (field.smu0).")
-        n, xyz, fac = fields._receiver_args(rec)
+        n, xyz, fac, a = self._receiver_adjoint_args(rec, method, magnetic, smu0)
         u = self._use_flags(use, "set_receiver_adjoint_b")
         wv = np.ascontiguousarray(np.broadcast_to(np.asarray(w), (self.nsys, n)), dtype=self.dtype)
-        a = complex(smu0) if magnetic else 0j
         _lib.check(self._lib.emg3d_mg_set_receiver_adjoint_b(self._h, int(method == 'cubic'), int(bool(magnetic)), a.real, a.imag,
                                                              n, _lib.ptr(xyz), _lib.ptr(fac), _lib.ptr(wv), _lib.ptr(u),
                                                              int(bool(accumulate))), "emg3d_mg_set_receiver_adjoint_b")
@@ -315,17 +314,7 @@ class DeviceMG:
         """Source of the selected system <- ``s mu_0 C(v) E`` (``emg3d_mg_jvec_source``): ``E`` = workspace vector
         ``efield_vec``, ``vx, vy, vz`` conductivity perturbations per direction (``nC`` values, F-ordered; ``None``: none)."""
         a = complex(smu0)
-        held, ptrs = [], []
-        for v in (vx, vy, vz):
-            if v is None:
-                ptrs.append(ctypes.c_void_p(None))
-                continue
-            same = [h for src, h in held if src is v]
-            arr = same[0] if same else np.ascontiguousarray(np.asarray(v, dtype=np.float64).ravel(order='F'))
-            if arr.size != self.nC:
-                raise ValueError(f"jvec_source: {arr.size} values for {self.nC} cells.")
-            held.append((v, arr))
-            ptrs.append(_lib.ptr(arr))
+        held, ptrs = self._perturbation_ptrs((vx, vy, vz), "jvec_source")
         _lib.check(self._lib.emg3d_mg_jvec_source(self._h, int(efield_vec), a.real, a.imag, *ptrs), "emg3d_mg_jvec_source")
 
     def set_receiver_adjoint(self, rec, w, accumulate=False, method='linear', magnetic=False, smu0=None):
@@ -333,13 +322,8 @@ class DeviceMG:
         magnetic=magnetic, smu0=smu0)`` -- linear or cubic-spline receivers on the electric field or on ``H = get_h_field(E)``
         (without ``mu_r``; needs ``smu0``) -- applied on the device (``emg3d_mg_set_receiver_adjoint_ex``); ``w``: one value per
         receiver.  Receivers with a NaN datum contribute nothing; results repeat bit for bit."""
-        if method not in ('cubic', 'linear'):
-            raise ValueError(f"`method` must be 'cubic' or 'linear'; provided: {method!r}.")
-        if magnetic and smu0 is None:
-            raise ValueError("magnetic receivers need `smu0` (field.smu0).")
-        n, xyz, fac = fields._receiver_args(rec)
+        n, xyz, fac, a = self._receiver_adjoint_args(rec, method, magnetic, smu0)
         wv = np.ascontiguousarray(np.broadcast_to(np.asarray(w), (n,)), dtype=self.dtype)
-        a = complex(smu0) if magnetic else 0j
         _lib.check(self._lib.emg3d_mg_set_receiver_adjoint_ex(self._h, int(method == 'cubic'), int(bool(magnetic)), a.real, a.imag,
                                                               n, _lib.ptr(xyz), _lib.ptr(fac), _lib.ptr(wv),
                                                               int(bool(accumulate))), "emg3d_mg_set_receiver_adjoint_ex")
@@ -672,6 +656,45 @@ class DeviceMG:
     def stream_ptr(self):
         """The handle's HIP stream (``hipStream_t`` as an integer) for ``torch.cuda.ExternalStream``."""
         return int(self._lib.emg3d_mg_stream(self._h) or 0)
+
+
+class FrequencyHandles:
+    """The handles of a loop over frequencies on one grid and model: one ``DeviceMG`` per dtype (and optional extra ``key``),
+    created at the first frequency that asks for it -- ``DeviceMG.from_model`` on ``parts = models.model_parts(grid, model,
+    raw=True)``, ``set_batch(nsys)`` if ``nsys > 1``, ``bvec_alloc(bvecs)`` if ``bvecs`` --, re-targeted at the later ones
+    (``DeviceMG.retarget``: bit for bit a fresh handle), all closed on exit."""
+
+    def __init__(self, grid, parts, device, nsys=1, bvecs=0):
+        self.grid, self.parts, self.device, self.nsys, self.bvecs = grid, parts, device, int(nsys), int(bvecs)
+        self._handles = {}
+
+    def target(self, spec, key=()):
+        """The handle for ``spec`` (a field or ``FrequencySpec``: ``dtype``, ``smu0``, ``sval``), standing at its frequency."""
+        key = (np.dtype(spec.dtype).str,) + tuple(key)
+        dev = self._handles.get(key)
+        if dev is not None:
+            dev.retarget(spec)
+            return dev
+        dev = self._handles[key] = DeviceMG.from_model(self.grid, self.parts, spec, device=self.device)
+        if self.nsys > 1:
+            dev.set_batch(self.nsys)
+        if self.bvecs:
+            dev.bvec_alloc(self.bvecs)
+        return dev
+
+    def __iter__(self):
+        return iter(self._handles.values())
+
+    def close(self):
+        for dev in self._handles.values():
+            dev.close()
+        self._handles = {}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 # --------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 column by the reference, tests/golden/make_receiver_adjoint_golden.py) against the oracle's forward operator, a NumPy
 restatement of what the device does for the cubic-spline receivers -- scatter of the 64 stencil weights, the transposed
 prefilter as D F D^-1, trimmed write -- against the fixture, the identity F^T = D F D^-1 itself, and the argument checks of
-the new Python options (raised before the library is touched)."""
+the new Python options (raised before the library is touched); and the one rule for the residual / adjoint source
+(optimize._adjoint_source) against the two expressions it replaced."""
 import numpy as np
 import pytest
 
@@ -203,3 +204,89 @@ def test_argument_errors_come_before_the_library(no_library):
         em.fields.get_receiver_adjoint(grid, rec[:3], np.ones(rec[0].size))
     with pytest.raises(TypeError, match="real"):
         em.fields.get_receiver_adjoint(grid, rec, 1j * np.ones(rec[0].size), freq=-1.0)
+
+
+class _SourceRecorder:
+    """Stands in for a DeviceMG: keeps what ``optimize._adjoint_source`` asks of it."""
+
+    def __init__(self):
+        self.sources, self.adjoints = [], []
+
+    def set_source(self, src, smu0, strength=0, accumulate=False, electric=True):
+        self.sources.append((int(src[0]), strength, accumulate, electric))
+
+    def set_receiver_adjoint(self, rec, w, **kwargs):
+        self.adjoints.append((np.array(w), kwargs))
+
+
+@pytest.mark.parametrize('electric', [True, False], ids=['electric', 'magnetic'])
+@pytest.mark.parametrize('freq', [1.5, -1.2], ids=['c128', 'f64'])
+def test_adjoint_source_rule_equals_both_expressions_it_replaced(freq, electric):
+    """The reference rule of optimize._adjoint_source -- strengths ``conj(w r) / s mu_0`` (magnetic: ``/ s mu_0`` again), zero
+    strengths skipped -- gives bit for bit (np.array_equal; the sign of a zero component is not seen) the strengths and the skip
+    set of the two expressions the entry points used before: ``conj(r) conj(w) / s mu_0`` with the tests ``isnan(r)`` and
+    ``strength == 0`` (gradient, survey_gradient), and ``where(isnan(w r), 0, conj(w r)) / s mu_0`` with the test ``== 0`` before
+    the division (the Jacobians; electric receivers only there).  Data: random residuals (complex for a frequency, real for a
+    Laplace value) with purely real, purely imaginary, zero and one NaN entry; real weights with zeros and, for the frequency,
+    one complex weight, 2 + 0.5j: its components are powers of two, so its product with a residual rounds once whether or not
+    the vectorised array product fuses multiply and add.  (For a general complex weight NumPy's array and scalar products differ
+    in the last bit on CPUs with FMA, so the two earlier expressions did; the weights of a least-squares misfit are real.)"""
+    import emg3d_amd as em
+    from emg3d_amd import optimize
+    n = 4000
+    rng = np.random.default_rng(17)
+    smu0 = em.fields.FrequencySpec(freq).smu0
+    r = rng.standard_normal(n) * 10.0 ** rng.uniform(-14, -8, n)
+    w = rng.uniform(0.5, 2, n) * 10.0 ** rng.uniform(20, 26, n)
+    if freq > 0:
+        r = r + 1j * rng.standard_normal(n) * 10.0 ** rng.uniform(-14, -8, n)
+        r[0:40] = r[0:40].real
+        r[40:80] = 1j * r[40:80].imag
+        w = w.astype(complex)
+        w[100] = 2 + 0.5j
+    r[80:120:3] = 0
+    r[7] = np.nan
+    w[60:400:7] = 0
+    rec = (np.arange(n, dtype=float),) + (np.zeros(n),) * 4        # (the x-coordinate names the receiver)
+
+    # the rule as gradient() and survey_gradient() had it
+    old_a = {}
+    for i in range(n):
+        if np.isnan(r[i]):
+            continue
+        st = r[i].conj() * np.conj(w[i]) / smu0
+        if not electric:
+            st = st / smu0
+        if st == 0:
+            continue
+        old_a[i] = st
+    # the rule as Jacobian and SurveyJacobian had it (electric receivers)
+    cw_jac = np.where(np.isnan(w * r), 0, np.conj(w * r))
+    old_b = {i: cw_jac[i] / smu0 for i in range(n) if not cw_jac[i] == 0}
+
+    cw = np.conj(w * r)
+    cw = np.where(np.isnan(cw), 0, cw)
+    dev = _SourceRecorder()
+    assert optimize._adjoint_source(dev, rec, smu0, cw, method='cubic', exact=False, electric=electric)
+    got = {k: st for k, st, _, _ in dev.sources}
+    assert not dev.adjoints and len(got) == len(dev.sources) and 1000 < len(got) < n - 50
+    assert [acc for _, _, acc, _ in dev.sources] == [False] + [True] * (len(got) - 1)
+    assert all(el is electric for _, _, _, el in dev.sources)
+    assert 7 not in got and 100 in got and 82 in got and 80 not in got and 81 not in got
+    keys = sorted(got)
+    assert keys == sorted(old_a)
+    assert np.array_equal(np.array([got[k] for k in keys]), np.array([old_a[k] for k in keys]))
+    if electric:
+        assert keys == sorted(old_b)
+        assert np.array_equal(np.array([got[k] for k in keys]), np.array([old_b[k] for k in keys]))
+    # nothing usable: no call, False; exact or linear receivers: one set_receiver_adjoint with cw as it is
+    none = _SourceRecorder()
+    assert not optimize._adjoint_source(none, rec, smu0, np.zeros(n), method='cubic', exact=False, electric=electric)
+    assert not optimize._adjoint_source(none, rec, smu0, np.zeros(n), method='cubic', exact=True, electric=electric)
+    assert not none.sources and not none.adjoints
+    for method, exact in (('cubic', True), ('linear', False)):
+        one = _SourceRecorder()
+        assert optimize._adjoint_source(one, rec, smu0, cw, method=method, exact=exact, electric=electric)
+        assert not one.sources and len(one.adjoints) == 1
+        assert np.array_equal(one.adjoints[0][0], cw)
+        assert one.adjoints[0][1] == dict(method=method, magnetic=not electric, smu0=smu0)
