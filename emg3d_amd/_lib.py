@@ -22,7 +22,7 @@ c_double = ctypes.c_double
 c_dp = ctypes.POINTER(ctypes.c_double)
 
 # include/emg3d_hip.h: EMG3D_HIP_ABI_VERSION -- a library built from another header version is refused at load
-ABI_VERSION = 110
+ABI_VERSION = 111
 
 # name -> (restype, argtypes); mirrors include/emg3d_hip.h one to one.
 SIGNATURES = {
@@ -58,6 +58,8 @@ SIGNATURES = {
     "emg3d_mg_create_vse": (c_int, [ctypes.POINTER(c_vp), c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp,
                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_double, c_double, c_double, c_int, c_int]),
     "emg3d_mg_set_smu0_eps": (c_int, [c_vp, c_double, c_double, c_double]),
+    "emg3d_mg_set_model": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp]),
+    "emg3d_mg_get_sigma": (c_int, [c_vp, c_int, c_vp]),
     "emg3d_mg_set_sfield_vector": (c_int, [c_vp, c_vp, c_double, c_double]),
     "emg3d_mg_set_sfield_dipole": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
     "emg3d_source_field": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),

@@ -32,7 +32,7 @@ template <class T>
 int create_impl(emg3d_mg_t** out, int dtype, i64 nx, i64 ny, i64 nz, const double* hx, const double* hy,
                 const double* hz, const double* origin, const void* eta_x, const void* eta_y,
                 const void* eta_z, const double* zeta, int device, bool sv = false, double smu0_re = 0.0,
-                double smu0_im = 0.0, const double* vol = nullptr, bool resistivity = false,
+                double smu0_im = 0.0, const double* vol = nullptr, int map = 0,
                 const double* epsr = nullptr, double seps0 = 0.0) {
     if (nx < 2 || ny < 2 || nz < 2) return -2;
     // (a failing step gives the handle's blocks back before it returns)
@@ -75,9 +75,7 @@ int create_impl(emg3d_mg_t** out, int dtype, i64 nx, i64 ny, i64 nz, const doubl
             L.eta[c] = m->template dalloc<T>(nC);
             m->sv[c] = m->template dalloc<double>(nC);
             CREATE_TRY(m->h2d(m->sv[c], src[c], (size_t)nC * sizeof(double)));
-            if (resistivity && !m->broken)        // the arrays hold rho: sigma = 1 / rho on the device
-                hipLaunchKernelGGL(k_recip_inplace, dim3((unsigned)std::min<i64>((nC + EMG_BLOCK - 1) / EMG_BLOCK, 4096)),
-                                   dim3(EMG_BLOCK), 0, m->stream, m->sv[c], nC);
+            m->sigma_of_map(m->sv[c], m->sv[c], map, nC);     // the arrays hold the model's property: sigma = backward(p) on the device
         }
         m->form_eta(L, scalar_of<T>(smu0_re, smu0_im));
     }
@@ -940,21 +938,23 @@ int emg3d_mg_create_sv(emg3d_mg_t** out, int dtype, int64_t nx, int64_t ny, int6
 int emg3d_mg_create_vs(emg3d_mg_t** out, int dtype, int64_t nx, int64_t ny, int64_t nz, const double* hx,
                        const double* hy, const double* hz, const double* origin, const double* sigma_x,
                        const double* sigma_y, const double* sigma_z, const double* vol, const double* zeta,
-                       double smu0_re, double smu0_im, int resistivity, int device) {
+                       double smu0_re, double smu0_im, int map, int device) {
     if (!out || !sigma_x || !vol) return -1;
+    if (map < 0 || map >= EMG_MAP_CODES) return -2;             // property map codes: include/emg3d_hip.h
     if (dtype ? smu0_re != 0.0 : smu0_im != 0.0) return -2;     // i b (frequency domain) or real (Laplace domain)
-    return dtype ? create_impl<c128>(out, 1, nx, ny, nz, hx, hy, hz, origin, sigma_x, sigma_y, sigma_z, zeta, device, true, smu0_re, smu0_im, vol, resistivity != 0)
-                 : create_impl<double>(out, 0, nx, ny, nz, hx, hy, hz, origin, sigma_x, sigma_y, sigma_z, zeta, device, true, smu0_re, smu0_im, vol, resistivity != 0);
+    return dtype ? create_impl<c128>(out, 1, nx, ny, nz, hx, hy, hz, origin, sigma_x, sigma_y, sigma_z, zeta, device, true, smu0_re, smu0_im, vol, map)
+                 : create_impl<double>(out, 0, nx, ny, nz, hx, hy, hz, origin, sigma_x, sigma_y, sigma_z, zeta, device, true, smu0_re, smu0_im, vol, map);
 }
 
 int emg3d_mg_create_vse(emg3d_mg_t** out, int dtype, int64_t nx, int64_t ny, int64_t nz, const double* hx,
                         const double* hy, const double* hz, const double* origin, const double* sigma_x,
                         const double* sigma_y, const double* sigma_z, const double* vol, const double* zeta,
-                        const double* epsilon_r, double smu0_re, double smu0_im, double seps0, int resistivity, int device) {
+                        const double* epsilon_r, double smu0_re, double smu0_im, double seps0, int map, int device) {
     if (!out || !sigma_x || !vol || !epsilon_r) return -1;
+    if (map < 0 || map >= EMG_MAP_CODES) return -2;
     if (dtype ? smu0_re != 0.0 : smu0_im != 0.0) return -2;     // i b (frequency domain) or real (Laplace domain)
-    return dtype ? create_impl<c128>(out, 1, nx, ny, nz, hx, hy, hz, origin, sigma_x, sigma_y, sigma_z, zeta, device, true, smu0_re, smu0_im, vol, resistivity != 0, epsilon_r, seps0)
-                 : create_impl<double>(out, 0, nx, ny, nz, hx, hy, hz, origin, sigma_x, sigma_y, sigma_z, zeta, device, true, smu0_re, smu0_im, vol, resistivity != 0, epsilon_r, seps0);
+    return dtype ? create_impl<c128>(out, 1, nx, ny, nz, hx, hy, hz, origin, sigma_x, sigma_y, sigma_z, zeta, device, true, smu0_re, smu0_im, vol, map, epsilon_r, seps0)
+                 : create_impl<double>(out, 0, nx, ny, nz, hx, hy, hz, origin, sigma_x, sigma_y, sigma_z, zeta, device, true, smu0_re, smu0_im, vol, map, epsilon_r, seps0);
 }
 
 void emg3d_mg_destroy(emg3d_mg_t* mg) {
@@ -1020,6 +1020,25 @@ int emg3d_mg_set_smu0_eps(emg3d_mg_t* mg, double smu0_re, double smu0_im, double
         m->seps0 = seps0;
         const int st = m->set_smu0(scalar_of<T>(smu0_re, smu0_im));
         if (st) { m->seps0 = seps0_before; return st; }         // (the handle keeps a consistent (s mu_0, s eps_0) pair)
+        return finish(m);
+    });
+}
+
+int emg3d_mg_set_model(emg3d_mg_t* mg, int map, const double* px, const double* py, const double* pz) {
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        const int st = m->set_model(map, px, py, pz);
+        if (st) return st;
+        return finish(m);
+    });
+}
+
+int emg3d_mg_get_sigma(emg3d_mg_t* mg, int comp, double* out) {
+    DISPATCH(mg, {
+        if (!m->sv[0] || !m->volw) return -7;
+        if (comp < 0 || comp > 2 || !out) return -2;
+        HIP_TRY(hipSetDevice(m->device));
+        HIP_TRY(m->d2h(out, m->sv[comp], (size_t)m->lv0->nCells * sizeof(double)));
         return finish(m);
     });
 }

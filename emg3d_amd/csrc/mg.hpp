@@ -627,7 +627,9 @@ struct MG : emg3d_mg {
     double seps0 = 0.0;            // c = s eps_0 (Laplace domain) resp. Im(s) eps_0 (frequency domain) of the current frequency
     static double imag_or_real(double x) { return x; }
     static double imag_or_real(c128 x) { return x.im; }
+    T smu0_now = T();              // the s mu_0 the level-0 eta was last formed with (form_eta): where the handle stands
     void form_eta(Level<T>& L0, T smu0) {
+        smu0_now = smu0;
         const unsigned blocks = (unsigned)std::min<i64>((L0.nCells + EMG_BLOCK - 1) / EMG_BLOCK, 4096);
         for (int c = 0; c < 3; ++c) {
             if (c > 0 && eta_alias[c]) continue;
@@ -651,6 +653,37 @@ struct MG : emg3d_mg {
     }
     int set_smu0(T smu0) {
         if (!sv[0]) return -7;
+        refresh_model(smu0);
+        return 0;
+    }
+    // sigma = backward(p) of property map `map` (k_sigma_of_map) from the device array `p` into `out`, which may be `p`
+    void sigma_of_map(double* out, const double* p, int map, i64 n) {
+        if (map == 0 && out == p) return;
+        MG_LAUNCH(k_sigma_of_map, dim3((unsigned)std::min<i64>((n + EMG_BLOCK - 1) / EMG_BLOCK, 4096)), dim3(EMG_BLOCK), 0, stream,
+                  out, p, map, n);
+    }
+    // ---- another model on the same handle (handles that keep sigma and V apart: emg3d_mg_create_vs / _vse) ----
+    // The property arrays of a model on the same grid, in the same anisotropy case, go into the sv[] the handle has; then
+    // everything that depends on sigma is recomputed as for another frequency, at the frequency the handle stands at.  No buffer
+    // moves: launch graphs, placement, workspace vectors and accumulators stay.  A failed upload may leave sv[] half
+    // written: the handle is then broken.
+    int set_model(int map, const double* px, const double* py, const double* pz) {
+        if (!sv[0] || !volw) return -7;
+        if (map < 0 || map >= EMG_MAP_CODES || !px) return -2;
+        const double* p[3] = {px, py, pz};
+        for (int c = 1; c < 3; ++c)
+            if ((p[c] == nullptr || p[c] == px) != eta_alias[c]) return -2;
+        const i64 nC = lv0->nCells;
+        for (int c = 0; c < 3; ++c) {
+            if (c > 0 && eta_alias[c]) continue;
+            const hipError_t st = h2d(sv[c], p[c], (size_t)nC * sizeof(double));
+            if (st != hipSuccess) { (void)hipGetLastError(); err = (int)st; broken = true; return (int)st; }
+            sigma_of_map(sv[c], sv[c], map, nC);
+        }
+        refresh_model(smu0_now);
+        return 0;
+    }
+    void refresh_model(T smu0) {
         Level<T>& L0 = *lv0;
         form_eta(L0, smu0);
         for (auto& kv : hier) {
@@ -671,7 +704,6 @@ struct MG : emg3d_mg {
         refresh(L0);
         for (auto& kv : hier) for (auto& l : kv.second.lv) if (l) refresh(*l);
         check_launch();
-        return 0;
     }
 
     // Level 0 of a model without magnetic permeabilities: zeta is the cell volume (hx hy) hz.  Checked bit for bit on the

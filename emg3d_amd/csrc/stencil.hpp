@@ -856,10 +856,23 @@ static __global__ __launch_bounds__(EMG_BLOCK) void k_zeta_is_volume(const doubl
     if (bad) *flag = 1;
 }
 
-// sigma = 1 / rho in place (Model.conductivity for the 'Resistivity' mapping, reference models.py: an IEEE division, the
-// same bits as NumPy's)
-static __global__ __launch_bounds__(EMG_BLOCK) void k_recip_inplace(double* v, i64 n) {
-    for (i64 i = (i64)blockIdx.x * EMG_BLOCK + threadIdx.x; i < n; i += (i64)gridDim.x * EMG_BLOCK) v[i] = 1.0 / v[i];
+// sigma = backward(p) of the model's property map (Model.conductivity; reference emg3d/maps.py:319-448), `out` may be `p` (in
+// place; hence no __restrict__).  Map codes (include/emg3d_hip.h): 0 conductivity (a copy), 1 resistivity (1 / p: an IEEE
+// division, NumPy's bits), 2 log10 conductivity (10^p), 3 ln conductivity (e^p), 4 log10 resistivity (10^-p), 5 ln resistivity (e^-p).
+// 2-5 go through the device's exp10 / exp: not NumPy's bits (DESIGN 8.6 has the measured distance); the negation is exact.
+// The code is uniform over the launch: one branch per thread outside the loop.  No LDS, no scratch.
+#define EMG_MAP_CODES 6
+static __global__ __launch_bounds__(EMG_BLOCK) void k_sigma_of_map(double* out, const double* p, int map, i64 n) {
+#pragma clang fp contract(off)
+    const i64 i0 = (i64)blockIdx.x * EMG_BLOCK + threadIdx.x, step = (i64)gridDim.x * EMG_BLOCK;
+    switch (map) {
+        case 1: for (i64 i = i0; i < n; i += step) out[i] = 1.0 / p[i]; break;
+        case 2: for (i64 i = i0; i < n; i += step) out[i] = exp10(p[i]); break;
+        case 3: for (i64 i = i0; i < n; i += step) out[i] = exp(p[i]); break;
+        case 4: for (i64 i = i0; i < n; i += step) out[i] = exp10(-p[i]); break;
+        case 5: for (i64 i = i0; i < n; i += step) out[i] = exp(-p[i]); break;
+        default: for (i64 i = i0; i < n; i += step) out[i] = p[i]; break;
+    }
 }
 
 // eta = (s mu_0 V) sigma as VolumeModel rounds it (reference models.py:631-658: `(smu0 * vol) * sigma`), from the cell

@@ -276,3 +276,141 @@ def cellaverages2edges(vx, vy, vz, vol, out_x, out_y, out_z):
     for o, r, shp in zip((out_x, out_y, out_z), outs, shapes):
         if r is not None:
             o[...] = r.reshape(shp, order='F')
+
+
+# --------------------------------------------------------------------------
+# Property maps
+# --------------------------------------------------------------------------
+class _Map:
+    """A property map: the model's own parameter ``p`` against the conductivity ``sigma`` every computation uses (the six maps of
+    the reference, emg3d/maps.py:284-448).  ``forward``: sigma -> p; ``backward``: p -> sigma; ``derivative_chain(gradient,
+    mapped)``: a gradient with respect to sigma becomes one with respect to p, IN PLACE (``gradient *= d sigma / d p``).
+
+    ``name`` is what ``Model(mapping=...)`` takes, ``code`` what the device takes (``emg3d_mg_create_vs``, ``emg3d_mg_set_model``:
+    the handle forms ``backward(p)`` itself), ``log`` whether ``p`` is a logarithm (any sign is then a valid value)."""
+    name = description = None
+    code = None
+    log = False
+
+    def __repr__(self):
+        return f"Map{self.name}: {self.description} <-> conductivity"
+
+    def forward(self, conductivity):
+        raise NotImplementedError
+
+    def backward(self, mapped):
+        raise NotImplementedError
+
+    def derivative_chain(self, gradient, mapped):
+        raise NotImplementedError
+
+    def chain_factor(self, sigma):
+        """``d sigma / d p`` from the conductivity itself, by multiplication only -- what the mapped Jacobian products use with
+        the conductivity the device holds (``DeviceMG.get_sigma``), so that no transcendental is evaluated a second time."""
+        raise NotImplementedError
+
+
+class MapConductivity(_Map):
+    """p = sigma."""
+    name, description, code = 'Conductivity', 'conductivity', 0
+
+    def forward(self, conductivity):
+        return conductivity
+
+    def backward(self, mapped):
+        return mapped
+
+    def derivative_chain(self, gradient, mapped):
+        pass
+
+    def chain_factor(self, sigma):
+        return np.ones_like(sigma)
+
+
+class MapResistivity(_Map):
+    """p = rho = 1 / sigma; d sigma / d p = -1 / p^2 = -sigma^2."""
+    name, description, code = 'Resistivity', 'resistivity', 1
+
+    def forward(self, conductivity):
+        return 1.0 / conductivity
+
+    def backward(self, mapped):
+        return 1.0 / mapped
+
+    def derivative_chain(self, gradient, mapped):
+        gradient *= -self.backward(mapped) ** 2
+
+    def chain_factor(self, sigma):
+        return -(sigma * sigma)
+
+
+class MapLgConductivity(_Map):
+    """p = log10(sigma); d sigma / d p = sigma ln 10."""
+    name, description, code, log = 'LgConductivity', 'log_10(conductivity)', 2, True
+
+    def forward(self, conductivity):
+        return np.log10(conductivity)
+
+    def backward(self, mapped):
+        return 10 ** mapped
+
+    def derivative_chain(self, gradient, mapped):
+        gradient *= self.backward(mapped) * np.log(10)
+
+    def chain_factor(self, sigma):
+        return sigma * np.log(10)
+
+
+class MapLnConductivity(_Map):
+    """p = ln(sigma); d sigma / d p = sigma."""
+    name, description, code, log = 'LnConductivity', 'log_e(conductivity)', 3, True
+
+    def forward(self, conductivity):
+        return np.log(conductivity)
+
+    def backward(self, mapped):
+        return np.exp(mapped)
+
+    def derivative_chain(self, gradient, mapped):
+        gradient *= self.backward(mapped)
+
+    def chain_factor(self, sigma):
+        return sigma.copy()
+
+
+class MapLgResistivity(_Map):
+    """p = log10(rho) = log10(1 / sigma); d sigma / d p = -sigma ln 10."""
+    name, description, code, log = 'LgResistivity', 'log_10(resistivity)', 4, True
+
+    def forward(self, conductivity):
+        return np.log10(1.0 / conductivity)
+
+    def backward(self, mapped):
+        return 10 ** -mapped
+
+    def derivative_chain(self, gradient, mapped):
+        gradient *= -self.backward(mapped) * np.log(10)
+
+    def chain_factor(self, sigma):
+        return -sigma * np.log(10)
+
+
+class MapLnResistivity(_Map):
+    """p = ln(rho) = ln(1 / sigma); d sigma / d p = -sigma."""
+    name, description, code, log = 'LnResistivity', 'log_e(resistivity)', 5, True
+
+    def forward(self, conductivity):
+        return np.log(1.0 / conductivity)
+
+    def backward(self, mapped):
+        return np.exp(-mapped)
+
+    def derivative_chain(self, gradient, mapped):
+        gradient *= -self.backward(mapped)
+
+    def chain_factor(self, sigma):
+        return -sigma
+
+
+MAPS = {m.name: m for m in (MapConductivity, MapResistivity, MapLgConductivity, MapLnConductivity, MapLgResistivity,
+                            MapLnResistivity)}

@@ -18,33 +18,34 @@ class Model:
 
     def __init__(self, grid, property_x=1., property_y=None, property_z=None, mu_r=None,
                  epsilon_r=None, mapping='Resistivity'):
-        if mapping not in ('Resistivity', 'Conductivity'):
-            raise ValueError("Only 'Resistivity' and 'Conductivity' mappings are supported.")
+        if mapping not in maps.MAPS:
+            raise ValueError(f"`mapping` must be one of {sorted(maps.MAPS)}; provided: {mapping!r}.")
         self.mapping = mapping
+        self.map = maps.MAPS[mapping]()
         self.vnC = tuple(grid.vnC)
         self.nC = int(grid.nC)
-        self.property_x = self._check(property_x, 'property_x')
-        self.property_y = None if property_y is None else self._check(property_y, 'property_y')
-        self.property_z = None if property_z is None else self._check(property_z, 'property_z')
+        self.property_x = self._check(property_x, 'property_x', mapped=True)
+        self.property_y = None if property_y is None else self._check(property_y, 'property_y', mapped=True)
+        self.property_z = None if property_z is None else self._check(property_z, 'property_z', mapped=True)
         self.mu_r = None if mu_r is None else self._check(mu_r, 'mu_r')
         self.epsilon_r = None if epsilon_r is None else self._check(epsilon_r, 'epsilon_r')
         self.case = (1 if self.property_y is not None else 0) + (2 if self.property_z is not None else 0)
         self.case_names = ['isotropic', 'HTI', 'VTI', 'tri-axial']
 
-    def _check(self, value, name):
+    def _check(self, value, name, mapped=False):
         value = np.asarray(value, dtype=np.float64)
         if value.size not in (1, self.nC):
             raise ValueError(f"Shape of {name} must be (), {self.vnC}, or {self.nC}.\n"
                              f"Provided: {value.shape}.")
-        if not np.all(np.isfinite(value)) or np.any(value <= 0):
-            raise ValueError(f"`{name}` must be all finite and positive.")
+        # (a logarithm may have any sign: reference models.py:457)
+        if not np.all(np.isfinite(value)) or (np.any(value <= 0) and not (mapped and self.map.log)):
+            raise ValueError(f"`{name}` must be all finite{'' if mapped and self.map.log else ' and positive'}.")
         if value.size == self.nC:
             value = value.reshape(self.vnC, order='F')
         return value
 
     def conductivity(self, name):
-        p = getattr(self, name)
-        return 1.0 / p if self.mapping == 'Resistivity' else p
+        return self.map.backward(getattr(self, name))
 
     def __repr__(self):
         return f"Model [{self.mapping}]; {self.case_names[self.case]}; {self.vnC}"
@@ -52,9 +53,9 @@ class Model:
     def interpolate2grid(self, grid, new_grid, **grid2grid_opts):
         """This model, located on ``grid``, on ``new_grid`` (reference emg3d/models.py:364-430): every property array
         through :func:`emg3d_amd.maps.grid2grid` with ``grid2grid_opts`` (defaults ``method='volume'``,
-        ``extrapolate=True``, ``log=True``: the mappings supported here are not logarithmic); scalars are expanded to the
+        ``extrapolate=True``, ``log=True`` unless the mapping is a logarithm already); scalars are expanded to the
         cells first.  Returns a new :class:`Model` on ``new_grid`` with the same mapping."""
-        inp = {'method': 'volume', 'extrapolate': True, 'log': True, **grid2grid_opts, 'grid': grid, 'new_grid': new_grid}
+        inp = {'method': 'volume', 'extrapolate': True, 'log': not self.map.log, **grid2grid_opts, 'grid': grid, 'new_grid': new_grid}
 
         def regrid(prop):
             return maps.grid2grid(values=prop * np.ones(grid.vnC) if prop.size == 1 else prop, **inp)
@@ -87,8 +88,10 @@ def sigma_volume(grid, model):
 
 
 class ModelParts(tuple):
-    """The tuple ``model_parts`` returns, plus ``epsilon_r`` (F-ordered array or None)."""
+    """The tuple ``model_parts`` returns, plus ``epsilon_r`` (F-ordered array or None) and ``map_code`` (``raw=True``: the code
+    of the model's property map, ``maps._Map.code``; None otherwise)."""
     epsilon_r = None
+    map_code = None
 
 
 def seps0_of(sval):
@@ -106,7 +109,9 @@ def model_parts(grid, model, raw=False):
 
     ``raw=True``: the model's property arrays as they are plus a flag, ``(p_x, p_y, p_z, vol, zeta, resistivity)`` -- for the
     'Resistivity' mapping the device then takes the reciprocal itself (``from_model_parts(..., resistivity=True)``; an
-    IEEE division, the bits of ``Model.conductivity``), which saves three host passes over the model per solve."""
+    IEEE division, the bits of ``Model.conductivity``), which saves three host passes over the model per solve.  The logarithmic
+    maps come with the flag ``False`` and are told apart by the attribute ``.map_code`` (set for every map), which
+    ``DeviceMG.from_model`` hands to the device: it forms ``sigma = backward(p)`` itself (``k_sigma_of_map``)."""
     vol = np.asfortranarray(grid.cell_volumes.reshape(grid.vnC, order='F'), dtype=np.float64)
     get = (lambda name: getattr(model, name)) if raw else model.conductivity
     sx = np.asfortranarray(np.broadcast_to(get('property_x'), grid.vnC), dtype=np.float64)
@@ -115,6 +120,8 @@ def model_parts(grid, model, raw=False):
     zeta = vol if model.mu_r is None else vol / model.mu_r
     out = (sx, sy, sz, vol, np.asfortranarray(zeta, dtype=np.float64))
     out = ModelParts(out + (model.mapping == 'Resistivity',) if raw else out)
+    if raw:
+        out.map_code = model.map.code
     if model.epsilon_r is not None:
         out.epsilon_r = np.asfortranarray(np.broadcast_to(model.epsilon_r, grid.vnC), dtype=np.float64)
     return out

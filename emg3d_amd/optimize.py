@@ -18,11 +18,16 @@ survey, every solve batched over the sources.  ``model_gradient(...,
 model_grid=)`` maps the gradient to the model grid as the reference does (``maps.grid2grid(grid, -grad, model_grid,
 'cubic')``, optimize.py:201-211) and applies the chain rule there.
 
+An inversion keeps a ``Jacobian`` / ``SurveyJacobian`` (or the ``FrequencyHandles`` of ``survey_gradient(handles=)``) open for its
+whole life: ``set_model`` presents the next model -- in any of the six property maps -- to the open handles, and ``mapped=True``
+gives the products in the model's own parameter.
+
 What the four entry points share is written once: the argument checks (``_check_arguments``), the receivers (``_receivers``), the
 residual / adjoint source of one system (``_adjoint_source``, the reference's rule included), the flags of a short chunk
 (``_first``) and, for the two Jacobians, ``_JacobianBase``; the per-dtype handles of the survey-level entry points, re-targeted
 from frequency to frequency, are a ``solver.FrequencyHandles`` (``DeviceMG.retarget``).
 """
+import contextlib
 import time
 
 import numpy as np
@@ -128,7 +133,7 @@ def gradient(grid, model, src, freq, rec, observed, weights=None, strength=0, de
     opts.pop('return_info', None)
     # (sigma, V) handle: eta with VolumeModel's rounding, i.e. the fields of solver.solve() bit for bit
     parts = models.model_parts(grid, model, raw=True)
-    with solver.DeviceMG.from_model_parts(grid, *parts, smu0=smu0, device=device) as dev:
+    with solver.DeviceMG.from_model_parts(grid, *parts, smu0=smu0, device=device, map_code=parts.map_code) as dev:
         # forward field (stays on the device)
         _, finfo = solver.solve(grid, None, sfield, handle=dev, return_info=True, source=(src, strength),
                                 download=False, **opts)
@@ -149,6 +154,21 @@ def gradient(grid, model, src, freq, rec, observed, weights=None, strength=0, de
     return phi, grad, dict(synthetic=synthetic, forward=finfo, backward=binfo)
 
 
+def _check_handles(handles, grid, nsys):
+    """``survey_gradient(handles=)``: the caller's ``FrequencyHandles`` must be made for this grid, ``nsys`` systems and one
+    batched vector."""
+    if not isinstance(handles, solver.FrequencyHandles):
+        raise TypeError(f"`handles` must be a solver.FrequencyHandles; provided: {type(handles).__name__}.")
+    hg = handles.grid
+    same = tuple(hg.vnC) == tuple(grid.vnC) and np.array_equal(hg.origin, grid.origin) and \
+        all(np.array_equal(a, b) for a, b in zip(hg.h, grid.h))
+    if not same:
+        raise ValueError("survey_gradient: `handles` were made for another grid.")
+    if handles.nsys != nsys or handles.bvecs != 1:
+        raise ValueError(f"survey_gradient: `handles` must be made with nsys=min(batch, n_src)={nsys} and bvecs=1; "
+                         f"they have nsys={handles.nsys}, bvecs={handles.bvecs}.")
+
+
 def _sum_survey(partials, misfits, vnC):
     """The defined order of the survey sums: ``grad = ((0 + G_0) + G_1) + ...`` over the frequencies as given, ``phi`` the
     sequential sum of ``misfits[i_src, i_freq]`` with the frequency as the outer and the source as the inner loop."""
@@ -163,7 +183,7 @@ def _sum_survey(partials, misfits, vnC):
 
 
 def survey_gradient(grid, model, sources, freqs, rec, observed, weights=None, strength=0, device=0, electric=True,
-                    adjoint='reference', batch=8, **solver_opts):
+                    adjoint='reference', batch=8, handles=None, **solver_opts):
     """Misfit and adjoint-state gradient of a SURVEY -- every source of ``sources`` at every frequency of ``freqs`` -- on the
     computational grid: what the reference's ``simulation.gradient`` (emg3d/optimize.py:115-217) sums over its (source, frequency)
     pairs, i.e. the sum of ``gradient()`` over the pairs, without a handle, a hierarchy and an ``nC``-sized download per pair.
@@ -189,7 +209,12 @@ def survey_gradient(grid, model, sources, freqs, rec, observed, weights=None, st
     ``synthetic`` ``(n_src, n_freq, n_rec)``, ``misfit`` ``(n_src, n_freq)``, ``partial`` the ``G_f`` with shape ``(n_freq,) +
     vnC`` (F-ordered; the unit of exchange of ``shard.gather_survey_gradient``), ``forward[i][j]`` / ``backward[i][j]`` the solver
     info dicts, ``phases`` host seconds spent in the forward solves, the data, the adjoint sources, the backward solves and the
-    accumulation."""
+    accumulation.
+
+    ``handles``: a ``solver.FrequencyHandles`` of the caller's, made on ``grid`` with ``nsys=min(batch, n_src)`` and ``bvecs=1``
+    (``ValueError`` otherwise) -- it is used and left open, for the next call after a ``handles.set_model(...)``: the loop of an
+    inversion then keeps hierarchies, work buffers and launch graphs.  The handles hold the model; ``model`` must be the one they
+    were last given.  The results are those of a call without ``handles``, bit for bit."""
     _check_arguments('Gradient', model, adjoint, count=('batch', batch), krylov=solver_opts.get('sslsolver')
                      and "survey_gradient: resident sources are solved by multigrid only")
     nrec, rec = _receivers(rec)
@@ -210,6 +235,8 @@ def survey_gradient(grid, model, sources, freqs, rec, observed, weights=None, st
     opts = {k: v for k, v in solver_opts.items() if k not in ('return_info', 'sslsolver')}
     vnC = tuple(int(n) for n in grid.vnC)
     nb = min(int(batch), ns)
+    if handles is not None:
+        _check_handles(handles, grid, nb)
     cplx = any(sp.dtype.kind == 'c' for sp in specs)
     synthetic = np.full((ns, nf, nrec), np.nan, dtype=np.complex128 if cplx else np.float64)
     misfits = np.zeros((ns, nf))
@@ -223,8 +250,11 @@ def survey_gradient(grid, model, sources, freqs, rec, observed, weights=None, st
         phases[name] += t1 - t0
         return t1
 
-    parts = models.model_parts(grid, model, raw=True)
-    with solver.FrequencyHandles(grid, parts, device, nsys=nb, bvecs=1) as handles:
+    if handles is None:
+        own = handles = solver.FrequencyHandles(grid, models.model_parts(grid, model, raw=True), device, nsys=nb, bvecs=1)
+    else:
+        own = contextlib.nullcontext()
+    with own:
         for j, spec in enumerate(specs):
             smu0 = spec.smu0
             dev = handles.target(spec)
@@ -285,8 +315,9 @@ def survey_gradient(grid, model, sources, freqs, rec, observed, weights=None, st
 def model_gradient(grid, model, grad, model_grid=None):
     """d(misfit) / d(model property) from ``gradient()``'s ``grad`` (on the computational grid ``grid``): the reference's
     last steps (optimize.py:201-214): the sign, the mapping to the model grid, then the chain rule of the model's property
-    map -- conductivity: identity; resistivity rho: d sigma / d rho = -1 / rho^2 (``maps.MapResistivity.derivative_chain``,
-    emg3d/maps.py).
+    map -- conductivity: identity; resistivity rho: d sigma / d rho = -1 / rho^2; the four logarithmic maps: their
+    ``derivative_chain`` (``maps.MapLgConductivity`` ...: ``sigma ln 10``, ``sigma``, ``-sigma ln 10``, ``-sigma`` with ``sigma =
+    backward(p)`` on the host).
 
     ``model_grid=None``: ``model`` lives on ``grid`` (the reference's ``gridding='same'``), nothing is regridded.
     Otherwise ``model`` lives on ``model_grid``: ``-grad`` is mapped there with ``maps.grid2grid(grid, -grad, model_grid,
@@ -302,7 +333,16 @@ def model_gradient(grid, model, grad, model_grid=None):
     if mapping == 'Resistivity':
         rho = np.asarray(model.property_x).reshape(vnC, order='F')
         return out * (-1.0 / rho ** 2)
-    raise NotImplementedError(f"model_gradient: property map {mapping!r} (apply its derivative_chain to -grad).")
+    # the logarithmic maps: the reference's statement (optimize.py:214), the chain factor from the mapped values on the host
+    out = np.array(out, dtype=np.float64, order='F')
+    model.map.derivative_chain(out, np.broadcast_to(np.asarray(model.property_x), vnC))
+    return out
+
+
+def _mapped(mapped):
+    if not isinstance(mapped, (bool, np.bool_)):
+        raise TypeError(f"`mapped` must be True or False; provided: {mapped!r}.")
+    return bool(mapped)
 
 
 def _perturbations(v, vnC):
@@ -357,6 +397,37 @@ class _JacobianBase:
             raise RuntimeError(self._closed)
         return self._held
 
+    # ---- products in the model's own property (``mapped=True``) -----------------------------------------------------------
+    # With sigma_c = backward(p_c) per component and D_c = d sigma_c / d p_c, the Jacobian with respect to p is J_m = J D: a
+    # perturbation of p is multiplied by D_c before it becomes the right-hand side, the cell results of J^T are multiplied by
+    # D_c on the way out (``components=False`` on an anisotropic model: the sum of the three D_c g_c).  D is formed on the host
+    # from the conductivity the DEVICE holds (``DeviceMG.get_sigma``) by multiplication only (``maps._Map.chain_factor``): host
+    # and device agree on sigma bit for bit, no transcendental runs a second time.  Formed at the first mapped product after
+    # ``open()`` / ``set_model()``; ``mapped=False`` (default) never asks for it.
+    _chain = None
+
+    def _chain_factors(self):
+        if self._chain is None:
+            dev = next(iter(self._held)) if isinstance(self._held, solver.FrequencyHandles) else self._held
+            fmap = self.model.map
+            dx = fmap.chain_factor(dev.get_sigma(0))
+            dy = fmap.chain_factor(dev.get_sigma(1)) if self.model.case in (1, 3) else dx
+            dz = fmap.chain_factor(dev.get_sigma(2)) if self.model.case in (2, 3) else dx
+            self._chain = (dx, dy, dz)
+        return self._chain
+
+    def _to_sigma(self, vec):
+        """(v_x, v_y, v_z), F-raveled perturbations of p (entries may be None) -> of sigma."""
+        return tuple(None if v is None else v * d.ravel(order='F') for v, d in zip(vec, self._chain_factors()))
+
+    def _from_sigma(self, g3, components):
+        """The three terms (g_x, g_y, g_z) with respect to sigma -- or, for an isotropic model, their sum -> with respect to p."""
+        d = self._chain_factors()
+        if not isinstance(g3, tuple):
+            return d[0] * g3
+        out = tuple(dc * g for dc, g in zip(d, g3))
+        return out if components else (out[0] + out[1]) + out[2]
+
     def _solve(self, dev, freq, n):
         """Solve the systems 0 .. n-1 of the handle (at ``freq``) for the sources they hold; the fields stay in HBM."""
         _, infos = solver.solve_sources(self.grid, None, None, freq, handle=dev, resident=n, download=False, **self._opts)
@@ -386,8 +457,9 @@ class Jacobian(_JacobianBase):
     * ``jvec(v)``: ``A de = s mu_0 C(v) E``, ``C(v)`` on an edge = 1/4 of the sum of ``V_c v_c`` over its four cells (0 on the PEC
       boundary), then ``J v = P de`` with the receiver operator ``P``.  ``v`` is a conductivity perturbation on this grid: one
       array perturbs sigma_x = sigma_y = sigma_z together, a 3-tuple ``(v_x, v_y, v_z)`` (entries may be None) the directions
-      separately -- for every model case, the operator always carries three eta.  Regridding and the chain rule of another
-      property map stay with the caller (``model_gradient`` shows how).
+      separately -- for every model case, the operator always carries three eta.  ``mapped=True`` (both products): ``v`` and the
+      result are in the model's own property instead (``Model(mapping=...)``: the chain factor per cell, ``_JacobianBase``).
+      Regridding stays with the caller (``model_gradient`` shows how).
     * ``jtvec(w) = Re(J^H w)`` (so that ``sum(v * jtvec(w)) == Re sum(conj(w) * jvec(v))``): ``A lam = P^T conj(w)``, then
       ``-sum_c edges2cellaverages_c(-Re(s mu_0 lam E))`` -- the gradient kernel with the sign flipped; ``components=True`` keeps
       the terms of sigma_x, sigma_y, sigma_z apart.  The gradient of ``1/2 sum W |r|^2`` is ``jtvec(W r)``.
@@ -432,22 +504,43 @@ class Jacobian(_JacobianBase):
             return self
         smu0 = self._spec.smu0
         parts = models.model_parts(self.grid, self.model, raw=True)
-        dev = solver.DeviceMG.from_model_parts(self.grid, *parts, smu0=smu0, device=self.device)
+        dev = solver.DeviceMG.from_model_parts(self.grid, *parts, smu0=smu0, device=self.device, map_code=parts.map_code)
         try:
             if self.nvec > 1:
                 dev.set_batch(self.nvec)
-            dev.select(0)
-            dev.set_source(self.src, smu0, strength=self.strength)
-            self.forward_info = self._solve(dev, self.freq, 1)[0]
-            dev.select(0)
-            self.synthetic = self._data(dev, smu0)
             dev.vec_alloc(1)
-            dev.vec_copy(0, dev.EFIELD)                     # keep the forward field
+            self._forward(dev)
         except BaseException:
             dev.close()
             raise
         self._held = dev
         return self
+
+    def _forward(self, dev):
+        smu0 = self._spec.smu0
+        dev.select(0)
+        dev.set_source(self.src, smu0, strength=self.strength)
+        self.forward_info = self._solve(dev, self.freq, 1)[0]
+        dev.select(0)
+        self.synthetic = self._data(dev, smu0)
+        dev.vec_copy(0, dev.EFIELD)                     # keep the forward field
+        self.info = self._chain = None
+
+    def set_model(self, model):
+        """Another model on the same grid, in the same anisotropy case (any property map), on the open handle:
+        ``DeviceMG.set_model``, the forward solve again into the parked vector, ``synthetic`` and ``forward_info`` anew -- then
+        every product is bit for bit that of a new ``Jacobian`` on ``model``.  Nothing is allocated."""
+        dev = self._require_open()
+        _check_arguments('Jacobian', model, self.adjoint, self.electric, self.receiver_interpolation)
+        dev.set_model(self.grid, model)
+        self.model = model
+        self._forward(dev)
+        return self
+
+    @property
+    def device_bytes(self):
+        """Device memory of the handle, the parked forward field included."""
+        return self._require_open().device_bytes
 
     def close(self):
         if self._held is not None:
@@ -457,10 +550,14 @@ class Jacobian(_JacobianBase):
     _closed = "Jacobian: the handle is closed (use it inside its `with` block, or call open())."
 
     # ---- J v ----------------------------------------------------------------------------------------------------------
-    def jvec(self, v):
-        """``J v``: the data change per unit of the conductivity perturbation ``v`` (see the class docstring)."""
+    def jvec(self, v, mapped=False):
+        """``J v``: the data change per unit of the conductivity perturbation ``v`` (see the class docstring); ``mapped=True``:
+        per unit of a perturbation of the model's own property (``_JacobianBase``)."""
+        mapped = _mapped(mapped)
         vecs, single = _perturbations(v, self._vnC)
         dev = self._require_open()
+        if mapped:
+            vecs = [self._to_sigma(vec) for vec in vecs]
         smu0 = self._spec.smu0
         out = np.empty((len(vecs), self.n_rec), dtype=self._spec.dtype)
         infos = []
@@ -492,9 +589,10 @@ class Jacobian(_JacobianBase):
                                method=self.receiver_interpolation, exact=self.adjoint == 'exact', electric=self.electric):
             dev.vec_scale(dev.SFIELD, 0.0)
 
-    def jtvec(self, w, components=False):
+    def jtvec(self, w, components=False, mapped=False):
         """``J^T w = Re(J^H w)``, a real cell array of shape ``grid.vnC`` (F-ordered); ``components=True``: the three terms
-        ``(g_x, g_y, g_z)`` that belong to sigma_x, sigma_y, sigma_z (their sum is the default result).
+        ``(g_x, g_y, g_z)`` that belong to sigma_x, sigma_y, sigma_z (their sum is the default result).  ``mapped=True``: with
+        respect to the model's own property (``_JacobianBase``).
 
         With ``receiver_interpolation='linear'``, or with ``adjoint='exact'``, this is the exact transpose of ``jvec`` (on the
         12 x 10 x 8 grid below the cubic pair then agrees as well as the linear one, to the accuracy of the solves; the gradient
@@ -504,10 +602,12 @@ class Jacobian(_JacobianBase):
         interpolation which ``jvec`` and the data use, and the two are NOT an adjoint pair: on the 12 x 10 x 8 grid of
         tests/golden/gradient.npz (1.5 Hz, random v and w) ``Re sum(conj(w) J v) = 0.4596`` against ``v . J^T w = 0.1202``, a
         relative gap of 0.74, where the linear pair agrees to 1.9e-8."""
+        mapped = _mapped(mapped)
         ws, single = self._data_vectors(w)
         dev = self._require_open()
         smu0 = self._spec.smu0
         outs, infos = [], []
+        keep, components = components, components or (mapped and self.model.case != 0)
         for g0 in range(0, len(ws), self.nvec):
             group = ws[g0:g0 + self.nvec]
             for b, wv in enumerate(group):
@@ -521,6 +621,9 @@ class Jacobian(_JacobianBase):
                 else:
                     outs.append(-dev.gradient(0, smu0).reshape(self._vnC, order='F'))
         self.info = infos[0] if single else infos
+        if mapped:
+            outs = [self._from_sigma(o, keep) for o in outs]
+            components = keep
         if single:
             return outs[0]
         if components:
@@ -621,26 +724,45 @@ class SurveyJacobian(_JacobianBase):
                     f"{free} bytes are free; use fewer sources or frequencies per SurveyJacobian (frequency shards).")
             for key, dev in devs.items():
                 dev.bvec_alloc(nslots[key])
-            self.synthetic = np.full((ns, nf, self.n_rec), np.nan, dtype=self.dtype)
-            self.forward_info = [[None] * nf for _ in range(ns)]
-            for j, spec in enumerate(self._specs):
-                dev, smu0 = handles.target(spec), spec.smu0
-                for c, (i0, n) in enumerate(self._chunks):
-                    for b in range(n):
-                        dev.select(b)
-                        dev.set_source(self.sources[i0 + b], smu0, strength=self.strength)
-                    infos = self._solve(dev, self.freqs[j], n)
-                    for b in range(n):
-                        self.forward_info[i0 + b][j] = infos[b]
-                        dev.select(b)
-                        self.synthetic[i0 + b, j] = self._data(dev, smu0)
-                    # park the chunk's forward fields (the solve has left all but the last system to finish frozen)
-                    dev.set_mask(_first(n, nb))
-                    dev.bvec_copy(self._slot[j] + c, dev.EFIELD)
+            self._forward(handles)
         except BaseException:
             handles.close()
             raise
         self._held = handles
+        return self
+
+    def _forward(self, handles):
+        """Solve all pairs forward (chunk by chunk), extract the data, park the fields in their batched vectors."""
+        ns, nf, nb = self.n_src, self.n_freq, self._nb
+        self.synthetic = np.full((ns, nf, self.n_rec), np.nan, dtype=self.dtype)
+        self.forward_info = [[None] * nf for _ in range(ns)]
+        for j, spec in enumerate(self._specs):
+            dev, smu0 = handles.target(spec), spec.smu0
+            for c, (i0, n) in enumerate(self._chunks):
+                for b in range(n):
+                    dev.select(b)
+                    dev.set_source(self.sources[i0 + b], smu0, strength=self.strength)
+                infos = self._solve(dev, self.freqs[j], n)
+                for b in range(n):
+                    self.forward_info[i0 + b][j] = infos[b]
+                    dev.select(b)
+                    self.synthetic[i0 + b, j] = self._data(dev, smu0)
+                # park the chunk's forward fields (the solve has left all but the last system to finish frozen)
+                dev.set_mask(_first(n, nb))
+                dev.bvec_copy(self._slot[j] + c, dev.EFIELD)
+        self.info = self.jvec_info = self.partial = self._chain = None
+
+    def set_model(self, model):
+        """Another model on the same grid, in the same anisotropy case (any property map), on the open handles -- what an
+        inversion does every iteration and every trial step: ``FrequencyHandles.set_model`` (the conductivities, eta, coarse
+        models and line factorisations of every handle recomputed in HBM), all pairs solved forward again into the SAME parked
+        vectors, ``synthetic`` and ``forward_info`` anew.  Every product is then bit for bit that of a new ``SurveyJacobian`` on
+        ``model``; no handle, hierarchy, launch graph or parked vector is created (``device_bytes`` stays)."""
+        handles = self._require_open()
+        _check_arguments('Jacobian', model, self.adjoint, self.electric, self.receiver_interpolation)
+        handles.set_model(model)
+        self.model = model
+        self._forward(handles)
         return self
 
     def close(self):
@@ -757,25 +879,49 @@ class SurveyJacobian(_JacobianBase):
         self.partial = partial if components else partial[0]
         return out if components else out[0]
 
-    def jvec(self, v):
-        """``J v`` for all pairs: ``(n_src, n_freq, n_rec)``; ``v`` as for ``Jacobian.jvec`` (one perturbation)."""
+    def _mapped_result(self, partial, components, mapped):
+        """``_result`` -- for ``mapped`` products of the three accumulators, which an anisotropic model needs whatever
+        ``components`` says, then times the chain factors (``_JacobianBase``).  ``partial`` stays what the device summed: the
+        ``G_f`` with respect to conductivity."""
+        if not mapped:
+            return self._result(partial, components)
+        three = components or self.model.case != 0
+        return self._from_sigma(self._result(partial, three), components)
+
+    def jvec(self, v, mapped=False):
+        """``J v`` for all pairs: ``(n_src, n_freq, n_rec)``; ``v`` as for ``Jacobian.jvec`` (one perturbation).  ``mapped=True``:
+        ``v`` perturbs the model's own property."""
+        mapped = _mapped(mapped)
         vec = self._perturbation(v)
+        if mapped:
+            self._require_open()
+            vec = self._to_sigma(vec)
         dd, self.info, _, _ = self._sweep(vec, None, None, False)
         return dd
 
-    def jtvec(self, w, components=False):
+    def jtvec(self, w, components=False, mapped=False):
         """``J^T w = sum over the pairs of Jacobian.jtvec(w[i, j])`` in the defined order: a real cell array of shape ``grid.vnC``
-        (F-ordered), or the three terms ``(g_x, g_y, g_z)`` of sigma_x, sigma_y, sigma_z with ``components=True``."""
+        (F-ordered), or the three terms ``(g_x, g_y, g_z)`` of sigma_x, sigma_y, sigma_z with ``components=True``.
+        ``mapped=True``: with respect to the model's own property, ``D_c g_c`` (``components=False`` on an anisotropic model:
+        their sum)."""
+        mapped = _mapped(mapped)
         w = self._data_array(w, 'w')
-        _, _, partial, self.info = self._sweep(None, w, None, components)
-        return self._result(partial, components)
+        three = components or (mapped and self.model.case != 0)
+        _, _, partial, self.info = self._sweep(None, w, None, three)
+        return self._mapped_result(partial, components, mapped)
 
-    def gauss_newton(self, v, weights=None, components=False):
-        """``J^T W J v``, bit for bit ``jtvec(weights * jvec(v), components)``, the two products run chunk by chunk."""
+    def gauss_newton(self, v, weights=None, components=False, mapped=False):
+        """``J^T W J v``, bit for bit ``jtvec(weights * jvec(v), components)``, the two products run chunk by chunk
+        (``mapped=True``: of both mapped products)."""
+        mapped = _mapped(mapped)
         vec = self._perturbation(v)
         weights = self._weights(weights)
-        _, self.jvec_info, partial, self.info = self._sweep(vec, None, weights, components)
-        return self._result(partial, components)
+        if mapped:
+            self._require_open()
+            vec = self._to_sigma(vec)
+        three = components or (mapped and self.model.case != 0)
+        _, self.jvec_info, partial, self.info = self._sweep(vec, None, weights, three)
+        return self._mapped_result(partial, components, mapped)
 
 
 def jvec(grid, model, src, freq, rec, v, **kwargs):

@@ -68,6 +68,8 @@ class DeviceMG:
         self.nC = int(grid.nC)
         self.device = int(device)
         self._smu0, self._sval, self._eps = smu0, sval, False
+        self._vnC = tuple(int(n) for n in grid.vnC)
+        self._alias = self._zeta = self._epsr = None        # (from_model_parts: what set_model compares a new model with)
         hx, hy, hz = (np.ascontiguousarray(h, dtype=np.float64) for h in grid.h)
         return hx, hy, hz, np.ascontiguousarray(grid.origin, dtype=np.float64)
 
@@ -92,11 +94,13 @@ class DeviceMG:
 
     @classmethod
     def from_model_parts(cls, grid, sigma_x, sigma_y, sigma_z, vol, zeta, resistivity=False, smu0=None, device=0,
-                         epsilon_r=None, sval=None):
+                         epsilon_r=None, sval=None, map_code=None):
         """Handle from ``models.model_parts`` and ``smu0 = s*mu_0``: ``eta = (smu0 * vol) * sigma`` is formed on the device
         with VolumeModel's rounding (``emg3d_mg_create_vs``) -- bit for bit the reference's eta at this and, after
         ``set_smu0``, at every other frequency.  ``resistivity=True``: the three arrays hold resistivities
-        (``models.model_parts(..., raw=True)``), the device takes the reciprocal.  ``epsilon_r`` (``parts.epsilon_r``) with
+        (``models.model_parts(..., raw=True)``), the device takes the reciprocal; ``map_code`` (``parts.map_code``: 0 conductivity,
+        1 resistivity, 2 / 3 log10 / ln conductivity, 4 / 5 log10 / ln resistivity) says the same for all six property maps and
+        goes before ``resistivity``: the device forms ``sigma = backward(p)``.  ``epsilon_r`` (``parts.epsilon_r``) with
         ``sval = s``: ``eta = (smu0 vol) (sigma - s eps_0 eps_r)`` (``emg3d_mg_create_vse``, reference models.py:639-647)."""
         if smu0 is None:
             raise TypeError("from_model_parts: smu0 is required.")
@@ -111,18 +115,20 @@ class DeviceMG:
         handle = ctypes.c_void_p()
         a = complex(smu0)
         self._eps = epsilon_r is not None
+        code = int(bool(resistivity)) if map_code is None else int(map_code)
+        self._alias, self._zeta = (sy is sx, sz is sx), zt
         if self._eps:
-            ep = _cells(epsilon_r)
+            ep = self._epsr = _cells(epsilon_r)
             _lib.check(self._lib.emg3d_mg_create_vse(
                 ctypes.byref(handle), _lib.dtype_code(self.dtype), *(int(n) for n in grid.vnC), _lib.ptr(hx),
                 _lib.ptr(hy), _lib.ptr(hz), _lib.ptr(origin), _lib.ptr(sx), _lib.ptr(sy), _lib.ptr(sz), _lib.ptr(vl),
-                _lib.ptr(zt), _lib.ptr(ep), a.real, a.imag, models.seps0_of(sval), int(bool(resistivity)), int(device)),
+                _lib.ptr(zt), _lib.ptr(ep), a.real, a.imag, models.seps0_of(sval), code, int(device)),
                 "emg3d_mg_create_vse")
         else:
             _lib.check(self._lib.emg3d_mg_create_vs(
                 ctypes.byref(handle), _lib.dtype_code(self.dtype), *(int(n) for n in grid.vnC), _lib.ptr(hx),
                 _lib.ptr(hy), _lib.ptr(hz), _lib.ptr(origin), _lib.ptr(sx), _lib.ptr(sy), _lib.ptr(sz), _lib.ptr(vl),
-                _lib.ptr(zt), a.real, a.imag, int(bool(resistivity)), int(device)), "emg3d_mg_create_vs")
+                _lib.ptr(zt), a.real, a.imag, code, int(device)), "emg3d_mg_create_vs")
         self._h = handle
         return self
 
@@ -131,7 +137,46 @@ class DeviceMG:
         """``from_model_parts`` for ``parts = models.model_parts(grid, model, raw=True)`` and a field / frequency object
         ``spec`` (``smu0``, ``sval``): with or without ``epsilon_r``."""
         return cls.from_model_parts(grid, *parts, smu0=spec.smu0, device=device, epsilon_r=getattr(parts, 'epsilon_r', None),
-                                    sval=spec.sval)
+                                    sval=spec.sval, map_code=getattr(parts, 'map_code', None))
+
+    def _model_arrays(self, grid, parts):
+        """The checks of ``set_model`` -- all of them before anything is uploaded -- and the arrays it uploads."""
+        if tuple(int(n) for n in grid.vnC) != self._vnC:
+            raise ValueError(f"set_model: the handle has {self._vnC} cells, the model's grid {tuple(grid.vnC)}.")
+        px, py, pz = parts[:3]
+        if px.shape != self._vnC:
+            raise ValueError(f"set_model: the handle has {self._vnC} cells, the model {px.shape}.")
+        if self._alias is not None:         # (a handle of another kind: the library refuses it)
+            if (py is px, pz is px) != self._alias:
+                raise ValueError("set_model: the anisotropy case of a handle is fixed at creation; the model has another.")
+            ep = getattr(parts, 'epsilon_r', None)
+            if (ep is not None) != self._eps:
+                raise ValueError("set_model: the handle was created " + ("with" if self._eps else "without") + " epsilon_r.")
+            if not np.array_equal(_cells(parts[4]), self._zeta) or (self._eps and not np.array_equal(_cells(ep), self._epsr)):
+                raise ValueError("set_model: mu_r and epsilon_r stay as the handle was created with them; the model's differ.")
+        sx = _cells(px)
+        return sx, (sx if py is px else _cells(py)), (sx if pz is px else _cells(pz))
+
+    def set_model(self, grid, model):
+        """Another model on the same grid (``emg3d_mg_set_model``; ``from_model`` / ``from_model_parts`` handles): its property
+        arrays go to the device as they are, which forms the conductivities with the model's map and recomputes eta, the coarse
+        models and every cached line factorisation at the frequency the handle stands at -- bit for bit a handle created from
+        ``model``; hierarchies, work buffers, launch graphs, workspace vectors and accumulators stay, for any batch size.  The
+        anisotropy case, ``mu_r`` and ``epsilon_r`` are those of the handle's first model (``ValueError`` otherwise, as for
+        a grid of another size, before anything is uploaded); the map may change."""
+        self._set_parts(grid, models.model_parts(grid, model, raw=True))
+
+    def _set_parts(self, grid, parts):
+        sx, sy, sz = self._model_arrays(grid, parts)
+        _lib.check(self._lib.emg3d_mg_set_model(self._h, int(parts.map_code), _lib.ptr(sx), _lib.ptr(sy), _lib.ptr(sz)),
+                   "emg3d_mg_set_model")
+
+    def get_sigma(self, comp=0):
+        """The conductivity of component ``comp`` (0, 1, 2) as the device holds it (``emg3d_mg_get_sigma``), shape ``vnC``,
+        F-ordered: for the logarithmic maps the device's ``exp10`` / ``exp`` of the model's property."""
+        out = np.empty(self.nC)
+        _lib.check(self._lib.emg3d_mg_get_sigma(self._h, int(comp), _lib.ptr(out)), "emg3d_mg_get_sigma")
+        return out.reshape(self._vnC, order='F')
 
     def set_smu0(self, smu0, sval=None):
         """Re-target a ``from_sigma_volume`` handle to another frequency (``emg3d_mg_set_smu0``): eta, the coarse models,
@@ -681,6 +726,16 @@ class FrequencyHandles:
         if self.bvecs:
             dev.bvec_alloc(self.bvecs)
         return dev
+
+    def set_model(self, model):
+        """Re-target every handle to ``model`` (``DeviceMG.set_model``; checked against all of them before the first upload);
+        handles created later are created from it."""
+        parts = models.model_parts(self.grid, model, raw=True)
+        for dev in self._handles.values():
+            dev._model_arrays(self.grid, parts)
+        for dev in self._handles.values():
+            dev._set_parts(self.grid, parts)
+        self.parts = parts
 
     def __iter__(self):
         return iter(self._handles.values())

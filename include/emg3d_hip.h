@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 110
+#define EMG3D_HIP_ABI_VERSION 111
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -155,19 +155,28 @@ int emg3d_mg_create_sv(emg3d_mg_t** out, int dtype, int64_t nx, int64_t ny, int6
 /* The same with the conductivities and the cell volumes as separate arrays: eta = (s mu_0 V) sigma is formed on the device
  * exactly as VolumeModel rounds it (reference models.py:631-658, `(smu0 * vol) * sigma`), so that a handle -- also one
  * re-targeted with emg3d_mg_set_smu0 -- holds bit for bit the eta of the reference at every frequency.  s mu_0 must be
- * purely imaginary (dtype 1) or real (dtype 0): -2 otherwise.  resistivity != 0: the sigma arrays hold resistivities
- * (Model's 'Resistivity' mapping) and the device takes the reciprocal (an IEEE division: Model.conductivity's bits).  */
+ * purely imaginary (dtype 1) or real (dtype 0): -2 otherwise.
+ * `map`: the property map of the three arrays, which hold the model's own parameter p; the device forms sigma = backward(p)
+ * (k_sigma_of_map, reference emg3d/maps.py:319-448):
+ *     0 conductivity        sigma = p          (the arrays are taken as they are)
+ *     1 resistivity         sigma = 1 / p      (an IEEE division: Model.conductivity's bits)
+ *     2 log10 conductivity  sigma = 10^p
+ *     3 ln conductivity     sigma = e^p
+ *     4 log10 resistivity   sigma = 10^-p
+ *     5 ln resistivity      sigma = e^-p
+ * 2-5 use the device's exp10 / exp, within a few ulp of NumPy's; emg3d_mg_get_sigma returns what the device
+ * holds.  Any other code: -2.                                                                                            */
 int emg3d_mg_create_vs(emg3d_mg_t** out, int dtype, int64_t nx, int64_t ny, int64_t nz, const double* hx,
                        const double* hy, const double* hz, const double* origin, const double* sigma_x,
                        const double* sigma_y, const double* sigma_z, const double* vol, const double* zeta,
-                       double smu0_re, double smu0_im, int resistivity, int device);
+                       double smu0_re, double smu0_im, int map, int device);
 /* ... and with displacement currents (Model.epsilon_r): eta = s mu_0 V (sigma - s eps_0 eps_r), reference
  * models.py:639-647, formed on the device as NumPy rounds it.  seps0 = s eps_0 (dtype 0) resp. Im(s) eps_0 (dtype 1: s is
  * purely imaginary, and so is s mu_0 = i smu0_im).  Another frequency: emg3d_mg_set_smu0_eps.                        */
 int emg3d_mg_create_vse(emg3d_mg_t** out, int dtype, int64_t nx, int64_t ny, int64_t nz, const double* hx,
                         const double* hy, const double* hz, const double* origin, const double* sigma_x,
                         const double* sigma_y, const double* sigma_z, const double* vol, const double* zeta,
-                        const double* epsilon_r, double smu0_re, double smu0_im, double seps0, int resistivity, int device);
+                        const double* epsilon_r, double smu0_re, double smu0_im, double seps0, int map, int device);
 void emg3d_mg_destroy(emg3d_mg_t* mg);
 
 /* Cycle parameters = the MGParameters fields used inside solver.multigrid
@@ -404,6 +413,20 @@ int emg3d_mg_smooth(emg3d_mg_t* mg, int nu, int lr_dir);
 int emg3d_mg_set_smu0(emg3d_mg_t* mg, double smu0_re, double smu0_im);
 /* The same for handles made by emg3d_mg_create_vse (-7 for any other; emg3d_mg_set_smu0 answers -7 for these). */
 int emg3d_mg_set_smu0_eps(emg3d_mg_t* mg, double smu0_re, double smu0_im, double seps0);
+
+/* Another MODEL on the same handle (handles made by emg3d_mg_create_vs / emg3d_mg_create_vse; -7 for any other, as
+ * emg3d_mg_set_smu0 answers for a handle it cannot serve): p_x, p_y, p_z hold the property of a model on the same grid in
+ * map `map` (codes: emg3d_mg_create_vs); NULL or p_x for p_y / p_z means "aliases p_x", and the pattern must be the one the
+ * handle was created with (-2 otherwise: the anisotropy case of a handle is fixed; -2 too for an unknown map code).  The
+ * arrays are uploaded into the conductivity buffers the handle has, sigma = backward(p) is formed there, then everything
+ * emg3d_mg_set_smu0 recomputes is recomputed at the frequency the handle stands at (with its s eps_0 on epsilon_r
+ * handles): bit for bit a handle created from that model.  No buffer moves, so captured launch graphs, the level-0 placement,
+ * workspace vectors (emg3d_mg_vec_*, emg3d_mg_bvec_*) and accumulators stay; any batch size.  The host arrays may be freed
+ * when the call returns.  A failed upload leaves the handle broken (every later call: hipErrorOutOfMemory).            */
+int emg3d_mg_set_model(emg3d_mg_t* mg, int map, const double* p_x, const double* p_y, const double* p_z);
+/* The conductivity of component comp (0, 1, 2; an aliased component gives sigma_x) as the device holds it: nC doubles,
+ * F-ordered.  Same handles as emg3d_mg_set_model (-7 otherwise).                                                       */
+int emg3d_mg_get_sigma(emg3d_mg_t* mg, int comp, double* out);
 
 /* Entry of solver.multigrid (solver.py:471-492): the reference fixes the cycmax of level 0 when the function is
  * entered, from var.clevel[var.sc_dir] of THAT moment, and keeps it for all cycles of the call although sc_dir rotates
