@@ -38,6 +38,10 @@ Outputs (np.savez_compressed):
   solves_entry.npz                      small odd grids where the first sc_dir has clevel 0 (level 0's cycmax is
                                         fixed on entry of solver.multigrid)
   (--big) solves_32.npz                 32^3 config-C1 plumbing case
+
+Written by a generator of its own (same import of the reference):
+  depth.npz                             make_depth_golden.py: every smoothing call (level, cycmax, grid, full-precision residual
+                                        norm) of three W- / F-cycles on hierarchies of up to seven levels
 """
 import os
 import sys
