@@ -22,7 +22,7 @@ c_double = ctypes.c_double
 c_dp = ctypes.POINTER(ctypes.c_double)
 
 # include/emg3d_hip.h: EMG3D_HIP_ABI_VERSION -- a library built from another header version is refused at load
-ABI_VERSION = 111
+ABI_VERSION = 112
 
 # name -> (restype, argtypes); mirrors include/emg3d_hip.h one to one.
 SIGNATURES = {
@@ -99,6 +99,13 @@ SIGNATURES = {
     "emg3d_volume_average_weights": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "emg3d_volume_average": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp,
                                      c_vp, c_vp, c_vp]),
+    "emg3d_volume_average_old_offsets": (c_int, [c_vp, c_i64, c_i64, c_vp]),
+    "emg3d_volume_average_adjoint": (c_int, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                             c_vp, c_vp]),
+    "emg3d_mg_set_model_grid": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "emg3d_mg_set_regrid_factors": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "emg3d_mg_grad_acc_get_model": (c_int, [c_vp, c_vp]),
+    "emg3d_mg_grad_acc3_get_model": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "emg3d_interp3d_grid": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                                     c_vp, c_int, c_int, c_double, c_double, c_vp]),
     "emg3d_mg_set_batch": (c_int, [c_vp, c_int]),

@@ -1116,6 +1116,79 @@ int emg3d_volume_average(int dtype, int64_t nx, int64_t ny, int64_t nz, const do
                  : volume_average_host<double>(n, e, (const double*)values, m, ne, (double*)new_values, new_vol);
 }
 
+int emg3d_volume_average_old_offsets(const int64_t* idx_in, int64_t nseg, int64_t n, int64_t* iptr) {
+    if (nseg < 0 || n < 1 || !idx_in || !iptr) return -2;
+    for (int64_t s = 0; s < nseg; ++s)
+        if (idx_in[s] < 0 || idx_in[s] >= n || (s > 0 && idx_in[s] < idx_in[s - 1])) return -2;
+    old_cell_offsets_host(idx_in, nseg, n, iptr);
+    return 0;
+}
+
+int emg3d_volume_average_adjoint(int64_t nx, int64_t ny, int64_t nz, const double* edges_x, const double* edges_y,
+                                 const double* edges_z, int64_t mx, int64_t my, int64_t mz, const double* new_edges_x,
+                                 const double* new_edges_y, const double* new_edges_z, const double* y, const double* new_vol,
+                                 double* out) {
+    if (nx < 1 || ny < 1 || nz < 1 || mx < 1 || my < 1 || mz < 1 || !edges_x || !edges_y || !edges_z || !new_edges_x ||
+        !new_edges_y || !new_edges_z || !y || !new_vol || !out) return -2;
+    const i64 n[3] = {nx, ny, nz}, m[3] = {mx, my, mz};
+    const double* e[3] = {edges_x, edges_y, edges_z};
+    const double* ne[3] = {new_edges_x, new_edges_y, new_edges_z};
+    return volume_average_adjoint_host(n, e, m, ne, y, new_vol, out);
+}
+
+int emg3d_mg_set_model_grid(emg3d_mg_t* mg, int64_t nx, int64_t ny, int64_t nz, const double* edges_x, const double* edges_y,
+                            const double* edges_z) {
+    if (!mg || nx < 1 || ny < 1 || nz < 1 || !edges_x || !edges_y || !edges_z) return -2;
+    const i64 n[3] = {nx, ny, nz};
+    const double* e[3] = {edges_x, edges_y, edges_z};
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        const int st = m->set_model_grid(n, e);
+        return st ? st : finish(m);
+    });
+}
+
+int emg3d_mg_set_regrid_factors(emg3d_mg_t* mg, const double* F_x, const double* F_y, const double* F_z, const double* Q_x,
+                                const double* Q_y, const double* Q_z) {
+    if (!mg) return -2;
+    const double* F[3] = {F_x, F_y, F_z};
+    const double* Q[3] = {Q_x, Q_y, Q_z};
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        const int st = m->set_regrid_factors(F, Q);
+        return st ? st : finish(m);
+    });
+}
+
+int emg3d_mg_grad_acc_get_model(emg3d_mg_t* mg, double* out) {
+    if (!mg || !out) return -2;
+    DISPATCH(mg, {
+        if (!m->mgl.set || !m->mgl.factors) return -7;
+        HIP_TRY(hipSetDevice(m->device));
+        if (!m->grad_acc) { const int st = m->grad_acc_reset(); if (st) return st; }
+        const int st = m->regrid_acc(m->grad_acc, 1);
+        if (st) return st;
+        HIP_TRY(m->d2h(out, m->mgl.res, (size_t)m->mgl.nM * sizeof(double)));
+        return finish(m);
+    });
+}
+
+int emg3d_mg_grad_acc3_get_model(emg3d_mg_t* mg, double* out_x, double* out_y, double* out_z) {
+    if (!mg || !out_x || !out_y || !out_z) return -2;
+    DISPATCH(mg, {
+        if (!m->mgl.set || !m->mgl.factors) return -7;
+        HIP_TRY(hipSetDevice(m->device));
+        if (!m->grad_acc3) { const int st = m->grad_acc3_reset(); if (st) return st; }
+        const int st = m->regrid_acc(m->grad_acc3, 3);
+        if (st) return st;
+        const i64 n = m->mgl.nM;
+        HIP_TRY(m->d2h(out_x, m->mgl.res, (size_t)n * sizeof(double)));
+        HIP_TRY(m->d2h(out_y, m->mgl.res + n, (size_t)n * sizeof(double)));
+        HIP_TRY(m->d2h(out_z, m->mgl.res + 2 * n, (size_t)n * sizeof(double)));
+        return finish(m);
+    });
+}
+
 int emg3d_interp3d_grid(int dtype, int64_t nx, int64_t ny, int64_t nz, const double* px, const double* py, const double* pz,
                         const void* values, int64_t mx, const double* xi_x, int64_t my, const double* xi_y, int64_t mz,
                         const double* xi_z, int method, int has_fill, double fill_value, double cval, void* out) {

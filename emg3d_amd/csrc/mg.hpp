@@ -22,6 +22,7 @@
 #include "smooth.hpp"
 #include "stencil.hpp"
 #include "gradient.hpp"        // k_gradient_acc (grad_acc_add)
+#include "regrid.hpp"          // k_volume_average_adjoint (grad_acc_get_model)
 #include "smooth_qpl.hpp"
 #include "smooth_qc.hpp"
 #include "smooth_thm.hpp"
@@ -972,6 +973,90 @@ struct MG : emg3d_mg {
         MG_LAUNCH((k_gradient_acc<T, true>), dim3(blocks), dim3(256), 0, stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd, bwd, L.nE, nsys,
                   bits, sr, si, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], grad_acc3, grad_acc3 + L.nCells,
                   grad_acc3 + 2 * L.nCells);
+        check_launch();
+        return err;
+    }
+
+    // ------------------------------------------- model grid (emg3d_mg_set_model_grid, _set_regrid_factors, _grad_acc(3)_get_model)
+    // The model of an inversion lives on a coarser grid and reaches this one by volume averaging (regrid.hpp: A); the accumulators
+    // go back to it as Q_c (.) A^T (F_c (.) acc_c), so that only nM-sized arrays cross PCIe.  The handle keeps the segment tables
+    // of the three axes with both sets of offsets, the factors (F_c: nC doubles, Q_c: nM doubles per direction; directions given
+    // with the pointer of direction x share its copy), nC doubles of scratch for t and 3 nM doubles for the results: all counted in
+    // `bytes`, freed with the handle.  The tables are allocated for the most segments an axis can have, so that another model grid
+    // of the same size (and other factors with the same sharing) replace the first in place: `bytes` stays.
+    struct ModelGridLink {
+        bool set = false, factors = false;
+        i64 n[3] = {0, 0, 0}, nM = 0;
+        double* w[3] = {nullptr, nullptr, nullptr};
+        i64 *in[3] = {nullptr, nullptr, nullptr}, *out[3] = {nullptr, nullptr, nullptr}, *ptr[3] = {nullptr, nullptr, nullptr},
+            *iptr[3] = {nullptr, nullptr, nullptr};
+        double *F[3] = {nullptr, nullptr, nullptr}, *Q[3] = {nullptr, nullptr, nullptr};
+        double *t = nullptr, *res = nullptr;
+    } mgl;
+    int set_model_grid(const i64 n[3], const double* const edges[3]) {
+        Level<T>& L = *lv0;
+        if (mgl.set && (n[0] != mgl.n[0] || n[1] != mgl.n[1] || n[2] != mgl.n[2])) return -2;
+        const double* nodes[3] = {L.nodes[0].data(), L.nodes[1].data(), L.nodes[2].data()};
+        VolAvgTables tb;
+        tb.build(n, edges, L.nC, nodes);
+        if (!mgl.set) {
+            for (int a = 0; a < 3; ++a) {
+                const i64 cap = n[a] + L.nC[a] + 1;
+                mgl.w[a] = dalloc<double>(cap); mgl.in[a] = dalloc<i64>(cap); mgl.out[a] = dalloc<i64>(cap);
+                mgl.ptr[a] = dalloc<i64>(L.nC[a] + 1); mgl.iptr[a] = dalloc<i64>(n[a] + 1);
+                mgl.n[a] = n[a];
+            }
+            mgl.nM = n[0] * n[1] * n[2];
+            mgl.t = dalloc<double>(L.nCells);
+            mgl.res = dalloc<double>(3 * mgl.nM);
+            if (broken) return err ? err : (int)hipErrorOutOfMemory;
+            mgl.set = true;
+        }
+        for (int a = 0; a < 3; ++a) {
+            hipError_t st = h2d(mgl.w[a], tb.w[a].data(), (size_t)tb.ns[a] * sizeof(double));
+            if (st == hipSuccess) st = h2d(mgl.in[a], tb.in[a].data(), (size_t)tb.ns[a] * sizeof(i64));
+            if (st == hipSuccess) st = h2d(mgl.out[a], tb.out[a].data(), (size_t)tb.ns[a] * sizeof(i64));
+            if (st == hipSuccess) st = h2d(mgl.ptr[a], tb.ptr[a].data(), (size_t)(L.nC[a] + 1) * sizeof(i64));
+            if (st == hipSuccess) st = h2d(mgl.iptr[a], tb.iptr[a].data(), (size_t)(n[a] + 1) * sizeof(i64));
+            if (st != hipSuccess) { mgl.set = false; return (int)st; }      // (half-written tables are not used)
+        }
+        return 0;
+    }
+    int set_regrid_factors(const double* const F[3], const double* const Q[3]) {
+        if (!mgl.set) return -7;
+        if (!F[0] || !Q[0]) return -2;
+        const bool have = mgl.F[0] != nullptr;          // (allocated by an earlier call, whether or not its uploads succeeded)
+        for (int c = 1; c < 3; ++c) {
+            if (!F[c] || !Q[c]) return -2;
+            if (have && ((F[c] == F[0]) != (mgl.F[c] == mgl.F[0]) || (Q[c] == Q[0]) != (mgl.Q[c] == mgl.Q[0]))) return -2;
+        }
+        const i64 nC = lv0->nCells;
+        if (!have) {
+            for (int c = 0; c < 3; ++c) {
+                mgl.F[c] = (c > 0 && F[c] == F[0]) ? mgl.F[0] : dalloc<double>(nC);
+                mgl.Q[c] = (c > 0 && Q[c] == Q[0]) ? mgl.Q[0] : dalloc<double>(mgl.nM);
+            }
+            if (broken) return err ? err : (int)hipErrorOutOfMemory;
+        }
+        mgl.factors = false;
+        for (int c = 0; c < 3; ++c) {
+            hipError_t st = hipSuccess;
+            if (c == 0 || mgl.F[c] != mgl.F[0]) st = h2d(mgl.F[c], F[c], (size_t)nC * sizeof(double));
+            if (st == hipSuccess && (c == 0 || mgl.Q[c] != mgl.Q[0])) st = h2d(mgl.Q[c], Q[c], (size_t)mgl.nM * sizeof(double));
+            if (st != hipSuccess) return (int)st;
+        }
+        mgl.factors = true;
+        return 0;
+    }
+    // res[k] = Q_k (.) A^T (F_k (.) acc[k]) for k = 0 .. ndir-1 (acc: ndir accumulators of nC doubles, left as they are)
+    int regrid_acc(const double* acc, int ndir) {
+        if (!mgl.set || !mgl.factors) return -7;
+        Level<T>& L = *lv0;
+        VolAvgAdjAxes ax;
+        for (int a = 0; a < 3; ++a) { ax.iptr[a] = mgl.iptr[a]; ax.out[a] = mgl.out[a]; ax.w[a] = mgl.w[a]; }
+        for (int k = 0; k < ndir && !broken; ++k)
+            volume_average_adjoint_launch(stream, mgl.res + k * mgl.nM, mgl.t, acc + k * L.nCells, mgl.F[k], mgl.Q[k], nullptr,
+                                          (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], mgl.n, L.nC, ax);
         check_launch();
         return err;
     }

@@ -132,6 +132,106 @@ __global__ __launch_bounds__(EMG_RGD_BLOCK) void k_volume_average(T* out, const 
     out[o] = div_vol<T>(acc, vol[o]);
 }
 
+// ---- the transpose of volume averaging (maps.volume_average_adjoint, emg3d_mg_grad_acc(3)_get_model) ------------------------
+// With A[o, i] = (sum of the segment weights (w_z w_y) w_x of new cell o that lie in old cell i) / vol[o] -- what
+// k_volume_average applies to a zero new array --, out = Q (.) A^T (F (.) y): y, F, vol on the NEW grid (m cells), out and Q on
+// the OLD grid (n cells).  The segments of an axis come out in ascending coordinate order, so they are sorted by old cell too:
+// old cell i owns the contiguous range [iptr[i], iptr[i+1]) (old_cell_offsets_host).  Two launches: k_regrid_scale streams
+// t[o] = (F[o] y[o]) / vol[o] into scratch (a term of the sum then costs one load, not three), k_volume_average_adjoint is a
+// gather, one thread per OLD cell, x fastest (the writes coalesce; no atomics, the result does not depend on the schedule):
+// out[i] = Q[i] * sum_sz sum_sy sum_sx ((w_z w_y) w_x) t[o], z outermost, segments ascending, from 0, nothing fused.  An old cell
+// without a segment (the old grid reaches beyond the new one) gets an exact 0.  Bytes: y, F read once, t written and read once
+// (neighbouring threads read neighbouring new cells), Q read and out written once.  double only: gradients are real.
+struct VolAvgAdjAxes {
+    const i64* iptr[3];         // per axis: segment offsets of the OLD cells (n + 1)
+    const i64* out[3];          // per axis: new cell of each segment
+    const double* w[3];         // per axis: segment length
+};
+
+// x1 cells n, ns segments with old cells in[] (ascending): iptr[0 .. n], old cell i owns segments [iptr[i], iptr[i+1])
+inline void old_cell_offsets_host(const i64* in, i64 ns, i64 n, i64* iptr) {
+    for (i64 i = 0; i <= n; ++i) iptr[i] = 0;
+    for (i64 s = 0; s < ns; ++s) ++iptr[in[s] + 1];
+    for (i64 i = 0; i < n; ++i) iptr[i + 1] += iptr[i];
+}
+
+// t[o] = (F[o] y[o]) / vol[o]; F == nullptr: F = 1; vol == nullptr: vol = (h0 h1) h2, the product of meshes.cell_volumes
+__global__ __launch_bounds__(EMG_RGD_BLOCK) void k_regrid_scale(double* t, const double* y, const double* F, const double* vol,
+                                                                const double* h0, const double* h1, const double* h2, i64 mx,
+                                                                i64 my, i64 mtot) {
+#pragma clang fp contract(off)
+    const i64 o = (i64)blockIdx.x * EMG_RGD_BLOCK + threadIdx.x;
+    if (o >= mtot) return;
+    double v;
+    if (vol) v = vol[o];
+    else {
+        const i64 ox = o % mx, oyz = o / mx;
+        v = (h0[ox] * h1[oyz % my]) * h2[oyz / my];
+    }
+    const double fy = F ? F[o] * y[o] : y[o];
+    t[o] = fy / v;
+}
+
+__global__ __launch_bounds__(EMG_RGD_BLOCK) void k_volume_average_adjoint(double* out, const double* t, const double* Q, i64 nx,
+                                                                          i64 ny, i64 mx, i64 my, i64 ntot, VolAvgAdjAxes ax) {
+#pragma clang fp contract(off)      // the arithmetic is part of the contract: the NumPy restatement does not fuse either
+    const i64 i = (i64)blockIdx.x * EMG_RGD_BLOCK + threadIdx.x;
+    if (i >= ntot) return;
+    const i64 ix = i % nx, iyz = i / nx;
+    const i64 iy = iyz % ny, iz = iyz / ny;
+    const i64 x0 = ax.iptr[0][ix], x1 = ax.iptr[0][ix + 1];
+    const i64 y0 = ax.iptr[1][iy], y1 = ax.iptr[1][iy + 1];
+    const i64 z0 = ax.iptr[2][iz], z1 = ax.iptr[2][iz + 1];
+    const i64 mxy = mx * my;
+    double acc = 0.0;
+    if (x1 - x0 <= EMG_RGD_XSEG) {
+        // the thread's x segments in registers, the loads of a row issued together, then summed in the same order
+        const int cx = (int)(x1 - x0);
+        double wx[EMG_RGD_XSEG];
+        i64 ox[EMG_RGD_XSEG];
+#pragma unroll
+        for (int k = 0; k < EMG_RGD_XSEG; ++k) {
+            wx[k] = k < cx ? ax.w[0][x0 + k] : 0.0;
+            ox[k] = k < cx ? ax.out[0][x0 + k] : 0;
+        }
+        for (i64 sz = z0; sz < z1; ++sz) {
+            const double wz = ax.w[2][sz];
+            const i64 bz = ax.out[2][sz] * mxy;
+            for (i64 sy = y0; sy < y1; ++sy) {
+                const double wzy = wz * ax.w[1][sy];
+                const double* row = t + bz + ax.out[1][sy] * mx;
+                double r[EMG_RGD_XSEG];
+#pragma unroll
+                for (int k = 0; k < EMG_RGD_XSEG; ++k) if (k < cx) r[k] = row[ox[k]];
+#pragma unroll
+                for (int k = 0; k < EMG_RGD_XSEG; ++k) if (k < cx) add_weighted(acc, wzy * wx[k], r[k]);
+            }
+        }
+    } else {
+        for (i64 sz = z0; sz < z1; ++sz) {
+            const double wz = ax.w[2][sz];
+            const i64 bz = ax.out[2][sz] * mxy;
+            for (i64 sy = y0; sy < y1; ++sy) {
+                const double wzy = wz * ax.w[1][sy];
+                const double* row = t + bz + ax.out[1][sy] * mx;
+                for (i64 sx = x0; sx < x1; ++sx) add_weighted(acc, wzy * ax.w[0][sx], row[ax.out[0][sx]]);
+            }
+        }
+    }
+    out[i] = Q ? Q[i] * acc : acc;
+}
+
+// the two launches on `stream`: out (n cells) = Q (.) A^T (F (.) y), t = scratch of m cells
+inline void volume_average_adjoint_launch(hipStream_t stream, double* out, double* t, const double* y, const double* F,
+                                          const double* Q, const double* vol, const double* h0, const double* h1, const double* h2,
+                                          const i64 n[3], const i64 m[3], const VolAvgAdjAxes& ax) {
+    const i64 ntot = n[0] * n[1] * n[2], mtot = m[0] * m[1] * m[2];
+    hipLaunchKernelGGL(k_regrid_scale, dim3((unsigned)((mtot + EMG_RGD_BLOCK - 1) / EMG_RGD_BLOCK)), dim3(EMG_RGD_BLOCK), 0, stream,
+                       t, y, F, vol, h0, h1, h2, m[0], m[1], mtot);
+    hipLaunchKernelGGL(k_volume_average_adjoint, dim3((unsigned)((ntot + EMG_RGD_BLOCK - 1) / EMG_RGD_BLOCK)), dim3(EMG_RGD_BLOCK), 0,
+                       stream, out, (const double*)t, Q, n[0], n[1], m[0], m[1], ntot, ax);
+}
+
 // Tensor-product targets: point r = i + mx (j + my k) at (cx[i], cy[j], cz[k]) (index coordinates of `coef`).
 template <class T>
 __global__ __launch_bounds__(EMG_RCV_BLOCK) void k_spline_eval_grid(T* out, const T* coef, i64 n0, i64 n1, i64 n2, const double* cx,
@@ -206,6 +306,57 @@ int volume_average_host(const i64 n[3], const double* const edges[3], const T* v
                        (const double*)dvol, n[0], n[1], m[0], m[1], mtot, ax);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(new_values, dout, (size_t)mtot * sizeof(T), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The segments of the three axes with both sets of offsets: new-cell (ptr, k_volume_average) and old-cell (iptr, the adjoint).
+struct VolAvgTables {
+    std::vector<double> w[3];
+    std::vector<i64> in[3], out[3], ptr[3], iptr[3];
+    i64 ns[3];
+    void build(const i64 n[3], const double* const edges[3], const i64 m[3], const double* const new_edges[3]) {
+        for (int a = 0; a < 3; ++a) {
+            const i64 cap = n[a] + m[a] + 1;
+            w[a].resize(cap); in[a].resize(cap); out[a].resize(cap); ptr[a].resize(m[a] + 1); iptr[a].resize(n[a] + 1);
+            ns[a] = volume_average_weights_host(edges[a], n[a] + 1, new_edges[a], m[a] + 1, w[a].data(), in[a].data(),
+                                                out[a].data(), ptr[a].data());
+            old_cell_offsets_host(in[a].data(), ns[a], n[a], iptr[a].data());
+        }
+    }
+};
+
+// out = A^T y of host arrays (F-ordered): y and new_vol on the new grid (m cells), out on the old grid (n cells).
+inline int volume_average_adjoint_host(const i64 n[3], const double* const edges[3], const i64 m[3],
+                                       const double* const new_edges[3], const double* y, const double* new_vol, double* out) {
+    for (int a = 0; a < 3; ++a) if (n[a] < 1 || m[a] < 1) return -2;
+    VolAvgTables tb;
+    tb.build(n, edges, m, new_edges);
+    const i64 tot = n[0] * n[1] * n[2], mtot = m[0] * m[1] * m[2];
+    // one block: [y | new_vol | t | out | per axis: iptr, out, w] (every part a multiple of 8 bytes)
+    size_t nb = (size_t)(3 * mtot + tot) * sizeof(double);
+    for (int a = 0; a < 3; ++a) nb += (size_t)(n[a] + 1) * sizeof(i64) + (size_t)tb.ns[a] * (sizeof(i64) + sizeof(double));
+    DevBlock blk;
+    HIP_TRY(blk.alloc(nb));
+    char* p = blk.get<char>();
+    double* dy = (double*)p;    p += (size_t)mtot * sizeof(double);
+    double* dvol = (double*)p;  p += (size_t)mtot * sizeof(double);
+    double* dt = (double*)p;    p += (size_t)mtot * sizeof(double);
+    double* dout = (double*)p;  p += (size_t)tot * sizeof(double);
+    VolAvgAdjAxes ax;
+    for (int a = 0; a < 3; ++a) {
+        i64* dp = (i64*)p;      p += (size_t)(n[a] + 1) * sizeof(i64);
+        i64* dn = (i64*)p;      p += (size_t)tb.ns[a] * sizeof(i64);
+        double* dw = (double*)p; p += (size_t)tb.ns[a] * sizeof(double);
+        HIP_TRY(hipMemcpy(dp, tb.iptr[a].data(), (size_t)(n[a] + 1) * sizeof(i64), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dn, tb.out[a].data(), (size_t)tb.ns[a] * sizeof(i64), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dw, tb.w[a].data(), (size_t)tb.ns[a] * sizeof(double), hipMemcpyHostToDevice));
+        ax.iptr[a] = dp; ax.out[a] = dn; ax.w[a] = dw;
+    }
+    HIP_TRY(hipMemcpy(dy, y, (size_t)mtot * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dvol, new_vol, (size_t)mtot * sizeof(double), hipMemcpyHostToDevice));
+    volume_average_adjoint_launch(nullptr, dout, dt, dy, nullptr, nullptr, dvol, nullptr, nullptr, nullptr, n, m, ax);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, dout, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 

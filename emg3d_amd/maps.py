@@ -188,6 +188,73 @@ def volume_average(edges_x, edges_y, edges_z, values, new_edges_x, new_edges_y, 
     new_values[...] = out.reshape(m, order='F')
 
 
+def _volume_average_old_offsets(ix1, n):
+    """The old-cell offsets of one axis' segments (``emg3d_volume_average_old_offsets``, host work, no device): ``ix1`` from
+    ``_volume_average_weights`` is ascending, old cell ``i`` of ``n`` owns segments ``iptr[i]:iptr[i+1]`` -- what the transpose of
+    volume averaging gathers with."""
+    ix1 = np.ascontiguousarray(ix1, dtype=np.int64)
+    iptr = np.empty(int(n) + 1, dtype=np.int64)
+    _lib.check(_lib.load().emg3d_volume_average_old_offsets(_lib.ptr(ix1), ix1.size, int(n), _lib.ptr(iptr)),
+               "emg3d_volume_average_old_offsets")
+    return iptr
+
+
+def volume_average_adjoint(edges_x, edges_y, edges_z, new_edges_x, new_edges_y, new_edges_z, y, new_vol):
+    """The exact transpose of :func:`volume_average`: with ``A`` the matrix ``volume_average`` applies to a zero ``new_values``
+    (``A[o, i]`` = the segment weights of new cell ``o`` that lie in old cell ``i``, over ``new_vol[o]``), returns ``A^T y`` --
+    ``y`` and ``new_vol`` real, on the new grid, the result (float64, F-ordered) on the old grid; ``sum(A v * y) == sum(v *
+    A^T y)``.  On the device (``emg3d_volume_average_adjoint``: one thread per old cell gathers ``y / new_vol`` over its
+    segments in a fixed order; no atomics, results repeat bit for bit).  An old cell that no part of the new grid covers gets
+    an exact 0.  The reference has no such function: it maps gradients to the model grid by cubic interpolation
+    (``optimize.model_gradient``), which is not the derivative of what ``Model.interpolate2grid`` does."""
+    lib = _lib.load()
+    if np.iscomplexobj(y):
+        raise TypeError("volume_average_adjoint: `y` must be real (gradients are real in both domains).")
+    edges = [np.ascontiguousarray(e, dtype=np.float64) for e in (edges_x, edges_y, edges_z)]
+    new_edges = [np.ascontiguousarray(e, dtype=np.float64) for e in (new_edges_x, new_edges_y, new_edges_z)]
+    n = tuple(e.size - 1 for e in edges)
+    m = tuple(e.size - 1 for e in new_edges)
+    if np.shape(y) != m or np.shape(new_vol) != m:
+        raise ValueError(f"volume_average_adjoint: y {np.shape(y)} and new_vol {np.shape(new_vol)} on a {m} grid.")
+    yv = np.ascontiguousarray(np.asarray(y, dtype=np.float64).ravel(order='F'))
+    vol = np.ascontiguousarray(np.asarray(new_vol, dtype=np.float64).ravel(order='F'))
+    out = np.empty(n, dtype=np.float64, order='F')
+    _lib.check(lib.emg3d_volume_average_adjoint(*n, *(_lib.ptr(e) for e in edges), *m, *(_lib.ptr(e) for e in new_edges),
+                                                _lib.ptr(yv), _lib.ptr(vol), _lib.ptr(out)), "emg3d_volume_average_adjoint")
+    return out
+
+
+def regrid_factors(model, sigma):
+    """The diagonal factors of the Jacobian of ``model.interpolate2grid(model_grid, grid)`` followed by the property map, per
+    direction: with ``A`` volume averaging from the model grid to the computational grid, ``d sigma_c / d p_m = F A Q``.
+    ``model`` lives on the model grid, ``sigma = (sigma_x, sigma_y, sigma_z)`` are the conductivities on the computational grid
+    as the device holds them (``DeviceMG.get_sigma``).  Returns ``(F, Q)``, 3-tuples of arrays (entries of directions that
+    share the model's ``property_x`` are the same object).
+
+    * logarithmic maps (regridded with ``log=False``): ``p_c = A p_m``; ``F = chain_factor(sigma_c)``, ``Q = 1``;
+    * ``Conductivity`` / ``Resistivity`` (``log=True``): ``p_c = 10^(A log10 p_m)``, ``d p_c / d p_m = diag(p_c) A diag(1 / p_m)``:
+      ``F = chain_factor(sigma_c) p_c`` -- ``sigma_c`` resp. ``-sigma_c`` --, ``Q = 1 / p_m``.
+
+    Multiplications and one reciprocal of the model's own arrays only: no transcendental runs a second time."""
+    fmap = model.map
+    props = (model.property_x, model.property_y if model.case in (1, 3) else None,
+             model.property_z if model.case in (2, 3) else None)
+    F, Q = [], []
+    for c in range(3):
+        if c > 0 and props[c] is None:
+            F.append(F[0]); Q.append(Q[0])
+            continue
+        s = np.asarray(sigma[c], dtype=np.float64)
+        p = np.broadcast_to(np.asarray(props[c], dtype=np.float64), model.vnC)
+        if fmap.log:
+            F.append(fmap.chain_factor(s))
+            Q.append(np.ones(p.shape))
+        else:
+            F.append(s.copy() if fmap.name == 'Conductivity' else -s)
+            Q.append(1.0 / p)
+    return tuple(F), tuple(Q)
+
+
 def grid2grid(grid, values, new_grid, method='linear', extrapolate=True, log=False):
     """Interpolate ``values`` located on ``grid`` to ``new_grid`` (reference emg3d/maps.py:34-178).
 

@@ -16,7 +16,9 @@ on one handle per dtype, the sum over the sources formed on the device (``Device
 handles and the forward fields of ALL pairs in HBM and gives ``J v``, ``J^T w`` and the Gauss-Newton product ``J^T W J v`` of the
 survey, every solve batched over the sources.  ``model_gradient(...,
 model_grid=)`` maps the gradient to the model grid as the reference does (``maps.grid2grid(grid, -grad, model_grid,
-'cubic')``, optimize.py:201-211) and applies the chain rule there.
+'cubic')``, optimize.py:201-211) and applies the chain rule there; ``method='transpose'`` and ``SurveyJacobian(model_grid=)`` give the
+exact derivative with respect to the cells of a model grid instead (the transpose of ``Model.interpolate2grid``'s volume averaging,
+applied to the accumulators in HBM).
 
 An inversion keeps a ``Jacobian`` / ``SurveyJacobian`` (or the ``FrequencyHandles`` of ``survey_gradient(handles=)``) open for its
 whole life: ``set_model`` presents the next model -- in any of the six property maps -- to the open handles, and ``mapped=True``
@@ -312,7 +314,7 @@ def survey_gradient(grid, model, sources, freqs, rec, observed, weights=None, st
     return phi, grad, dict(synthetic=synthetic, misfit=misfits, partial=partial, forward=finfo, backward=binfo, phases=phases)
 
 
-def model_gradient(grid, model, grad, model_grid=None):
+def model_gradient(grid, model, grad, model_grid=None, method='cubic'):
     """d(misfit) / d(model property) from ``gradient()``'s ``grad`` (on the computational grid ``grid``): the reference's
     last steps (optimize.py:201-214): the sign, the mapping to the model grid, then the chain rule of the model's property
     map -- conductivity: identity; resistivity rho: d sigma / d rho = -1 / rho^2; the four logarithmic maps: their
@@ -321,7 +323,26 @@ def model_gradient(grid, model, grad, model_grid=None):
 
     ``model_grid=None``: ``model`` lives on ``grid`` (the reference's ``gridding='same'``), nothing is regridded.
     Otherwise ``model`` lives on ``model_grid``: ``-grad`` is mapped there with ``maps.grid2grid(grid, -grad, model_grid,
-    method='cubic')`` and the chain rule takes the property on ``model_grid``."""
+    method='cubic')`` and the chain rule takes the property on ``model_grid``.
+
+    ``method='transpose'`` (needs ``model_grid``): the exact derivative with respect to the model cells instead, for a model that
+    reaches ``grid`` through ``model.interpolate2grid(model_grid, grid)`` (volume averaging, in ``log10`` for ``Conductivity`` /
+    ``Resistivity``): ``Q (.) A^T (F (.) -grad)`` with ``maps.volume_average_adjoint`` and ``maps.regrid_factors`` -- the
+    transpose of what ``SurveyJacobian(model_grid=).jvec`` applies, which the cubic interpolation of the reference is not."""
+    if method not in ('cubic', 'transpose'):
+        raise ValueError(f"`method` must be 'cubic' or 'transpose'; provided: {method!r}.")
+    if method == 'transpose':
+        if model_grid is None:
+            raise ValueError("model_gradient: method='transpose' needs `model_grid` (the grid `model` lives on).")
+        if model.case != 0:
+            raise NotImplementedError("model_gradient: `grad` is the sum over the directions; method='transpose' takes isotropic "
+                                      "models (SurveyJacobian(model_grid=) gives the directions of an anisotropic one).")
+        cmodel = model.interpolate2grid(model_grid, grid)
+        F, Q = maps.regrid_factors(model, (cmodel.conductivity('property_x'),) * 3)
+        vol = grid.cell_volumes.reshape(grid.vnC, order='F')
+        y = F[0] * -np.asarray(grad, dtype=np.float64).reshape(grid.vnC, order='F')
+        return Q[0] * maps.volume_average_adjoint(model_grid.nodes_x, model_grid.nodes_y, model_grid.nodes_z, grid.nodes_x,
+                                                  grid.nodes_y, grid.nodes_z, y, vol)
     out = -np.asarray(grad)
     vnC = grid.vnC
     if model_grid is not None:
@@ -672,12 +693,23 @@ class SurveyJacobian(_JacobianBase):
     ``Jacobian`` (tri-axial models included, without ``mu_r`` / ``epsilon_r``; ``electric=False`` needs ``adjoint='exact'``), with
     the defaults ``'cubic'`` and ``'exact'``: the pair ``jvec`` / ``jtvec`` is then an adjoint pair, and ``gauss_newton`` symmetric
     positive semi-definite, to the accuracy of the solves.  ``forward_info[i][j]`` and, after a product, ``info[i][j]`` (the last
-    solve of the pair; ``jvec_info`` the J v solve of ``gauss_newton``) are the solver info dicts."""
+    solve of the pair; ``jvec_info`` the J v solve of ``gauss_newton``) are the solver info dicts.
+
+    ``model_grid`` (a ``TensorMesh``; default None: nothing changes): ``model`` lives on ``model_grid`` and ``grid`` is the
+    computational grid.  ``open()`` and ``set_model(model_on_model_grid)`` regrid with ``model.interpolate2grid(model_grid, grid)``
+    (volume averaging ``A``, in ``log10`` for ``'Conductivity'`` / ``'Resistivity'``); the products are with respect to the MODEL
+    cells, in the model's own property: ``jvec(v, mapped=True) = J (F (.) A (Q (.) v))`` with ``v`` of shape ``model_grid.vnC``,
+    ``jtvec(w, mapped=True) = Q (.) A^T (F (.) J^T w)`` of that shape (``maps.regrid_factors``; ``A^T`` applied to the accumulators
+    on the device, ``DeviceMG.grad_acc_get_model``: one ``nM``-sized array per frequency and direction comes back), ``partial`` the
+    per-frequency results on the model grid in the ``G_f`` sign convention.  The two are an adjoint pair as without a model grid.
+    ``mapped=False`` (the default) raises ``ValueError`` there: the conductivity on the model grid is not what the solves see."""
 
     def __init__(self, grid, model, sources, freqs, rec, batch=8, receiver_interpolation='cubic', adjoint='exact', electric=True,
-                 strength=0, device=0, **solver_opts):
+                 strength=0, device=0, model_grid=None, **solver_opts):
         _check_arguments('Jacobian', model, adjoint, electric, receiver_interpolation, count=('batch', batch),
                          krylov=solver_opts.get('sslsolver') and "SurveyJacobian: the products are multigrid solves")
+        self.model_grid = model_grid
+        self._check_model_grid(model)
         self.sources = list(sources)
         self.freqs = [float(f) for f in np.atleast_1d(freqs)]
         if len(self.sources) < 1 or len(self.freqs) < 1:
@@ -691,6 +723,7 @@ class SurveyJacobian(_JacobianBase):
         self._opts = {k: v for k, v in solver_opts.items() if k not in ('return_info', 'sslsolver')}
         self._specs = [fields.FrequencySpec(f) for f in self.freqs]
         self._vnC = tuple(int(n) for n in grid.vnC)
+        self._vnM = self._vnC if model_grid is None else tuple(int(n) for n in model_grid.vnC)     # the cells of `v` and `J^T w`
         self._nb = min(self.batch, self.n_src)
         self._chunks = [(i0, min(self._nb, self.n_src - i0)) for i0 in range(0, self.n_src, self._nb)]
         cplx = any(sp.dtype.kind == 'c' for sp in self._specs)
@@ -698,13 +731,62 @@ class SurveyJacobian(_JacobianBase):
         self._held = None
         self.synthetic = self.forward_info = self.info = self.jvec_info = self.partial = None
 
+    # ---- the model grid ------------------------------------------------------------------------------------------------
+    # With ``model_grid`` the model lives there and reaches ``grid`` through ``model.interpolate2grid(model_grid, grid)``: volume
+    # averaging A, in log10 for the two linear maps.  Per direction d sigma_c / d p_m = F A Q with diagonal F (on ``grid``) and Q
+    # (on ``model_grid``; ``maps.regrid_factors``), so J_m v = J (F (.) A (Q (.) v)) and J_m^T w = Q (.) A^T (F (.) J^T w).  ``jvec``
+    # forms its right-hand side once per product with the device's volume averaging; ``jtvec`` reads the accumulators back through
+    # ``grad_acc(3)_get_model`` (k_volume_average_adjoint on the resident tables and factors): model-grid-sized arrays only.
+    _regrid_FQ = None
+    _no_sigma = ("SurveyJacobian: on a model grid the products are defined in the model's own property only (the conductivity on "
+                 "the model grid is not what the solves see); use mapped=True.")
+
+    def _check_model_grid(self, model):
+        if self.model_grid is not None and tuple(model.vnC) != tuple(int(n) for n in self.model_grid.vnC):
+            raise ValueError(f"SurveyJacobian: `model` must live on `model_grid` {tuple(self.model_grid.vnC)}; it has "
+                             f"{tuple(model.vnC)} cells.")
+
+    def _on_grid(self, model):
+        """``model`` on the computational grid."""
+        return model if self.model_grid is None else model.interpolate2grid(self.model_grid, self.grid)
+
+    def _refresh_factors(self, handles):
+        dev = next(iter(handles))
+        case = self.model.case
+        sx = dev.get_sigma(0)
+        sigma = (sx, dev.get_sigma(1) if case in (1, 3) else sx, dev.get_sigma(2) if case in (2, 3) else sx)
+        self._regrid_FQ = maps.regrid_factors(self.model, sigma)
+        handles.set_regrid_factors(*self._regrid_FQ)
+
+    def _to_grid(self, vec):
+        """(v_x, v_y, v_z), F-raveled perturbations of p on the model grid (entries may be None) -> of sigma on ``grid``; entries
+        that are the same array with the same factors stay one array."""
+        F, Q = self._regrid_FQ
+        out, done = [], []
+        for c, v in enumerate(vec):
+            hit = [r for v0, c0, r in done if v0 is v and F[c0] is F[c] and Q[c0] is Q[c]]
+            if v is None or hit:
+                out.append(None if v is None else hit[0])
+                continue
+            vm = np.asfortranarray(Q[c] * v.reshape(self._vnM, order='F'))
+            r = np.ascontiguousarray((F[c] * maps.grid2grid(self.model_grid, vm, self.grid, 'volume')).ravel(order='F'))
+            done.append((v, c, r))
+            out.append(r)
+        return tuple(out)
+
+    def _mapped_or_refuse(self, mapped):
+        mapped = _mapped(mapped)
+        if self.model_grid is not None and not mapped:
+            raise ValueError(self._no_sigma)
+        return mapped
+
     # ---- handles ------------------------------------------------------------------------------------------------------
     def open(self):
         """Create the handles, size and allocate the parked fields, solve all pairs forward (chunk by chunk), extract the data."""
         if self._held is not None:
             return self
         ns, nf, nb = self.n_src, self.n_freq, self._nb
-        parts = models.model_parts(self.grid, self.model, raw=True)
+        parts = models.model_parts(self.grid, self._on_grid(self.model), raw=True)
         handles = solver.FrequencyHandles(self.grid, parts, self.device, nsys=nb)
         self._slot, first, nslots = {}, {}, {}
         for j, spec in enumerate(self._specs):
@@ -724,6 +806,8 @@ class SurveyJacobian(_JacobianBase):
                     f"{free} bytes are free; use fewer sources or frequencies per SurveyJacobian (frequency shards).")
             for key, dev in devs.items():
                 dev.bvec_alloc(nslots[key])
+            if self.model_grid is not None:
+                handles.set_model_grid(self.model_grid)
             self._forward(handles)
         except BaseException:
             handles.close()
@@ -751,16 +835,20 @@ class SurveyJacobian(_JacobianBase):
                 dev.set_mask(_first(n, nb))
                 dev.bvec_copy(self._slot[j] + c, dev.EFIELD)
         self.info = self.jvec_info = self.partial = self._chain = None
+        if self.model_grid is not None:
+            self._refresh_factors(handles)
 
     def set_model(self, model):
         """Another model on the same grid, in the same anisotropy case (any property map), on the open handles -- what an
         inversion does every iteration and every trial step: ``FrequencyHandles.set_model`` (the conductivities, eta, coarse
         models and line factorisations of every handle recomputed in HBM), all pairs solved forward again into the SAME parked
         vectors, ``synthetic`` and ``forward_info`` anew.  Every product is then bit for bit that of a new ``SurveyJacobian`` on
-        ``model``; no handle, hierarchy, launch graph or parked vector is created (``device_bytes`` stays)."""
+        ``model``; no handle, hierarchy, launch graph or parked vector is created (``device_bytes`` stays).  With ``model_grid``
+        the model lives there: it is regridded as ``open()`` does and the regrid factors are refreshed in place."""
         handles = self._require_open()
         _check_arguments('Jacobian', model, self.adjoint, self.electric, self.receiver_interpolation)
-        handles.set_model(model)
+        self._check_model_grid(model)
+        handles.set_model(self._on_grid(model))
         self.model = model
         self._forward(handles)
         return self
@@ -779,9 +867,9 @@ class SurveyJacobian(_JacobianBase):
 
     # ---- arguments ----------------------------------------------------------------------------------------------------
     def _perturbation(self, v):
-        vecs, single = _perturbations(v, self._vnC)
+        vecs, single = _perturbations(v, self._vnM)
         if not single:
-            raise ValueError(f"`v` must have shape {self._vnC} (or be a 3-tuple of such arrays): one perturbation per product.")
+            raise ValueError(f"`v` must have shape {self._vnM} (or be a 3-tuple of such arrays): one perturbation per product.")
         return vecs[0]
 
     def _data_array(self, w, name):
@@ -831,7 +919,8 @@ class SurveyJacobian(_JacobianBase):
         jinfo = [[None] * nf for _ in range(ns)]
         binfo = [[None] * nf for _ in range(ns)]
         nacc = 3 if components else 1
-        partial = np.zeros((nacc, nf) + self._vnC[::-1]).transpose(0, 1, 4, 3, 2) if adj else None     # every G_f F-ordered
+        on_model = self.model_grid is not None          # read back through A^T: G_f on the model grid, factors applied
+        partial = np.zeros((nacc, nf) + self._vnM[::-1]).transpose(0, 1, 4, 3, 2) if adj else None     # every G_f F-ordered
         for j, spec in enumerate(self._specs):
             dev, smu0 = handles.target(spec), spec.smu0
             real = dev.dtype.kind != 'c'
@@ -867,15 +956,18 @@ class SurveyJacobian(_JacobianBase):
                 else:
                     dev.grad_acc_add(slot, smu0, use)
             if adj:
-                got = dev.grad_acc3_get() if components else (dev.grad_acc_get(),)
+                if on_model:
+                    got = dev.grad_acc3_get_model() if components else (dev.grad_acc_get_model(),)
+                else:
+                    got = dev.grad_acc3_get() if components else (dev.grad_acc_get(),)
                 for q in range(nacc):
-                    partial[q, j] = got[q].reshape(self._vnC, order='F')
+                    partial[q, j] = got[q].reshape(self._vnM, order='F')
         return dd, jinfo, partial, binfo
 
     def _result(self, partial, components):
         """``-(((0 + G_0) + G_1) + ...)`` per accumulator."""
         zeros = np.zeros((self.n_src, self.n_freq))
-        out = tuple(-_sum_survey(p, zeros, self._vnC)[1] for p in partial)
+        out = tuple(-_sum_survey(p, zeros, self._vnM)[1] for p in partial)
         self.partial = partial if components else partial[0]
         return out if components else out[0]
 
@@ -886,16 +978,19 @@ class SurveyJacobian(_JacobianBase):
         if not mapped:
             return self._result(partial, components)
         three = components or self.model.case != 0
+        if self.model_grid is not None:         # the device has applied F and Q: what is left is the sum of the directions
+            out = self._result(partial, three)
+            return out if components or not three else (out[0] + out[1]) + out[2]
         return self._from_sigma(self._result(partial, three), components)
 
     def jvec(self, v, mapped=False):
         """``J v`` for all pairs: ``(n_src, n_freq, n_rec)``; ``v`` as for ``Jacobian.jvec`` (one perturbation).  ``mapped=True``:
         ``v`` perturbs the model's own property."""
-        mapped = _mapped(mapped)
+        mapped = self._mapped_or_refuse(mapped)
         vec = self._perturbation(v)
         if mapped:
             self._require_open()
-            vec = self._to_sigma(vec)
+            vec = self._to_sigma(vec) if self.model_grid is None else self._to_grid(vec)
         dd, self.info, _, _ = self._sweep(vec, None, None, False)
         return dd
 
@@ -904,7 +999,7 @@ class SurveyJacobian(_JacobianBase):
         (F-ordered), or the three terms ``(g_x, g_y, g_z)`` of sigma_x, sigma_y, sigma_z with ``components=True``.
         ``mapped=True``: with respect to the model's own property, ``D_c g_c`` (``components=False`` on an anisotropic model:
         their sum)."""
-        mapped = _mapped(mapped)
+        mapped = self._mapped_or_refuse(mapped)
         w = self._data_array(w, 'w')
         three = components or (mapped and self.model.case != 0)
         _, _, partial, self.info = self._sweep(None, w, None, three)
@@ -913,12 +1008,12 @@ class SurveyJacobian(_JacobianBase):
     def gauss_newton(self, v, weights=None, components=False, mapped=False):
         """``J^T W J v``, bit for bit ``jtvec(weights * jvec(v), components)``, the two products run chunk by chunk
         (``mapped=True``: of both mapped products)."""
-        mapped = _mapped(mapped)
+        mapped = self._mapped_or_refuse(mapped)
         vec = self._perturbation(v)
         weights = self._weights(weights)
         if mapped:
             self._require_open()
-            vec = self._to_sigma(vec)
+            vec = self._to_sigma(vec) if self.model_grid is None else self._to_grid(vec)
         three = components or (mapped and self.model.case != 0)
         _, self.jvec_info, partial, self.info = self._sweep(vec, None, weights, three)
         return self._mapped_result(partial, components, mapped)

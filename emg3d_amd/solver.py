@@ -70,6 +70,7 @@ class DeviceMG:
         self._smu0, self._sval, self._eps = smu0, sval, False
         self._vnC = tuple(int(n) for n in grid.vnC)
         self._alias = self._zeta = self._epsr = None        # (from_model_parts: what set_model compares a new model with)
+        self._vnM = None                                    # (set_model_grid: the cells of the model grid)
         hx, hy, hz = (np.ascontiguousarray(h, dtype=np.float64) for h in grid.h)
         return hx, hy, hz, np.ascontiguousarray(grid.origin, dtype=np.float64)
 
@@ -309,6 +310,65 @@ class DeviceMG:
         """The three accumulators ``(acc_x, acc_y, acc_z)``: ``nC`` doubles each, F-ordered."""
         outs = [np.empty(self.nC, dtype=np.float64) for _ in range(3)]
         _lib.check(self._lib.emg3d_mg_grad_acc3_get(self._h, *(_lib.ptr(o) for o in outs)), "emg3d_mg_grad_acc3_get")
+        return tuple(outs)
+
+    # ---- the accumulators on a model grid (optimize.SurveyJacobian(model_grid=)) ----
+    def set_model_grid(self, model_grid):
+        """Link the handle to the grid the model lives on (``emg3d_mg_set_model_grid``): the segment tables of volume averaging
+        from ``model_grid`` to the handle's grid, built once and kept in HBM with the scratch of ``grad_acc(3)_get_model``
+        (counted by ``device_bytes``).  Another model grid of the same size replaces the first in place."""
+        edges = [np.ascontiguousarray(e, dtype=np.float64) for e in (model_grid.nodes_x, model_grid.nodes_y, model_grid.nodes_z)]
+        vnM = tuple(int(n) for n in model_grid.vnC)
+        st = self._lib.emg3d_mg_set_model_grid(self._h, *vnM, *(_lib.ptr(e) for e in edges))
+        if st == -2:
+            raise ValueError(f"set_model_grid: the handle is linked to a model grid of another size than {vnM}.")
+        _lib.check(st, "emg3d_mg_set_model_grid")
+        self._vnM = vnM
+
+    def _require_model_grid(self, st, name):
+        """``_lib.check`` for the model-grid calls: status -7 = no model grid, or no factors yet."""
+        if st == -7:
+            raise RuntimeError(f"{name}: the handle has no model grid or no regrid factors (set_model_grid, set_regrid_factors).")
+        _lib.check(st, name)
+
+    def set_regrid_factors(self, F, Q):
+        """The diagonal factors of ``grad_acc(3)_get_model`` per direction (``emg3d_mg_set_regrid_factors``): ``F = (F_x, F_y,
+        F_z)`` on the handle's grid, ``Q = (Q_x, Q_y, Q_z)`` on the model grid, resident; entries that are the same object as the
+        first are uploaded once.  Later calls (another model) replace the values in place."""
+        vnM = self._vnM
+        if vnM is None:
+            raise RuntimeError("set_regrid_factors: the handle has no model grid (set_model_grid).")
+        if len(F) != 3 or len(Q) != 3:
+            raise ValueError("set_regrid_factors: `F` and `Q` must be 3-tuples (x, y, z).")
+        held = []
+        for arrs, shape, name in ((F, self._vnC, 'F'), (Q, vnM, 'Q')):
+            base = len(held)
+            for c, a in enumerate(arrs):
+                if c > 0 and a is arrs[0]:
+                    held.append(held[base])
+                    continue
+                if np.shape(a) != shape:
+                    raise ValueError(f"set_regrid_factors: `{name}[{c}]` must have shape {shape}; provided: {np.shape(a)}.")
+                held.append(_cells(a))
+        st = self._lib.emg3d_mg_set_regrid_factors(self._h, *(_lib.ptr(a) for a in held))
+        if st == -2:
+            raise ValueError("set_regrid_factors: the directions must share factors as in the handle's first call.")
+        self._require_model_grid(st, "emg3d_mg_set_regrid_factors")
+
+    def grad_acc_get_model(self):
+        """``Q_x (.) A^T (F_x (.) acc)`` of the accumulator of ``grad_acc_add`` (``emg3d_mg_grad_acc_get_model``; ``A``: volume
+        averaging from the model grid): ``nM`` doubles, F-ordered.  The accumulator stays as it is."""
+        out = np.empty(int(np.prod(self._vnM or (1,))), dtype=np.float64)
+        self._require_model_grid(self._lib.emg3d_mg_grad_acc_get_model(self._h, _lib.ptr(out)), "emg3d_mg_grad_acc_get_model")
+        return out
+
+    def grad_acc3_get_model(self):
+        """``Q_c (.) A^T (F_c (.) acc_c)`` of the three accumulators of ``grad_acc3_add`` (``emg3d_mg_grad_acc3_get_model``):
+        three arrays of ``nM`` doubles, F-ordered.  The accumulators stay as they are."""
+        n = int(np.prod(self._vnM or (1,)))
+        outs = [np.empty(n, dtype=np.float64) for _ in range(3)]
+        self._require_model_grid(self._lib.emg3d_mg_grad_acc3_get_model(self._h, *(_lib.ptr(o) for o in outs)),
+                                 "emg3d_mg_grad_acc3_get_model")
         return tuple(outs)
 
     def _perturbation_ptrs(self, vs, what):
@@ -712,6 +772,7 @@ class FrequencyHandles:
     def __init__(self, grid, parts, device, nsys=1, bvecs=0):
         self.grid, self.parts, self.device, self.nsys, self.bvecs = grid, parts, device, int(nsys), int(bvecs)
         self._handles = {}
+        self._model_grid = self._factors = None
 
     def target(self, spec, key=()):
         """The handle for ``spec`` (a field or ``FrequencySpec``: ``dtype``, ``smu0``, ``sval``), standing at its frequency."""
@@ -725,6 +786,10 @@ class FrequencyHandles:
             dev.set_batch(self.nsys)
         if self.bvecs:
             dev.bvec_alloc(self.bvecs)
+        if self._model_grid is not None:
+            dev.set_model_grid(self._model_grid)
+            if self._factors is not None:
+                dev.set_regrid_factors(*self._factors)
         return dev
 
     def set_model(self, model):
@@ -736,6 +801,21 @@ class FrequencyHandles:
         for dev in self._handles.values():
             dev._set_parts(self.grid, parts)
         self.parts = parts
+
+    def set_model_grid(self, model_grid):
+        """Link every open handle, and the handles created later, to the grid the model lives on (``DeviceMG.set_model_grid``)."""
+        for dev in self._handles.values():
+            dev.set_model_grid(model_grid)
+        self._model_grid = model_grid
+
+    def set_regrid_factors(self, F, Q):
+        """The factors of ``grad_acc(3)_get_model`` for every open handle and the handles created later
+        (``DeviceMG.set_regrid_factors``)."""
+        if self._model_grid is None:
+            raise RuntimeError("set_regrid_factors: the handles have no model grid (set_model_grid).")
+        for dev in self._handles.values():
+            dev.set_regrid_factors(F, Q)
+        self._factors = (tuple(F), tuple(Q))
 
     def __iter__(self):
         return iter(self._handles.values())

@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 111
+#define EMG3D_HIP_ABI_VERSION 112
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -363,6 +363,40 @@ int emg3d_volume_average(int dtype, int64_t nx, int64_t ny, int64_t nz, const do
                          const double* edges_z, const void* values, int64_t mx, int64_t my, int64_t mz,
                          const double* new_edges_x, const double* new_edges_y, const double* new_edges_z, void* new_values,
                          const double* new_vol);
+/* The segments of emg3d_volume_average_weights come out in ascending coordinate order, so they are sorted by OLD cell too:
+ * iptr (n + 1 entries, n = n1 - 1 old cells): old cell i owns segments [iptr[i], iptr[i+1]) -- the offsets the transpose below
+ * gathers with.  -2 if idx_in is not ascending or leaves [0, n).  O(n) host work, no device.                             */
+int emg3d_volume_average_old_offsets(const int64_t* idx_in, int64_t nseg, int64_t n, int64_t* iptr);
+/* The transpose of emg3d_volume_average, double only (optimize.model_gradient(method='transpose')): with A the matrix that
+ * emg3d_volume_average applies to a zero new array -- A[o, i] = (sum of the segment weights (w_z w_y) w_x of new cell o that lie
+ * in old cell i) / new_vol[o] --, out = A^T y: y and new_vol F-ordered (mx,my,mz) on the NEW grid, out F-ordered (nx,ny,nz) on
+ * the OLD grid (overwritten).  One thread per old cell gathers t[o] = y[o] / new_vol[o] over the tensor product of its segments:
+ * out[i] = sum_z sum_y sum_x ((w_z w_y) w_x) t[o], z outermost, segments ascending, from 0, nothing fused -- no atomics, results
+ * repeat bit for bit.  An old cell without a segment (the old grid reaches beyond the new one) gets an exact 0.          */
+int emg3d_volume_average_adjoint(int64_t nx, int64_t ny, int64_t nz, const double* edges_x, const double* edges_y,
+                                 const double* edges_z, int64_t mx, int64_t my, int64_t mz, const double* new_edges_x,
+                                 const double* new_edges_y, const double* new_edges_z, const double* y, const double* new_vol,
+                                 double* out);
+/* Sensitivities on a model grid (optimize.SurveyJacobian(model_grid=)): the model lives on a grid of (nx,ny,nz) cells with the
+ * given edges and reaches the handle's grid by volume averaging (A as above: old = model grid, new = the handle's grid).
+ *   set_model_grid     : the segment tables of the three axes with their new-cell and old-cell offsets, built once and kept in
+ *                        HBM, plus nC doubles of scratch and 3 nM doubles for results; counted by emg3d_mg_device_bytes, freed with
+ *                        the handle.  A second call takes a model grid of the same (nx,ny,nz) in place (-2 for another size).
+ *   set_regrid_factors : the diagonal factors per direction, F_c on the handle's grid (nC doubles), Q_c on the model grid (nM
+ *                        doubles), resident; a direction given with the pointer of direction x shares its copy.  Later calls
+ *                        replace the values in place and must share in the same way (-2 otherwise).  -7 without a model grid.
+ *   grad_acc_get_model : out (nM doubles, F-ordered) = Q_x (.) A^T (F_x (.) acc) of the accumulator of emg3d_mg_grad_acc_*
+ *                        (isotropic models: one factor pair serves the sum of the three directions).
+ *   grad_acc3_get_model: out_c = Q_c (.) A^T (F_c (.) acc_c) of the three accumulators of emg3d_mg_grad_acc3_*.
+ * Both leave the accumulators as they are (the _get calls afterwards return them unchanged); only nM-sized arrays cross
+ * PCIe; the arithmetic is emg3d_volume_average_adjoint's with t[o] = (F[o] acc[o]) / vol[o], vol = (hx hy) hz, and the sum times
+ * Q[i].  -7 without a model grid or factors.                                                                              */
+int emg3d_mg_set_model_grid(emg3d_mg_t* mg, int64_t nx, int64_t ny, int64_t nz, const double* edges_x, const double* edges_y,
+                            const double* edges_z);
+int emg3d_mg_set_regrid_factors(emg3d_mg_t* mg, const double* F_x, const double* F_y, const double* F_z, const double* Q_x,
+                                const double* Q_y, const double* Q_z);
+int emg3d_mg_grad_acc_get_model(emg3d_mg_t* mg, double* out);
+int emg3d_mg_grad_acc3_get_model(emg3d_mg_t* mg, double* out_x, double* out_y, double* out_z);
 /* emg3d_interp3d on the tensor product of three coordinate vectors xi_x (mx), xi_y (my), xi_z (mz): out is F-ordered
  * (mx,my,mz), out[i + mx (j + my k)] = emg3d_interp3d at (xi_x[i], xi_y[j], xi_z[k]) bit for bit; method / has_fill /
  * fill_value / cval as there (maps.grid2grid, reference emg3d/maps.py:34-178, uses 0, 1 and 3).  The per-axis work is
