@@ -1271,6 +1271,16 @@ int emg3d_mg_grad_acc3_get(emg3d_mg_t* mg, double* out_x, double* out_y, double*
     });
 }
 
+int emg3d_mg_sens_acc_add(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use_fwd, const int32_t* use_adj,
+                          const double* weights, int split) {
+    if (!mg || !use_fwd || !use_adj || !weights) return -2;
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        const int st = m->sens_acc_add(fwd_bvec, smu0_re, smu0_im, use_fwd, use_adj, weights, split != 0);
+        return st ? st : finish(m);
+    });
+}
+
 int emg3d_mg_jvec_source_b(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const double* vx, const double* vy,
                            const double* vz, const int32_t* use) {
     if (!mg || !use) return -2;

@@ -3,7 +3,9 @@
 //                   averages, one output array per component;
 //   k_gradient    = optimize.gradient for one (source, frequency) pair on its computational grid (reference
 //                   emg3d/optimize.py:176-199): -Re(lambda E s mu_0) on the edges, mapped to cells, components added;
-//   k_gradient_acc = the same for all systems of a batch in one launch, added into a per-cell accumulator in system order.
+//   k_gradient_acc = the same for all systems of a batch in one launch, added into a per-cell accumulator in system order;
+//   k_sens_acc    = the survey sensitivity diagonal: W |row|^2 for all pairs of an adjoint and a forward system, into the same
+//                   accumulators (no counterpart in the reference).
 // Gather form: one thread per CELL sums the contributions of its 12 edges in the order in which the reference's
 // loops (iz, iy, ix ascending, four statements per edge) add them -- deterministic and equal to the reference's
 // accumulation order, no atomics.
@@ -122,6 +124,108 @@ __global__ void k_gradient_acc(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* 
         grad_cell<T>(j, nC, vol, fl, e + (i64)b * nE, bk + (i64)b * nE, sr, si, g);
         if (SPLIT) { run += g[0]; run1 += g[1]; run2 += g[2]; }
         else run += (g[0] + g[1]) + g[2];
+    }
+    acc[idx] = run;
+    if (SPLIT) { acc1[idx] = run1; acc2[idx] = run2; }
+}
+
+// ---- survey sensitivity diagonal: diag(J^H W J) (optimize.SurveyJacobian.sensitivity_diagonal) -----------------------------
+// Row (source s, receiver r) of J at a cell is c = c_x + c_y + c_z, c_c = edges2cellaverages_c(s mu_0 lambda_r E_s): the operator is
+// complex symmetric, so lambda_r, the field of receiver r's adjoint source ALONE, serves every source.  An all-pairs product: the
+// real part is NOT taken before averaging (the row is complex), and the sum over the pairs is one of squares.
+__device__ __forceinline__ double sens_prod(double l, double e, double sr, double) { return (l * e) * sr; }
+__device__ __forceinline__ c128 sens_prod(c128 l, c128 e, double sr, double si) { return (l * e) * mk(sr, si); }
+__device__ __forceinline__ double sens_abs2(double c) { return c * c; }
+__device__ __forceinline__ double sens_abs2(c128 c) { return c.re * c.re + c.im * c.im; }
+
+// The twelve edges of a cell: component c, edge k = (i_t1 - j_t1) + 2 (i_t2 - j_t2) with the transverse axes t1 < t2 of
+// e2c_component -- the order in which its loops visit them.  Indexed with compile-time constants only (registers, no scratch).
+template <class V>
+struct CellEdges { V v[3][4]; };
+
+__device__ __forceinline__ void cell_edge_offsets(const i64 j[3], const FieldLayout& fl, CellEdges<i64>& o) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int t1 = (c == 0) ? 1 : 0, t2 = (c == 2) ? 1 : 2;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            i64 e[3];
+            e[c] = j[c]; e[t1] = j[t1] + (k & 1); e[t2] = j[t2] + (k >> 1);
+            o.v[c][k] = fl.off[c] + e[0] * fl.st[c][0] + e[1] * fl.st[c][1] + e[2] * fl.st[c][2];
+        }
+    }
+}
+template <class T>
+__device__ __forceinline__ void cell_edge_load(const T* f, const CellEdges<i64>& o, CellEdges<T>& out) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) out.v[c][k] = f[o.v[c][k]];
+}
+
+// The three components of one row of J at cell j: cc[c] = edges2cellaverages_c( (lambda * E) * s mu_0 ), the four statements per
+// edge those of grad_cell (e2c_component), the edge values taken from registers.  One body for both forms of k_sens_acc.
+template <class T>
+__device__ __forceinline__ void sens_cell(const i64 j[3], const i64 nC[3], double vol, const CellEdges<T>& lam, const CellEdges<T>& ev,
+                                          double sr, double si, T cc[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int t1 = (c == 0) ? 1 : 0, t2 = (c == 2) ? 1 : 2;
+        const T(&lc)[4] = lam.v[c];
+        const T(&ec)[4] = ev.v[c];
+        cc[c] = e2c_component<T>(c, j, nC, vol, [&](i64 i0, i64 i1, i64 i2) {
+            const i64 i[3] = {i0, i1, i2};
+            const bool q1 = i[t1] != j[t1], q2 = i[t2] != j[t2];          // (selects, not an index: nothing to spill)
+            const T l = q2 ? (q1 ? lc[3] : lc[2]) : (q1 ? lc[1] : lc[0]);
+            const T e = q2 ? (q1 ? ec[3] : ec[2]) : (q1 ? ec[1] : ec[0]);
+            return sens_prod(l, e, sr, si);
+        });
+    }
+}
+
+// acc[cell] += W[b_r nsys + b_s] |(c_x + c_y) + c_z|^2 over the pairs (b_r, b_s) -- LOOP ORDER (part of the contract): the adjoint
+// systems b_r with bit b_r of `use_adj` set, ascending, outer; the forward systems b_s with bit b_s of `use_fwd` set, ascending,
+// inner; a pair with W == 0 is skipped (no load, no term).  lambda_{b_r} = slice b_r of the level-0 field array `adj`, E_{b_s} =
+// slice b_s of the batched vector `fwd`.  SPLIT: acc, acc1, acc2 += W |c_x|^2, W |c_y|^2, W |c_z|^2.  One thread per cell, one read
+// and one write of each accumulator, no atomics; the twelve lambda values of a receiver stay in registers across the inner loop.
+// Per launch a lambda field is read once, an E field once per active adjoint system (twelve edge values per cell and use, each
+// edge shared by up to four cells through the caches): at most (n_adj + pairs) nE sizeof(T) bytes from HBM; W is wave-uniform and
+// comes through the scalar cache.  Launched with 256 threads: the bound lets the complex
+// kernel keep its 2 x 12 edge values and 12 offsets in registers (the default bound of 1024 threads caps it at 128 and spills).
+template <class T, bool SPLIT>
+__global__ void __launch_bounds__(256) k_sens_acc(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* fwd, const T* adj, i64 nE, int nsys, unsigned long long use_fwd,
+                           unsigned long long use_adj, const double* W, double sr, double si, const double* h0, const double* h1,
+                           const double* h2, double* acc, double* acc1, double* acc2) {
+    const i64 nC[3] = {n0, n1, n2};
+    const i64 n = n0 * n1 * n2;
+    const i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const i64 j[3] = {idx % n0, (idx / n0) % n1, idx / (n0 * n1)};
+    const double vol = (h0[j[0]] * h1[j[1]]) * h2[j[2]];
+    if (nsys < 64) {                    // (never a shift by 64: nsys = 64 with bit 63 set is a valid batch)
+        use_fwd &= (1ull << nsys) - 1ull;
+        use_adj &= (1ull << nsys) - 1ull;
+    }
+    CellEdges<i64> o;
+    cell_edge_offsets(j, fl, o);
+    double run = acc[idx], run1 = 0.0, run2 = 0.0;
+    if (SPLIT) { run1 = acc1[idx]; run2 = acc2[idx]; }
+    for (unsigned long long ra = use_adj; ra; ra &= ra - 1ull) {          // (wave-uniform: the masks are kernel arguments)
+        const int br = __builtin_ctzll(ra);
+        const double* Wr = W + (i64)br * nsys;
+        CellEdges<T> lam;
+        cell_edge_load(adj + (i64)br * nE, o, lam);
+        for (unsigned long long rf = use_fwd; rf; rf &= rf - 1ull) {
+            const int bs = __builtin_ctzll(rf);
+            const double w = Wr[bs];
+            if (w == 0.0) continue;
+            CellEdges<T> ev;
+            cell_edge_load(fwd + (i64)bs * nE, o, ev);
+            T cc[3];
+            sens_cell<T>(j, nC, vol, lam, ev, sr, si, cc);
+            if (SPLIT) { run += w * sens_abs2(cc[0]); run1 += w * sens_abs2(cc[1]); run2 += w * sens_abs2(cc[2]); }
+            else run += w * sens_abs2((cc[0] + cc[1]) + cc[2]);
+        }
     }
     acc[idx] = run;
     if (SPLIT) { acc1[idx] = run1; acc2[idx] = run2; }

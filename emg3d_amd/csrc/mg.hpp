@@ -976,6 +976,43 @@ struct MG : emg3d_mg {
         check_launch();
         return err;
     }
+    // Survey sensitivity diagonal (emg3d_mg_sens_acc_add, k_sens_acc): acc += W[b_r nsys + b_s] |row(b_r, b_s)|^2 over all pairs of an
+    // adjoint system b_r (slice of the level-0 field array) and a forward system b_s (slice of batched vector `fwd_bvec`), into
+    // grad_acc (split = 0) or the three of grad_acc3 (split = 1), in ONE launch.  The weight table is nsys x nsys doubles of the
+    // handle's own, allocated at the first call (counted in `bytes`; nsys is fixed once a batched vector exists) and uploaded by
+    // every call.  -2: a bad vector, an accumulator that was never reset, a non-finite weight.
+    double* sens_w = nullptr;
+    int sens_acc_add(int fwd_bvec, double sr, double si, const int32_t* use_fwd, const int32_t* use_adj, const double* weights, int split) {
+        if (fwd_bvec < 0 || fwd_bvec >= (int)bvecs.size()) return -2;
+        if (split ? !grad_acc3 : !grad_acc) return -2;
+        const i64 nw = (i64)nsys * nsys;
+        for (i64 q = 0; q < nw; ++q) if (!std::isfinite(weights[q])) return -2;
+        if (!sens_w) sens_w = dalloc<double>(nw);
+        if (!sens_w) return err ? err : (int)hipErrorOutOfMemory;
+        const hipError_t st = h2d(sens_w, weights, (size_t)nw * sizeof(double));
+        if (st != hipSuccess) return (int)st;
+        Level<T>& L = *lv0;
+        unsigned long long bf = 0, ba = 0;
+        for (int b = 0; b < nsys; ++b) {
+            if (use_fwd[b]) bf |= 1ull << b;
+            if (use_adj[b]) ba |= 1ull << b;
+        }
+        const T* fwd = bvecs[(size_t)fwd_bvec];
+        e_to_ref(L);
+        const T* adj = L.e;
+        const unsigned blocks = (unsigned)((L.nCells + 255) / 256);
+        double* a0 = split ? grad_acc3 : grad_acc;
+        double* a1 = split ? grad_acc3 + L.nCells : nullptr;
+        double* a2 = split ? grad_acc3 + 2 * L.nCells : nullptr;
+        if (split)
+            MG_LAUNCH((k_sens_acc<T, true>), dim3(blocks), dim3(256), 0, stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd, adj, L.nE, nsys, bf,
+                      ba, (const double*)sens_w, sr, si, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], a0, a1, a2);
+        else
+            MG_LAUNCH((k_sens_acc<T, false>), dim3(blocks), dim3(256), 0, stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd, adj, L.nE, nsys, bf,
+                      ba, (const double*)sens_w, sr, si, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], a0, a1, a2);
+        check_launch();
+        return err;
+    }
 
     // ------------------------------------------- model grid (emg3d_mg_set_model_grid, _set_regrid_factors, _grad_acc(3)_get_model)
     // The model of an inversion lives on a coarser grid and reaches this one by volume averaging (regrid.hpp: A); the accumulators

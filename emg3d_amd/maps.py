@@ -345,6 +345,81 @@ def cellaverages2edges(vx, vy, vz, vol, out_x, out_y, out_z):
             o[...] = r.reshape(shp, order='F')
 
 
+def _edges2cellaverages_host(comps, vol):
+    """``edges2cellaverages`` in plain numpy, in the scalar type of its arguments (``np.longdouble`` included): the three cell
+    arrays, returned.  Per cell the statements are added in the order of the device's ``e2c_component`` -- the cell's four edges
+    of a component with the second transverse axis outermost, per edge the reference's four statements (m1, m2), (p1, m2), (m1,
+    p2), (p1, p2) of which a boundary cell receives two or four -- each as one array operation (a statement that does not hit a
+    cell adds an exact zero there)."""
+    n = vol.shape
+    J = np.ogrid[:n[0], :n[1], :n[2]]
+    everywhere = np.ones((1, 1, 1), dtype=bool)
+    out = []
+    for c, f in enumerate(comps):
+        t1, t2 = (1 if c == 0 else 0), (1 if c == 2 else 2)
+        acc = np.zeros(n, dtype=np.result_type(f.dtype, vol.dtype))
+
+        def hits(t, q):     # which cells edge j + q of axis t reaches through m = max(e - 1, 0) and through p = min(e, n - 1)
+            return (everywhere if q else J[t] == 0), (J[t] == n[t] - 1 if q else everywhere)
+        for q2 in (0, 1):
+            m2, p2 = hits(t2, q2)
+            for q1 in (0, 1):
+                m1, p1 = hits(t1, q1)
+                sl = [slice(None)] * 3
+                sl[t1], sl[t2] = slice(q1, n[t1] + q1), slice(q2, n[t2] + q2)
+                v = (vol * f[tuple(sl)]) / 4
+                for a1, a2 in ((m1, m2), (p1, m2), (m1, p2), (p1, p2)):
+                    acc = acc + np.where(a1 & a2, v, 0)
+        out.append(acc)
+    return out
+
+
+def sensitivity_diagonal(grid, fwd, adj, smu0, weights, components=False, dtype=np.float64):
+    """Host restatement (plain numpy) of what ``DeviceMG.sens_acc_add`` adds, from zero: ``sum over the pairs of weights[b_adj,
+    b_fwd] * |c_x + c_y + c_z|^2`` with ``c_c = edges2cellaverages_c((adj[b_adj] * fwd[b_fwd]) * smu0)`` and the cell volumes
+    ``(hx * hy) * hz`` of ``grid`` -- the diagonal of ``J^H W J`` when ``adj[b]`` is the field of receiver ``b``'s adjoint source
+    and ``fwd[b]`` the forward field of source ``b`` (``optimize.SurveyJacobian.sensitivity_diagonal``).  ``fwd``: ``(n_fwd, nE)``,
+    ``adj``: ``(n_adj, nE)`` fields ``[fx|fy|fz]`` (both real or complex), ``weights``: ``(n_adj, n_fwd)``, real; a pair with weight
+    0 is skipped.  The pairs are added in the kernel's order (adjoint systems outer, forward systems inner, both ascending), the
+    statements per cell in its order too.  ``dtype``: the real type everything is evaluated and accumulated in (``np.longdouble``:
+    the yardstick of the tests).  ``components=True``: ``(W |c_x|^2, W |c_y|^2, W |c_z|^2)`` summed likewise.  Returns arrays of
+    shape ``grid.vnC`` and type ``dtype``.  ``maps.edges2cellaverages`` runs on the device in float64, so the averaging is
+    restated here (``_edges2cellaverages_host``)."""
+    rtype = np.dtype(dtype)
+    fwd, adj = np.atleast_2d(np.asarray(fwd)), np.atleast_2d(np.asarray(adj))
+    cplx = np.iscomplexobj(fwd) or np.iscomplexobj(adj) or np.iscomplexobj(smu0)
+    ftype = np.result_type(rtype, np.complex64) if cplx else rtype
+    nx, ny, nz = (int(n) for n in grid.vnC)
+    shapes = ((nx, ny + 1, nz + 1), (nx + 1, ny, nz + 1), (nx + 1, ny + 1, nz))
+    off = np.cumsum([0] + [int(np.prod(s)) for s in shapes])
+    weights = np.asarray(weights, dtype=np.float64)
+    if fwd.shape[1] != off[3] or adj.shape[1] != off[3] or weights.shape != (adj.shape[0], fwd.shape[0]):
+        raise ValueError(f"sensitivity_diagonal: fields of {off[3]} edges and weights of shape (n_adj, n_fwd) are needed; provided: "
+                         f"{fwd.shape}, {adj.shape}, {weights.shape}.")
+    hx, hy, hz = (np.asarray(h, dtype=np.float64).astype(rtype) for h in grid.h)
+    vol = (hx[:, None, None] * hy[None, :, None]) * hz[None, None, :]
+    s = ftype.type(smu0) if cplx else rtype.type(np.real(smu0))
+    fwd, adj = fwd.astype(ftype), adj.astype(ftype)
+    acc = [np.zeros((nx, ny, nz), dtype=rtype) for _ in range(3 if components else 1)]
+
+    def abs2(c):
+        return c.real * c.real + c.imag * c.imag if cplx else c * c
+    for ba in range(adj.shape[0]):
+        for bf in range(fwd.shape[0]):
+            w = weights[ba, bf]
+            if w == 0:
+                continue
+            prod = (adj[ba] * fwd[bf]) * s
+            cc = _edges2cellaverages_host([prod[off[c]:off[c + 1]].reshape(shapes[c], order='F') for c in range(3)], vol)
+            w = rtype.type(w)
+            if components:
+                acc = [a + w * abs2(c) for a, c in zip(acc, cc)]
+            else:
+                acc[0] = acc[0] + w * abs2((cc[0] + cc[1]) + cc[2])
+    out = tuple(np.asfortranarray(a) for a in acc)
+    return out if components else out[0]
+
+
 # --------------------------------------------------------------------------
 # Property maps
 # --------------------------------------------------------------------------

@@ -730,6 +730,7 @@ class SurveyJacobian(_JacobianBase):
         self.dtype = np.dtype(np.complex128 if cplx else np.float64)
         self._held = None
         self.synthetic = self.forward_info = self.info = self.jvec_info = self.partial = None
+        self.sensitivity_info = self.sensitivity_partial = None
 
     # ---- the model grid ------------------------------------------------------------------------------------------------
     # With ``model_grid`` the model lives there and reaches ``grid`` through ``model.interpolate2grid(model_grid, grid)``: volume
@@ -835,6 +836,7 @@ class SurveyJacobian(_JacobianBase):
                 dev.set_mask(_first(n, nb))
                 dev.bvec_copy(self._slot[j] + c, dev.EFIELD)
         self.info = self.jvec_info = self.partial = self._chain = None
+        self.sensitivity_info = self.sensitivity_partial = None
         if self.model_grid is not None:
             self._refresh_factors(handles)
 
@@ -1017,6 +1019,85 @@ class SurveyJacobian(_JacobianBase):
         three = components or (mapped and self.model.case != 0)
         _, self.jvec_info, partial, self.info = self._sweep(vec, None, weights, three)
         return self._mapped_result(partial, components, mapped)
+
+    # ---- diag(J^H W J) ------------------------------------------------------------------------------------------------
+    _no_diagonal_on_model_grid = (
+        "SurveyJacobian.sensitivity_diagonal: not available with `model_grid`.  The diagonal on the model grid is not A^T of the "
+        "diagonal on the computational grid: a row there is Q (.) A^T (F (.) row), whose squares mix the cells A averages over.")
+
+    def sensitivity_diagonal(self, weights=None, components=False, mapped=False):
+        """The diagonal of the Gauss-Newton Hessian ``J^H W J``, the cumulative sensitivity ``out[j] = sum over the data d = (i_src,
+        i_freq, i_rec) of weights[d] |J_dj|^2``: a real array of shape ``grid.vnC`` (F-ordered).  ``J_dj = jtvec(e_d) + i
+        jtvec(i e_d)`` is entry ``j`` of the complex row of datum ``d`` (Laplace-domain entries of ``freqs``: the real row
+        ``jtvec(e_d)``).  ``components=True``: the three diagonals ``(d_x, d_y, d_z)`` with respect to sigma_x, sigma_y, sigma_z (of
+        the rows ``jtvec(., components=True)``).  ``mapped=True``: of the rows with respect to the model's own property, i.e. times
+        the square of the chain factor.  For an anisotropic model that holds per direction (``components=True``); the square of the
+        mapped SUM ``|sum_c D_c J_c|^2`` needs the cross terms ``J_a conj(J_b)``, which no accumulator holds:
+        ``NotImplementedError``.
+
+        The operator is complex symmetric, so the row of (source s, receiver r) is the cell average of ``s mu_0 lambda_r E_s`` with
+        ``lambda_r`` the field of receiver ``r``'s adjoint source alone: ``n_rec`` solves per frequency give every row (``2 n_src
+        n_rec`` through ``jtvec``).  Per frequency the accumulator is reset; the receivers go in chunks of the handle's width
+        ``min(batch, n_src)``, system ``b`` of a chunk with the unit row of receiver ``r0 + b`` (built as ``jtvec`` builds its
+        sources, for every ``receiver_interpolation``, ``adjoint`` and ``electric``), one batched solve per chunk, then ONE
+        ``DeviceMG.sens_acc_add`` per parked chunk of forward fields with that block of ``weights``; one ``nC``-sized array (three)
+        comes back per frequency.  ``weights``: real, broadcast to ``(n_src, n_freq, n_rec)``, not negative (default 1); NaN: no
+        datum.  A receiver without a datum at a frequency is not solved for (``sensitivity_info[i_freq][i_rec]`` is ``None``,
+        otherwise the solver's info dict).  The result is ``((0 + P_0) + P_1) + ...`` over ``freqs`` on the host,
+        ``sensitivity_partial`` the ``P_f`` -- ``(n_freq,) + vnC``, ``(3, n_freq) + vnC`` with ``components=True``, with respect to
+        conductivity -- for frequency shards to add.  Deterministic for a given ``batch``; another ``batch`` adds the same
+        non-negative terms in another order.  Nothing is allocated but the handle's weight table; works after ``set_model``.
+
+        With ``model_grid`` it raises ``ValueError``: the diagonal on the model grid is not ``A^T`` of this one."""
+        mapped = _mapped(mapped)
+        if self.model_grid is not None:
+            raise ValueError(self._no_diagonal_on_model_grid)
+        if mapped and not components and self.model.case != 0:
+            raise NotImplementedError("SurveyJacobian.sensitivity_diagonal: mapped=True on an anisotropic model gives the diagonal per "
+                                      "direction (components=True); the square of the mapped sum needs cross terms that are not "
+                                      "accumulated.")
+        weights = self._weights(weights)
+        if np.any(np.nan_to_num(weights) < 0) or np.any(np.isinf(weights)):
+            raise ValueError("`weights` must be finite and not negative (NaN: no datum).")
+        weights = np.where(np.isnan(weights), 0.0, weights)
+        handles = self._require_open()
+        nf, nr, nb = self.n_freq, self.n_rec, self._nb
+        nacc = 3 if components else 1
+        partial = np.zeros((nacc, nf) + self._vnC[::-1]).transpose(0, 1, 4, 3, 2)       # every P_f F-ordered
+        sinfo = [[None] * nr for _ in range(nf)]
+        for j, spec in enumerate(self._specs):
+            dev, smu0 = handles.target(spec), spec.smu0
+            dev.grad_acc3_reset() if components else dev.grad_acc_reset()
+            wanted = np.any(weights[:, j, :] != 0, axis=0)          # receivers with a datum at this frequency
+            for r0 in range(0, nr, nb):
+                n = min(nb, nr - r0)
+                live = wanted[r0:r0 + n]
+                if not live.any():
+                    continue
+                cw = np.zeros((n, nr), dtype=dev.dtype)
+                for b in np.flatnonzero(live):
+                    cw[b, r0 + b] = 1
+                self._adjoint_sources(dev, smu0, cw, n)
+                infos = self._solve(dev, self.freqs[j], n)
+                use_adj = _first(0, nb)
+                use_adj[:n] = live
+                for b in np.flatnonzero(live):
+                    sinfo[j][r0 + b] = infos[b]
+                for c, (i0, ns) in enumerate(self._chunks):
+                    table = np.zeros((nb, nb))
+                    table[:n, :ns] = weights[i0:i0 + ns, j, r0:r0 + n].T * live[:, None]
+                    if np.any(table != 0):
+                        dev.sens_acc_add(self._slot[j] + c, smu0, _first(ns, nb), use_adj, table, split=components)
+            got = dev.grad_acc3_get() if components else (dev.grad_acc_get(),)
+            for q in range(nacc):
+                partial[q, j] = got[q].reshape(self._vnC, order='F')
+        self.sensitivity_info = sinfo
+        self.sensitivity_partial = partial if components else partial[0]
+        zeros = np.zeros((self.n_src, nf))
+        out = tuple(_sum_survey(p, zeros, self._vnC)[1] for p in partial)
+        if mapped:
+            out = tuple(d * d * o for d, o in zip(self._chain_factors(), out))
+        return out if components else out[0]
 
 
 def jvec(grid, model, src, freq, rec, v, **kwargs):

@@ -312,6 +312,28 @@ class DeviceMG:
         _lib.check(self._lib.emg3d_mg_grad_acc3_get(self._h, *(_lib.ptr(o) for o in outs)), "emg3d_mg_grad_acc3_get")
         return tuple(outs)
 
+    # ---- survey sensitivity diagonal: all pairs of adjoint and forward systems (optimize.SurveyJacobian.sensitivity_diagonal) ----
+    def sens_acc_add(self, fwd_bvec, smu0, use_fwd, use_adj, weights, split=False):
+        """``acc += weights[b_adj, b_fwd] * |(c_x + c_y) + c_z|^2`` over the pairs of an adjoint system ``b_adj`` (``use_adj[b_adj]
+        != 0``; its field ``lambda`` = system ``b_adj``'s field) and a forward system ``b_fwd`` (``use_fwd[b_fwd] != 0``; ``E`` = slice
+        ``b_fwd`` of the batched vector ``fwd_bvec``, a saved copy), ``c_c = edges2cellaverages_c(s mu_0 lambda E)``: one launch
+        (``emg3d_mg_sens_acc_add``), adjoint systems ascending in the outer loop, forward systems ascending in the inner one, a
+        pair with weight 0 skipped.  Into the accumulator of ``grad_acc_reset`` / ``grad_acc_get``; ``split=True``: ``W |c_x|^2, W
+        |c_y|^2, W |c_z|^2`` into the three of ``grad_acc3_reset`` / ``grad_acc3_get``.  The accumulator must have been reset once.
+        ``weights``: ``(nsys, nsys)`` finite doubles, uploaded into a table of the handle's own."""
+        a = complex(smu0)
+        uf, ua = self._use_flags(use_fwd, "sens_acc_add"), self._use_flags(use_adj, "sens_acc_add")
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (self.nsys, self.nsys):
+            raise ValueError(f"sens_acc_add: `weights` must have shape {(self.nsys, self.nsys)}; provided: {w.shape}.")
+        if not np.isfinite(w).all():
+            raise ValueError("sens_acc_add: `weights` must be finite.")
+        st = self._lib.emg3d_mg_sens_acc_add(self._h, int(fwd_bvec), a.real, a.imag, _lib.ptr(uf), _lib.ptr(ua), _lib.ptr(w),
+                                             int(bool(split)))
+        self._check_bvec(st, "emg3d_mg_sens_acc_add",
+                         f"sens_acc_add: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy), or the "
+                         f"accumulator was never reset (grad_acc{'3' if split else ''}_reset).")
+
     # ---- the accumulators on a model grid (optimize.SurveyJacobian(model_grid=)) ----
     def set_model_grid(self, model_grid):
         """Link the handle to the grid the model lives on (``emg3d_mg_set_model_grid``): the segment tables of volume averaging

@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 112
+#define EMG3D_HIP_ABI_VERSION 113
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -279,6 +279,21 @@ int emg3d_mg_grad_acc_get(emg3d_mg_t* mg, double* out);
 int emg3d_mg_grad_acc3_reset(emg3d_mg_t* mg);
 int emg3d_mg_grad_acc3_add(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use);
 int emg3d_mg_grad_acc3_get(emg3d_mg_t* mg, double* out_x, double* out_y, double* out_z);
+/* Survey sensitivity diagonal (optimize.SurveyJacobian.sensitivity_diagonal): diag(J^H W J) = sum over the data d of W_d |J_dj|^2.
+ * The operator is complex symmetric, so row (source s, receiver r) of J at a cell is c = c_x + c_y + c_z with
+ * c_c = edges2cellaverages_c(s mu_0 lambda_r E_s), lambda_r the solution for receiver r's adjoint source alone (it serves every
+ * source) and E_s the forward field: an all-pairs product of two sets of fields, complex before it is squared.
+ *   sens_acc_add: acc += weights[b_adj * nsys + b_fwd] * |(c_x + c_y) + c_z|^2 over the pairs, in ONE launch, one read and one write
+ *                 of acc per cell, no atomics -- adjoint systems b_adj with use_adj[b_adj] != 0 in ascending order (outer loop;
+ *                 lambda = slice b_adj of the level-0 field array), forward systems b_fwd with use_fwd[b_fwd] != 0 in ascending order
+ *                 (inner loop; E = slice b_fwd of the batched vector `fwd_bvec`, a saved copy as for grad_acc_add); a pair whose
+ *                 weight is 0 is skipped and contributes exactly nothing.  split = 0: into the accumulator of grad_acc_*;
+ *                 split != 0: W |c_x|^2, W |c_y|^2, W |c_z|^2 into the three of grad_acc3_*.  grad_acc(3)_reset and _get serve
+ *                 unchanged.  use_fwd, use_adj: nsys flags each; weights: nsys * nsys doubles, uploaded by the call into a table of
+ *                 the handle's own (allocated at the first call, counted by emg3d_mg_device_bytes).  -2: a bad fwd_bvec, an
+ *                 accumulator that was never reset, a weight that is not finite.                                           */
+int emg3d_mg_sens_acc_add(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use_fwd,
+                          const int32_t* use_adj, const double* weights, int split);
 
 /* ---- sensitivity products (optimize.Jacobian) --------------------------------------------------------------------
  * The reference (v0.17.0) has the gradient only; these are the pieces of J v and J^T w with J = d(data) / d(conductivity) for
