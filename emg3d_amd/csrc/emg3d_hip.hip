@@ -618,10 +618,9 @@ static int jvec_source_b_impl(MG<T>* m, int fwd_bvec, double smu0_re, double smu
     if (sizeof(T) == 8 && smu0_im != 0.0) return -2;
     HIP_TRY(hipSetDevice(m->device));
     Level<T>& L = *m->lv0;
-    if (fwd_bvec < 0 || fwd_bvec >= (int)m->bvecs.size()) return -2;       // a saved copy, as grad_acc_add asks
-    const T* fwd = m->bvecs[(size_t)fwd_bvec];
-    unsigned long long bits = 0;
-    for (int b = 0; b < m->nsys; ++b) if (use[b]) bits |= 1ull << b;
+    const T* fwd = m->saved_bvec(fwd_bvec);
+    if (!fwd) return -2;
+    const unsigned long long bits = m->use_bits(use);
     if (!bits) return 0;
     const double* hv[3] = {vx, vy, vz};
     const double* dv[3];
@@ -636,34 +635,60 @@ static int jvec_source_b_impl(MG<T>* m, int fwd_bvec, double smu0_re, double smu
     return finish(m);
 }
 
-// one output (gy == gz == NULL: grad = (g_x + g_y) + g_z) or the three components
-static int gradient_impl(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, double* gx, double* gy, double* gz) {
-    const bool split = gy != nullptr;
+// The shared bodies of the exports that return per-cell results.  `split` = 0: one array, the directions summed, to out[0]; 1: the
+// three directions to out[0 .. 2].
+// out[q] <- the q-th run of n doubles of the device block `src`, q = 0 (split: 0 .. 2)
+template <class T>
+static int download_parts(MG<T>* m, int split, double* const out[3], const double* src, i64 n) {
+    for (int q = 0; q < (split ? 3 : 1); ++q) HIP_TRY(m->d2h(out[q], src + q * n, (size_t)n * sizeof(double)));
+    return 0;
+}
+
+static int gradient_impl(emg3d_mg_t* mg, int split, int efield_vec, double smu0_re, double smu0_im, double* const out[3]) {
     DISPATCH(mg, {
         HIP_TRY(hipSetDevice(m->device));
-        Level<T>& L = *m->lv0;
         const T* fwd = m->vec(efield_vec);
         if (!fwd || efield_vec == -2) return -2;           // the forward field must be a saved copy, not the live field
         // the gradient (nC doubles, or 3 nC) is staged in the residual buffer (3 nC * 8 < nE * sizeof(T))
-        double* dg = reinterpret_cast<double*>(L.r);
-        const i64 n = L.nCells;
-        const unsigned blocks = (unsigned)((n + 255) / 256);
+        double* dg = reinterpret_cast<double*>(m->lv0->r);
+        const i64 n = m->lv0->nCells;
+        double* g[3];
+        for (int q = 0; q < 3; ++q) g[q] = (q == 0 || split) ? dg + q * n : nullptr;
         const T* bwd = m->sel_e();
         if (m->broken) return (int)hipErrorOutOfMemory;
-        if (split)
-            hipLaunchKernelGGL((k_gradient<T, true>), dim3(blocks), dim3(256), 0, m->stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd, bwd,
-                               smu0_re, smu0_im, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], dg, dg + n, dg + 2 * n);
-        else
-            hipLaunchKernelGGL((k_gradient<T, false>), dim3(blocks), dim3(256), 0, m->stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd, bwd,
-                               smu0_re, smu0_im, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], dg, (double*)nullptr,
-                               (double*)nullptr);
+        MG_CELL_LAUNCH(*m, k_gradient, split, g, fwd, bwd, smu0_re, smu0_im);
         m->check_launch();
-        HIP_TRY(m->d2h(gx, dg, (size_t)n * sizeof(double)));
-        if (split) {
-            HIP_TRY(m->d2h(gy, dg + n, (size_t)n * sizeof(double)));
-            HIP_TRY(m->d2h(gz, dg + 2 * n, (size_t)n * sizeof(double)));
-        }
+        { const int st = download_parts(m, split, out, dg, n); if (st) return st; }
         return finish(m);
+    });
+}
+
+static int acc_reset_impl(emg3d_mg_t* mg, int split) {
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        const int st = m->acc_reset(split);
+        return st ? st : finish(m);
+    });
+}
+
+static int acc_add_impl(emg3d_mg_t* mg, int split, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use) {
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        const int st = m->acc_add(split, fwd_bvec, smu0_re, smu0_im, use);
+        return st ? st : finish(m);
+    });
+}
+
+// the accumulator(s) as they are, or (on_model) through regrid_acc on the model grid; never reset: zeros
+static int acc_get_impl(emg3d_mg_t* mg, int split, bool on_model, double* const out[3]) {
+    DISPATCH(mg, {
+        if (on_model && (!m->mgl.set || !m->mgl.factors)) return -7;
+        HIP_TRY(hipSetDevice(m->device));
+        int st = m->acc_ready(split);
+        if (!st && on_model) st = m->regrid_acc(split);
+        if (!st) st = on_model ? download_parts(m, split, out, m->mgl.res, m->mgl.nM)
+                               : download_parts(m, split, out, m->cell_acc[split], m->lv0->nCells);
+        return st ? st : finish(m);
     });
 }
 
@@ -1162,31 +1187,14 @@ int emg3d_mg_set_regrid_factors(emg3d_mg_t* mg, const double* F_x, const double*
 
 int emg3d_mg_grad_acc_get_model(emg3d_mg_t* mg, double* out) {
     if (!mg || !out) return -2;
-    DISPATCH(mg, {
-        if (!m->mgl.set || !m->mgl.factors) return -7;
-        HIP_TRY(hipSetDevice(m->device));
-        if (!m->grad_acc) { const int st = m->grad_acc_reset(); if (st) return st; }
-        const int st = m->regrid_acc(m->grad_acc, 1);
-        if (st) return st;
-        HIP_TRY(m->d2h(out, m->mgl.res, (size_t)m->mgl.nM * sizeof(double)));
-        return finish(m);
-    });
+    double* const o[3] = {out, nullptr, nullptr};
+    return acc_get_impl(mg, 0, true, o);
 }
 
 int emg3d_mg_grad_acc3_get_model(emg3d_mg_t* mg, double* out_x, double* out_y, double* out_z) {
     if (!mg || !out_x || !out_y || !out_z) return -2;
-    DISPATCH(mg, {
-        if (!m->mgl.set || !m->mgl.factors) return -7;
-        HIP_TRY(hipSetDevice(m->device));
-        if (!m->grad_acc3) { const int st = m->grad_acc3_reset(); if (st) return st; }
-        const int st = m->regrid_acc(m->grad_acc3, 3);
-        if (st) return st;
-        const i64 n = m->mgl.nM;
-        HIP_TRY(m->d2h(out_x, m->mgl.res, (size_t)n * sizeof(double)));
-        HIP_TRY(m->d2h(out_y, m->mgl.res + n, (size_t)n * sizeof(double)));
-        HIP_TRY(m->d2h(out_z, m->mgl.res + 2 * n, (size_t)n * sizeof(double)));
-        return finish(m);
-    });
+    double* const o[3] = {out_x, out_y, out_z};
+    return acc_get_impl(mg, 1, true, o);
 }
 
 int emg3d_interp3d_grid(int dtype, int64_t nx, int64_t ny, int64_t nz, const double* px, const double* py, const double* pz,
@@ -1203,72 +1211,37 @@ int emg3d_interp3d_grid(int dtype, int64_t nx, int64_t ny, int64_t nz, const dou
 
 int emg3d_mg_gradient(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, double* grad) {
     if (!mg || !grad) return -2;
-    return gradient_impl(mg, efield_vec, smu0_re, smu0_im, grad, nullptr, nullptr);
+    double* const o[3] = {grad, nullptr, nullptr};
+    return gradient_impl(mg, 0, efield_vec, smu0_re, smu0_im, o);
 }
 
 int emg3d_mg_gradient3(emg3d_mg_t* mg, int efield_vec, double smu0_re, double smu0_im, double* grad_x, double* grad_y,
                        double* grad_z) {
     if (!mg || !grad_x || !grad_y || !grad_z) return -2;
-    return gradient_impl(mg, efield_vec, smu0_re, smu0_im, grad_x, grad_y, grad_z);
+    double* const o[3] = {grad_x, grad_y, grad_z};
+    return gradient_impl(mg, 1, efield_vec, smu0_re, smu0_im, o);
 }
 
-int emg3d_mg_grad_acc_reset(emg3d_mg_t* mg) {
-    if (!mg) return -2;
-    DISPATCH(mg, {
-        HIP_TRY(hipSetDevice(m->device));
-        const int st = m->grad_acc_reset();
-        return st ? st : finish(m);
-    });
-}
+int emg3d_mg_grad_acc_reset(emg3d_mg_t* mg) { return mg ? acc_reset_impl(mg, 0) : -2; }
+int emg3d_mg_grad_acc3_reset(emg3d_mg_t* mg) { return mg ? acc_reset_impl(mg, 1) : -2; }
 
 int emg3d_mg_grad_acc_add(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use) {
-    if (!mg || !use) return -2;
-    DISPATCH(mg, {
-        HIP_TRY(hipSetDevice(m->device));
-        const int st = m->grad_acc_add(fwd_bvec, smu0_re, smu0_im, use);
-        return st ? st : finish(m);
-    });
+    return (mg && use) ? acc_add_impl(mg, 0, fwd_bvec, smu0_re, smu0_im, use) : -2;
+}
+int emg3d_mg_grad_acc3_add(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use) {
+    return (mg && use) ? acc_add_impl(mg, 1, fwd_bvec, smu0_re, smu0_im, use) : -2;
 }
 
 int emg3d_mg_grad_acc_get(emg3d_mg_t* mg, double* out) {
     if (!mg || !out) return -2;
-    DISPATCH(mg, {
-        HIP_TRY(hipSetDevice(m->device));
-        if (!m->grad_acc) { const int st = m->grad_acc_reset(); if (st) return st; }
-        HIP_TRY(m->d2h(out, m->grad_acc, (size_t)m->lv0->nCells * sizeof(double)));
-        return finish(m);
-    });
-}
-
-int emg3d_mg_grad_acc3_reset(emg3d_mg_t* mg) {
-    if (!mg) return -2;
-    DISPATCH(mg, {
-        HIP_TRY(hipSetDevice(m->device));
-        const int st = m->grad_acc3_reset();
-        return st ? st : finish(m);
-    });
-}
-
-int emg3d_mg_grad_acc3_add(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use) {
-    if (!mg || !use) return -2;
-    DISPATCH(mg, {
-        HIP_TRY(hipSetDevice(m->device));
-        const int st = m->grad_acc3_add(fwd_bvec, smu0_re, smu0_im, use);
-        return st ? st : finish(m);
-    });
+    double* const o[3] = {out, nullptr, nullptr};
+    return acc_get_impl(mg, 0, false, o);
 }
 
 int emg3d_mg_grad_acc3_get(emg3d_mg_t* mg, double* out_x, double* out_y, double* out_z) {
     if (!mg || !out_x || !out_y || !out_z) return -2;
-    DISPATCH(mg, {
-        HIP_TRY(hipSetDevice(m->device));
-        if (!m->grad_acc3) { const int st = m->grad_acc3_reset(); if (st) return st; }
-        const i64 n = m->lv0->nCells;
-        HIP_TRY(m->d2h(out_x, m->grad_acc3, (size_t)n * sizeof(double)));
-        HIP_TRY(m->d2h(out_y, m->grad_acc3 + n, (size_t)n * sizeof(double)));
-        HIP_TRY(m->d2h(out_z, m->grad_acc3 + 2 * n, (size_t)n * sizeof(double)));
-        return finish(m);
-    });
+    double* const o[3] = {out_x, out_y, out_z};
+    return acc_get_impl(mg, 1, false, o);
 }
 
 int emg3d_mg_sens_acc_add(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use_fwd, const int32_t* use_adj,

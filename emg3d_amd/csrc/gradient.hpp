@@ -6,6 +6,8 @@
 //   k_gradient_acc = the same for all systems of a batch in one launch, added into a per-cell accumulator in system order;
 //   k_sens_acc    = the survey sensitivity diagonal: W |row|^2 for all pairs of an adjoint and a forward system, into the same
 //                   accumulators (no counterpart in the reference).
+// The last three are the per-cell kernels: one thread per cell behind the same cell_frame, SPLIT = the sum of the three directions
+// or the directions apart, launched through MG_CELL_LAUNCH (mg.hpp), the accumulators those of MG::cell_acc.
 // Gather form: one thread per CELL sums the contributions of its 12 edges in the order in which the reference's
 // loops (iz, iy, ix ascending, four statements per edge) add them -- deterministic and equal to the reference's
 // accumulation order, no atomics.
@@ -83,17 +85,39 @@ __device__ __forceinline__ void grad_cell(const i64 j[3], const i64 nC[3], doubl
     }
 }
 
+// The frame of one thread of the per-cell kernels (k_gradient, k_gradient_acc, k_sens_acc): its cell idx -> (j0, j1, j2), x fastest,
+// and vol = (hx*hy)*hz (meshes cell_volumes).  false: the thread has no cell.
+__device__ __forceinline__ bool cell_frame(i64 n0, i64 n1, i64 n2, const double* h0, const double* h1, const double* h2, i64& idx,
+                                           i64 j[3], double& vol) {
+    idx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n0 * n1 * n2) return false;
+    j[0] = idx % n0; j[1] = (idx / n0) % n1; j[2] = idx / (n0 * n1);
+    vol = (h0[j[0]] * h1[j[1]]) * h2[j[2]];
+    return true;
+}
+
+// The running sums of a cell: one read and one write of acc (SPLIT: of acc, acc1, acc2) per thread and launch.
+template <bool SPLIT>
+__device__ __forceinline__ void acc_load(i64 idx, const double* acc, const double* acc1, const double* acc2, double& run, double& run1,
+                                         double& run2) {
+    run = acc[idx]; run1 = 0.0; run2 = 0.0;
+    if (SPLIT) { run1 = acc1[idx]; run2 = acc2[idx]; }
+}
+template <bool SPLIT>
+__device__ __forceinline__ void acc_store(i64 idx, double* acc, double* acc1, double* acc2, double run, double run1, double run2) {
+    acc[idx] = run;
+    if (SPLIT) { acc1[idx] = run1; acc2[idx] = run2; }
+}
+
 // grad[cell] = sum_c edges2cellaverages_c( -Re(b * e * smu0) ), vol = (hx*hy)*hz (meshes cell_volumes).
 // SPLIT: the three components go to g0, g1, g2 instead (emg3d_mg_gradient3); their sum (g0 + g1) + g2 is the one-output result.
 template <class T, bool SPLIT>
 __global__ void k_gradient(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* e, const T* b, double sr, double si,
                            const double* h0, const double* h1, const double* h2, double* g0, double* g1, double* g2) {
     const i64 nC[3] = {n0, n1, n2};
-    const i64 n = n0 * n1 * n2;
-    const i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n) return;
-    const i64 j[3] = {idx % n0, (idx / n0) % n1, idx / (n0 * n1)};
-    const double vol = (h0[j[0]] * h1[j[1]]) * h2[j[2]];
+    i64 idx, j[3];
+    double vol;
+    if (!cell_frame(n0, n1, n2, h0, h1, h2, idx, j, vol)) return;
     double g[3];
     grad_cell<T>(j, nC, vol, fl, e, b, sr, si, g);
     if (SPLIT) { g0[idx] = g[0]; g1[idx] = g[1]; g2[idx] = g[2]; }
@@ -111,13 +135,11 @@ __global__ void k_gradient_acc(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* 
                                double sr, double si, const double* h0, const double* h1, const double* h2, double* acc, double* acc1,
                                double* acc2) {
     const i64 nC[3] = {n0, n1, n2};
-    const i64 n = n0 * n1 * n2;
-    const i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n) return;
-    const i64 j[3] = {idx % n0, (idx / n0) % n1, idx / (n0 * n1)};
-    const double vol = (h0[j[0]] * h1[j[1]]) * h2[j[2]];
-    double run = acc[idx], run1 = 0.0, run2 = 0.0;
-    if (SPLIT) { run1 = acc1[idx]; run2 = acc2[idx]; }
+    i64 idx, j[3];
+    double vol;
+    if (!cell_frame(n0, n1, n2, h0, h1, h2, idx, j, vol)) return;
+    double run, run1, run2;
+    acc_load<SPLIT>(idx, acc, acc1, acc2, run, run1, run2);
     for (int b = 0; b < nsys; ++b) {
         if (!((use >> b) & 1ull)) continue;
         double g[3];
@@ -125,8 +147,7 @@ __global__ void k_gradient_acc(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* 
         if (SPLIT) { run += g[0]; run1 += g[1]; run2 += g[2]; }
         else run += (g[0] + g[1]) + g[2];
     }
-    acc[idx] = run;
-    if (SPLIT) { acc1[idx] = run1; acc2[idx] = run2; }
+    acc_store<SPLIT>(idx, acc, acc1, acc2, run, run1, run2);
 }
 
 // ---- survey sensitivity diagonal: diag(J^H W J) (optimize.SurveyJacobian.sensitivity_diagonal) -----------------------------
@@ -197,19 +218,17 @@ __global__ void __launch_bounds__(256) k_sens_acc(i64 n0, i64 n1, i64 n2, FieldL
                            unsigned long long use_adj, const double* W, double sr, double si, const double* h0, const double* h1,
                            const double* h2, double* acc, double* acc1, double* acc2) {
     const i64 nC[3] = {n0, n1, n2};
-    const i64 n = n0 * n1 * n2;
-    const i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n) return;
-    const i64 j[3] = {idx % n0, (idx / n0) % n1, idx / (n0 * n1)};
-    const double vol = (h0[j[0]] * h1[j[1]]) * h2[j[2]];
+    i64 idx, j[3];
+    double vol;
+    if (!cell_frame(n0, n1, n2, h0, h1, h2, idx, j, vol)) return;
     if (nsys < 64) {                    // (never a shift by 64: nsys = 64 with bit 63 set is a valid batch)
         use_fwd &= (1ull << nsys) - 1ull;
         use_adj &= (1ull << nsys) - 1ull;
     }
     CellEdges<i64> o;
     cell_edge_offsets(j, fl, o);
-    double run = acc[idx], run1 = 0.0, run2 = 0.0;
-    if (SPLIT) { run1 = acc1[idx]; run2 = acc2[idx]; }
+    double run, run1, run2;
+    acc_load<SPLIT>(idx, acc, acc1, acc2, run, run1, run2);
     for (unsigned long long ra = use_adj; ra; ra &= ra - 1ull) {          // (wave-uniform: the masks are kernel arguments)
         const int br = __builtin_ctzll(ra);
         const double* Wr = W + (i64)br * nsys;
@@ -227,8 +246,7 @@ __global__ void __launch_bounds__(256) k_sens_acc(i64 n0, i64 n1, i64 n2, FieldL
             else run += w * sens_abs2((cc[0] + cc[1]) + cc[2]);
         }
     }
-    acc[idx] = run;
-    if (SPLIT) { acc1[idx] = run1; acc2[idx] = run2; }
+    acc_store<SPLIT>(idx, acc, acc1, acc2, run, run1, run2);
 }
 
 // ---- the transpose: cells -> edges (J v of optimize.Jacobian) ---------------------------------------------------------------

@@ -21,8 +21,8 @@
 #include "common.hpp"
 #include "smooth.hpp"
 #include "stencil.hpp"
-#include "gradient.hpp"        // k_gradient_acc (grad_acc_add)
-#include "regrid.hpp"          // k_volume_average_adjoint (grad_acc_get_model)
+#include "gradient.hpp"        // k_gradient_acc, k_sens_acc (acc_add, sens_acc_add)
+#include "regrid.hpp"          // k_volume_average_adjoint (regrid_acc)
 #include "smooth_qpl.hpp"
 #include "smooth_qc.hpp"
 #include "smooth_thm.hpp"
@@ -248,6 +248,20 @@ struct emg3d_mg {
 // handle is missing, and a kernel that touches a null pointer takes the whole PROCESS down with a memory fault instead of
 // returning the error.  A broken handle launches nothing; every entry point answers hipErrorOutOfMemory until it is destroyed.
 #define MG_LAUNCH(...) do { if (!broken) hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+
+// One launch of a per-cell kernel K<T, SPLIT> of gradient.hpp on level 0 of the handle `mg` (one thread per cell, 256 per block),
+// SPLIT chosen by `split` here and nowhere else: nC and the field layout go in front of the kernel's own arguments (...), the widths
+// and the three output pointers `a` behind them.
+#define MG_CELL_LAUNCH_(mg, K, S, a, ...)                                                                                          \
+    hipLaunchKernelGGL((K<T, S>), dim3((unsigned)(((mg).lv0->nCells + 255) / 256)), dim3(256), 0, (mg).stream, (mg).lv0->nC[0],     \
+                       (mg).lv0->nC[1], (mg).lv0->nC[2], (mg).lv0->fl, __VA_ARGS__, (const double*)(mg).lv0->h[0],                 \
+                       (const double*)(mg).lv0->h[1], (const double*)(mg).lv0->h[2], (a)[0], (a)[1], (a)[2])
+#define MG_CELL_LAUNCH(mg, K, split, a, ...)                            \
+    do {                                                                \
+        if ((mg).broken) break;                                         \
+        if (split) MG_CELL_LAUNCH_(mg, K, true, a, __VA_ARGS__);        \
+        else MG_CELL_LAUNCH_(mg, K, false, a, __VA_ARGS__);             \
+    } while (0)
 
 // The device's part of the selection knobs (sweep_plan.hpp): its SIMDs, its LDS per workgroup, and whether k_line_sweep_tha gets the
 // dynamic LDS it needs -- more than 64 KB must be asked for per instantiation and device, once (tha_attrs, on the current device).
@@ -923,93 +937,66 @@ struct MG : emg3d_mg {
         return err;
     }
 
-    // ------------------------------------------- survey gradient accumulator (emg3d_mg_grad_acc_*)
-    // nC doubles of the handle's own (not the residual buffer emg3d_mg_gradient stages in): allocated on first use, counted in
-    // `bytes`, freed with the handle; cycles, set_smu0 and set_mask do not touch it.
-    double* grad_acc = nullptr;
-    int grad_acc_reset() {
-        if (!grad_acc) grad_acc = dalloc<double>(lv0->nCells);
-        if (!grad_acc) return err ? err : (int)hipErrorOutOfMemory;
-        hipMemsetAsync(grad_acc, 0, (size_t)lv0->nCells * sizeof(double), stream);
+    // ------------------------------------------- per-cell accumulators (emg3d_mg_grad_acc(3)_*, emg3d_mg_sens_acc_add)
+    // Two blocks of the handle's own (not the residual buffer emg3d_mg_gradient stages in), indexed by `split`: cell_acc[0] = nC
+    // doubles, the summed form; cell_acc[1] = 3 nC doubles [acc_x | acc_y | acc_z], the per-direction form (optimize.SurveyJacobian).
+    // Independent of each other, each allocated on first use, counted in `bytes`, freed with the handle; cycles, set_smu0 and
+    // set_mask do not touch them.
+    double* cell_acc[2] = {nullptr, nullptr};
+    int acc_reset(int split) {
+        const i64 n = (split ? 3 : 1) * lv0->nCells;
+        if (!cell_acc[split]) cell_acc[split] = dalloc<double>(n);
+        if (!cell_acc[split]) return err ? err : (int)hipErrorOutOfMemory;
+        hipMemsetAsync(cell_acc[split], 0, (size_t)n * sizeof(double), stream);
         return 0;
     }
-    // acc += g_b for the systems with use[b] != 0, ascending b, in ONE launch (k_gradient_acc): forward fields = batched vector
-    // `fwd_bvec` (a saved copy, not the live field array), back-propagated fields = the level-0 field array.
-    int grad_acc_add(int fwd_bvec, double sr, double si, const int32_t* use) {
-        if (fwd_bvec < 0 || fwd_bvec >= (int)bvecs.size()) return -2;
-        if (!grad_acc) { const int st = grad_acc_reset(); if (st) return st; }
-        Level<T>& L = *lv0;
+    int acc_ready(int split) { return cell_acc[split] ? 0 : acc_reset(split); }         // first use: allocated and zero
+    // what the per-cell kernels take as acc, acc1, acc2
+    void acc_ptrs(int split, double* out[3]) const {
+        out[0] = cell_acc[split];
+        out[1] = split ? cell_acc[1] + lv0->nCells : nullptr;
+        out[2] = split ? cell_acc[1] + 2 * lv0->nCells : nullptr;
+    }
+    unsigned long long use_bits(const int32_t* use) const {         // bit b = use[b] != 0, b = 0 .. nsys-1
         unsigned long long bits = 0;
         for (int b = 0; b < nsys; ++b) if (use[b]) bits |= 1ull << b;
-        const T* fwd = bvecs[(size_t)fwd_bvec];
-        e_to_ref(L);
-        const T* bwd = L.e;
-        const unsigned blocks = (unsigned)((L.nCells + 255) / 256);
-        MG_LAUNCH((k_gradient_acc<T, false>), dim3(blocks), dim3(256), 0, stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd, bwd, L.nE, nsys,
-                  bits, sr, si, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], grad_acc, (double*)nullptr,
-                  (double*)nullptr);
-        check_launch();
-        return err;
+        return bits;
     }
-    // The same per direction (emg3d_mg_grad_acc3_*, optimize.SurveyJacobian): three accumulators [acc_x | acc_y | acc_z] of nC doubles
-    // each in one block of the handle's own, independent of grad_acc; acc_c += g_c,b, g_c,b bit for bit emg3d_mg_gradient3's.
-    double* grad_acc3 = nullptr;
-    int grad_acc3_reset() {
-        if (!grad_acc3) grad_acc3 = dalloc<double>(3 * lv0->nCells);
-        if (!grad_acc3) return err ? err : (int)hipErrorOutOfMemory;
-        hipMemsetAsync(grad_acc3, 0, (size_t)(3 * lv0->nCells) * sizeof(double), stream);
-        return 0;
-    }
-    int grad_acc3_add(int fwd_bvec, double sr, double si, const int32_t* use) {
-        if (fwd_bvec < 0 || fwd_bvec >= (int)bvecs.size()) return -2;
-        if (!grad_acc3) { const int st = grad_acc3_reset(); if (st) return st; }
-        Level<T>& L = *lv0;
-        unsigned long long bits = 0;
-        for (int b = 0; b < nsys; ++b) if (use[b]) bits |= 1ull << b;
-        const T* fwd = bvecs[(size_t)fwd_bvec];
-        e_to_ref(L);
-        const T* bwd = L.e;
-        const unsigned blocks = (unsigned)((L.nCells + 255) / 256);
-        MG_LAUNCH((k_gradient_acc<T, true>), dim3(blocks), dim3(256), 0, stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd, bwd, L.nE, nsys,
-                  bits, sr, si, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], grad_acc3, grad_acc3 + L.nCells,
-                  grad_acc3 + 2 * L.nCells);
+    // the forward fields of a batch: a saved copy, not the live field array (which holds the back-propagated fields); nullptr: no such
+    const T* saved_bvec(int id) const { return (id < 0 || id >= (int)bvecs.size()) ? nullptr : bvecs[(size_t)id]; }
+    // acc += g_b (split: acc_c += g_c,b, bit for bit emg3d_mg_gradient3's) for the systems with use[b] != 0, ascending b, in ONE
+    // launch (k_gradient_acc): forward fields = batched vector `fwd_bvec`, back-propagated fields = the level-0 field array.
+    int acc_add(int split, int fwd_bvec, double sr, double si, const int32_t* use) {
+        const T* fwd = saved_bvec(fwd_bvec);
+        if (!fwd) return -2;
+        { const int st = acc_ready(split); if (st) return st; }
+        double* a[3];
+        acc_ptrs(split, a);
+        e_to_ref(*lv0);
+        MG_CELL_LAUNCH(*this, k_gradient_acc, split, a, fwd, (const T*)lv0->e, lv0->nE, nsys, use_bits(use), sr, si);
         check_launch();
         return err;
     }
     // Survey sensitivity diagonal (emg3d_mg_sens_acc_add, k_sens_acc): acc += W[b_r nsys + b_s] |row(b_r, b_s)|^2 over all pairs of an
     // adjoint system b_r (slice of the level-0 field array) and a forward system b_s (slice of batched vector `fwd_bvec`), into
-    // grad_acc (split = 0) or the three of grad_acc3 (split = 1), in ONE launch.  The weight table is nsys x nsys doubles of the
-    // handle's own, allocated at the first call (counted in `bytes`; nsys is fixed once a batched vector exists) and uploaded by
-    // every call.  -2: a bad vector, an accumulator that was never reset, a non-finite weight.
+    // cell_acc[split], in ONE launch.  The weight table is nsys x nsys doubles of the handle's own, allocated at the first call
+    // (counted in `bytes`; nsys is fixed once a batched vector exists) and uploaded by every call.  -2: a bad vector, an accumulator
+    // that was never reset, a non-finite weight.
     double* sens_w = nullptr;
     int sens_acc_add(int fwd_bvec, double sr, double si, const int32_t* use_fwd, const int32_t* use_adj, const double* weights, int split) {
-        if (fwd_bvec < 0 || fwd_bvec >= (int)bvecs.size()) return -2;
-        if (split ? !grad_acc3 : !grad_acc) return -2;
+        const T* fwd = saved_bvec(fwd_bvec);
+        if (!fwd || !cell_acc[split]) return -2;
         const i64 nw = (i64)nsys * nsys;
         for (i64 q = 0; q < nw; ++q) if (!std::isfinite(weights[q])) return -2;
         if (!sens_w) sens_w = dalloc<double>(nw);
         if (!sens_w) return err ? err : (int)hipErrorOutOfMemory;
         const hipError_t st = h2d(sens_w, weights, (size_t)nw * sizeof(double));
         if (st != hipSuccess) return (int)st;
-        Level<T>& L = *lv0;
-        unsigned long long bf = 0, ba = 0;
-        for (int b = 0; b < nsys; ++b) {
-            if (use_fwd[b]) bf |= 1ull << b;
-            if (use_adj[b]) ba |= 1ull << b;
-        }
-        const T* fwd = bvecs[(size_t)fwd_bvec];
-        e_to_ref(L);
-        const T* adj = L.e;
-        const unsigned blocks = (unsigned)((L.nCells + 255) / 256);
-        double* a0 = split ? grad_acc3 : grad_acc;
-        double* a1 = split ? grad_acc3 + L.nCells : nullptr;
-        double* a2 = split ? grad_acc3 + 2 * L.nCells : nullptr;
-        if (split)
-            MG_LAUNCH((k_sens_acc<T, true>), dim3(blocks), dim3(256), 0, stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd, adj, L.nE, nsys, bf,
-                      ba, (const double*)sens_w, sr, si, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], a0, a1, a2);
-        else
-            MG_LAUNCH((k_sens_acc<T, false>), dim3(blocks), dim3(256), 0, stream, L.nC[0], L.nC[1], L.nC[2], L.fl, fwd, adj, L.nE, nsys, bf,
-                      ba, (const double*)sens_w, sr, si, (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], a0, a1, a2);
+        double* a[3];
+        acc_ptrs(split, a);
+        e_to_ref(*lv0);
+        MG_CELL_LAUNCH(*this, k_sens_acc, split, a, fwd, (const T*)lv0->e, lv0->nE, nsys, use_bits(use_fwd), use_bits(use_adj),
+                       (const double*)sens_w, sr, si);
         check_launch();
         return err;
     }
@@ -1085,10 +1072,12 @@ struct MG : emg3d_mg {
         mgl.factors = true;
         return 0;
     }
-    // res[k] = Q_k (.) A^T (F_k (.) acc[k]) for k = 0 .. ndir-1 (acc: ndir accumulators of nC doubles, left as they are)
-    int regrid_acc(const double* acc, int ndir) {
+    // res[k] = Q_k (.) A^T (F_k (.) acc[k]) for the ndir = 1 (split: 3) accumulators of cell_acc[split], which are left as they are
+    int regrid_acc(int split) {
         if (!mgl.set || !mgl.factors) return -7;
         Level<T>& L = *lv0;
+        const double* acc = cell_acc[split];
+        const int ndir = split ? 3 : 1;
         VolAvgAdjAxes ax;
         for (int a = 0; a < 3; ++a) { ax.iptr[a] = mgl.iptr[a]; ax.out[a] = mgl.out[a]; ax.w[a] = mgl.w[a]; }
         for (int k = 0; k < ndir && !broken; ++k)

@@ -79,6 +79,11 @@ def _first(n, nb):
     return f
 
 
+def _each(got):
+    """The arrays a ``DeviceMG.grad_acc_get*`` call returned: the one, or the three of ``components=True``."""
+    return got if isinstance(got, tuple) else (got,)
+
+
 def _adjoint_source(dev, rec, smu0, cw, *, method, exact, electric):
     """Residual / adjoint source of the selected system of ``dev`` from ``cw = conj(weights * residual)`` (resp. ``conj(w)``; NaN
     already replaced by 0), one value per receiver.  Returns whether a source was set -- if not, the source is left as it was.
@@ -927,7 +932,7 @@ class SurveyJacobian(_JacobianBase):
             dev, smu0 = handles.target(spec), spec.smu0
             real = dev.dtype.kind != 'c'
             if adj:
-                dev.grad_acc3_reset() if components else dev.grad_acc_reset()
+                dev.grad_acc_reset(components)
             for c, (i0, n) in enumerate(self._chunks):
                 slot = self._slot[j] + c
                 if vec is not None:
@@ -953,17 +958,11 @@ class SurveyJacobian(_JacobianBase):
                 for b in range(n):
                     if live[b]:
                         binfo[i0 + b][j] = infos[b]
-                if components:
-                    dev.grad_acc3_add(slot, smu0, use)
-                else:
-                    dev.grad_acc_add(slot, smu0, use)
+                dev.grad_acc_add(slot, smu0, use, components)
             if adj:
-                if on_model:
-                    got = dev.grad_acc3_get_model() if components else (dev.grad_acc_get_model(),)
-                else:
-                    got = dev.grad_acc3_get() if components else (dev.grad_acc_get(),)
-                for q in range(nacc):
-                    partial[q, j] = got[q].reshape(self._vnM, order='F')
+                got = dev.grad_acc_get_model(components) if on_model else dev.grad_acc_get(components)
+                for q, g in enumerate(_each(got)):
+                    partial[q, j] = g.reshape(self._vnM, order='F')
         return dd, jinfo, partial, binfo
 
     def _result(self, partial, components):
@@ -1067,7 +1066,7 @@ class SurveyJacobian(_JacobianBase):
         sinfo = [[None] * nr for _ in range(nf)]
         for j, spec in enumerate(self._specs):
             dev, smu0 = handles.target(spec), spec.smu0
-            dev.grad_acc3_reset() if components else dev.grad_acc_reset()
+            dev.grad_acc_reset(components)
             wanted = np.any(weights[:, j, :] != 0, axis=0)          # receivers with a datum at this frequency
             for r0 in range(0, nr, nb):
                 n = min(nb, nr - r0)
@@ -1087,10 +1086,9 @@ class SurveyJacobian(_JacobianBase):
                     table = np.zeros((nb, nb))
                     table[:n, :ns] = weights[i0:i0 + ns, j, r0:r0 + n].T * live[:, None]
                     if np.any(table != 0):
-                        dev.sens_acc_add(self._slot[j] + c, smu0, _first(ns, nb), use_adj, table, split=components)
-            got = dev.grad_acc3_get() if components else (dev.grad_acc_get(),)
-            for q in range(nacc):
-                partial[q, j] = got[q].reshape(self._vnC, order='F')
+                        dev.sens_acc_add(self._slot[j] + c, smu0, _first(ns, nb), use_adj, table, components=components)
+            for q, g in enumerate(_each(dev.grad_acc_get(components))):
+                partial[q, j] = g.reshape(self._vnC, order='F')
         self.sensitivity_info = sinfo
         self.sensitivity_partial = partial if components else partial[0]
         zeros = np.zeros((self.n_src, nf))

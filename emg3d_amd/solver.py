@@ -258,26 +258,38 @@ class DeviceMG:
                    "emg3d_mg_gradient")
         return out
 
-    # ---- survey gradient: the gradients of all systems of a batch, summed on the device (optimize.survey_gradient) ----
-    def grad_acc_reset(self):
-        """Zero the handle's gradient accumulator (``nC`` doubles of its own, allocated on first use; cycles, ``set_smu0`` and
-        ``set_mask`` leave it alone)."""
-        _lib.check(self._lib.emg3d_mg_grad_acc_reset(self._h), "emg3d_mg_grad_acc_reset")
+    # ---- per-cell accumulators of the handle: the gradients of all systems of a batch, summed on the device ----
+    # Two independent blocks: one array of ``nC`` doubles (optimize.survey_gradient), and with ``components=True`` three, one per
+    # direction (optimize.SurveyJacobian).  The C ABI has one entry point per form: name + '3'.
+    def _acc_call(self, name, components, *args):
+        name = f"emg3d_mg_grad_acc{'3' if components else ''}_{name}"
+        return getattr(self._lib, name)(self._h, *args), name
 
-    def grad_acc_add(self, fwd_bvec, smu0, use):
+    def _acc_out(self, n, components):
+        """Where a ``get`` writes and what it returns: one array of ``n`` doubles, or the pointers and the tuple of three."""
+        outs = [np.empty(n, dtype=np.float64) for _ in range(3 if components else 1)]
+        return [_lib.ptr(o) for o in outs], (tuple(outs) if components else outs[0])
+
+    def grad_acc_reset(self, components=False):
+        """Zero the handle's gradient accumulator (``nC`` doubles of its own, allocated on first use; cycles, ``set_smu0`` and
+        ``set_mask`` leave it alone).  ``components=True``: the three per-direction accumulators instead (``nC`` doubles each)."""
+        _lib.check(*self._acc_call("reset", components))
+
+    def grad_acc_add(self, fwd_bvec, smu0, use, components=False):
         """``acc = (((acc + g_0) + g_1) + ...)`` over the systems ``b`` with ``use[b] != 0`` in ascending order, in one launch:
         ``g_b`` is bit for bit ``gradient()`` of system ``b`` -- forward field = slice ``b`` of the batched vector ``fwd_bvec``
-        (``bvec_copy(fwd_bvec, EFIELD)``; not the live field), back-propagated field = system ``b``'s field."""
+        (``bvec_copy(fwd_bvec, EFIELD)``; not the live field), back-propagated field = system ``b``'s field.  ``components=True``:
+        ``acc_c = (((acc_c + g_c,0) + g_c,1) + ...)`` for ``c = x, y, z``, ``g_c,b`` bit for bit ``gradient(components=True)``."""
         a = complex(smu0)
-        u = self._use_flags(use, "grad_acc_add")
-        st = self._lib.emg3d_mg_grad_acc_add(self._h, int(fwd_bvec), a.real, a.imag, _lib.ptr(u))
-        self._check_bvec(st, "emg3d_mg_grad_acc_add",
-                         f"grad_acc_add: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy).")
+        what = f"grad_acc{'3' if components else ''}_add"
+        u = self._use_flags(use, what)
+        st, name = self._acc_call("add", components, int(fwd_bvec), a.real, a.imag, _lib.ptr(u))
+        self._check_bvec(st, name, f"{what}: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy).")
 
-    def grad_acc_get(self):
-        """The accumulator: ``nC`` doubles, F-ordered."""
-        out = np.empty(self.nC, dtype=np.float64)
-        _lib.check(self._lib.emg3d_mg_grad_acc_get(self._h, _lib.ptr(out)), "emg3d_mg_grad_acc_get")
+    def grad_acc_get(self, components=False):
+        """The accumulator: ``nC`` doubles, F-ordered.  ``components=True``: the three ``(acc_x, acc_y, acc_z)``."""
+        ptrs, out = self._acc_out(self.nC, components)
+        _lib.check(*self._acc_call("get", components, *ptrs))
         return out
 
     def _use_flags(self, use, what):
@@ -292,35 +304,29 @@ class DeviceMG:
             raise ValueError(message)
         _lib.check(st, name)
 
-    # ---- the same per direction: three accumulators, independent of the one above (optimize.SurveyJacobian) ----
+    # the per-direction form under its own names
     def grad_acc3_reset(self):
-        """Zero the handle's three per-direction gradient accumulators (``nC`` doubles each, allocated on first use)."""
-        _lib.check(self._lib.emg3d_mg_grad_acc3_reset(self._h), "emg3d_mg_grad_acc3_reset")
+        self.grad_acc_reset(components=True)
 
     def grad_acc3_add(self, fwd_bvec, smu0, use):
-        """``acc_c = (((acc_c + g_c,0) + g_c,1) + ...)`` for ``c = x, y, z`` over the systems with ``use[b] != 0`` in ascending
-        order, in one launch: ``g_c,b`` is bit for bit ``gradient(components=True)`` of system ``b`` (fields as ``grad_acc_add``)."""
-        a = complex(smu0)
-        u = self._use_flags(use, "grad_acc3_add")
-        st = self._lib.emg3d_mg_grad_acc3_add(self._h, int(fwd_bvec), a.real, a.imag, _lib.ptr(u))
-        self._check_bvec(st, "emg3d_mg_grad_acc3_add",
-                         f"grad_acc3_add: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy).")
+        self.grad_acc_add(fwd_bvec, smu0, use, components=True)
 
     def grad_acc3_get(self):
-        """The three accumulators ``(acc_x, acc_y, acc_z)``: ``nC`` doubles each, F-ordered."""
-        outs = [np.empty(self.nC, dtype=np.float64) for _ in range(3)]
-        _lib.check(self._lib.emg3d_mg_grad_acc3_get(self._h, *(_lib.ptr(o) for o in outs)), "emg3d_mg_grad_acc3_get")
-        return tuple(outs)
+        return self.grad_acc_get(components=True)
+
+    def grad_acc3_get_model(self):
+        return self.grad_acc_get_model(components=True)
 
     # ---- survey sensitivity diagonal: all pairs of adjoint and forward systems (optimize.SurveyJacobian.sensitivity_diagonal) ----
-    def sens_acc_add(self, fwd_bvec, smu0, use_fwd, use_adj, weights, split=False):
+    def sens_acc_add(self, fwd_bvec, smu0, use_fwd, use_adj, weights, split=False, components=False):
         """``acc += weights[b_adj, b_fwd] * |(c_x + c_y) + c_z|^2`` over the pairs of an adjoint system ``b_adj`` (``use_adj[b_adj]
         != 0``; its field ``lambda`` = system ``b_adj``'s field) and a forward system ``b_fwd`` (``use_fwd[b_fwd] != 0``; ``E`` = slice
         ``b_fwd`` of the batched vector ``fwd_bvec``, a saved copy), ``c_c = edges2cellaverages_c(s mu_0 lambda E)``: one launch
         (``emg3d_mg_sens_acc_add``), adjoint systems ascending in the outer loop, forward systems ascending in the inner one, a
-        pair with weight 0 skipped.  Into the accumulator of ``grad_acc_reset`` / ``grad_acc_get``; ``split=True``: ``W |c_x|^2, W
-        |c_y|^2, W |c_z|^2`` into the three of ``grad_acc3_reset`` / ``grad_acc3_get``.  The accumulator must have been reset once.
-        ``weights``: ``(nsys, nsys)`` finite doubles, uploaded into a table of the handle's own."""
+        pair with weight 0 skipped.  Into the accumulator of ``grad_acc_reset`` / ``grad_acc_get``; ``components=True`` (also spelled
+        ``split=True``): ``W |c_x|^2, W |c_y|^2, W |c_z|^2`` into the three of ``grad_acc_reset(components=True)``.  The accumulator
+        must have been reset once.  ``weights``: ``(nsys, nsys)`` finite doubles, uploaded into a table of the handle's own."""
+        components = bool(components) or bool(split)
         a = complex(smu0)
         uf, ua = self._use_flags(use_fwd, "sens_acc_add"), self._use_flags(use_adj, "sens_acc_add")
         w = np.ascontiguousarray(weights, dtype=np.float64)
@@ -329,10 +335,10 @@ class DeviceMG:
         if not np.isfinite(w).all():
             raise ValueError("sens_acc_add: `weights` must be finite.")
         st = self._lib.emg3d_mg_sens_acc_add(self._h, int(fwd_bvec), a.real, a.imag, _lib.ptr(uf), _lib.ptr(ua), _lib.ptr(w),
-                                             int(bool(split)))
+                                             int(components))
         self._check_bvec(st, "emg3d_mg_sens_acc_add",
                          f"sens_acc_add: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy), or the "
-                         f"accumulator was never reset (grad_acc{'3' if split else ''}_reset).")
+                         f"accumulator was never reset (grad_acc{'3' if components else ''}_reset).")
 
     # ---- the accumulators on a model grid (optimize.SurveyJacobian(model_grid=)) ----
     def set_model_grid(self, model_grid):
@@ -377,21 +383,13 @@ class DeviceMG:
             raise ValueError("set_regrid_factors: the directions must share factors as in the handle's first call.")
         self._require_model_grid(st, "emg3d_mg_set_regrid_factors")
 
-    def grad_acc_get_model(self):
+    def grad_acc_get_model(self, components=False):
         """``Q_x (.) A^T (F_x (.) acc)`` of the accumulator of ``grad_acc_add`` (``emg3d_mg_grad_acc_get_model``; ``A``: volume
-        averaging from the model grid): ``nM`` doubles, F-ordered.  The accumulator stays as it is."""
-        out = np.empty(int(np.prod(self._vnM or (1,))), dtype=np.float64)
-        self._require_model_grid(self._lib.emg3d_mg_grad_acc_get_model(self._h, _lib.ptr(out)), "emg3d_mg_grad_acc_get_model")
+        averaging from the model grid): ``nM`` doubles, F-ordered.  ``components=True``: ``Q_c (.) A^T (F_c (.) acc_c)`` of the three
+        per-direction accumulators (``emg3d_mg_grad_acc3_get_model``), three such arrays.  The accumulators stay as they are."""
+        ptrs, out = self._acc_out(int(np.prod(self._vnM or (1,))), components)
+        self._require_model_grid(*self._acc_call("get_model", components, *ptrs))
         return out
-
-    def grad_acc3_get_model(self):
-        """``Q_c (.) A^T (F_c (.) acc_c)`` of the three accumulators of ``grad_acc3_add`` (``emg3d_mg_grad_acc3_get_model``):
-        three arrays of ``nM`` doubles, F-ordered.  The accumulators stay as they are."""
-        n = int(np.prod(self._vnM or (1,)))
-        outs = [np.empty(n, dtype=np.float64) for _ in range(3)]
-        self._require_model_grid(self._lib.emg3d_mg_grad_acc3_get_model(self._h, *(_lib.ptr(o) for o in outs)),
-                                 "emg3d_mg_grad_acc3_get_model")
-        return tuple(outs)
 
     def _perturbation_ptrs(self, vs, what):
         held, ptrs = [], []

@@ -91,6 +91,84 @@ def test_grad_acc_is_the_sequential_sum_of_the_system_gradients(freq, nsys):
         assert np.array_equal(dev.grad_acc_get(), np.zeros(grid.nC))
 
 
+@pytest.mark.parametrize("freq", [1.5, -1.5], ids=["c128", "f64"])
+def test_both_spellings_address_the_same_accumulators(freq):
+    """grad_acc_*(components=True) and sens_acc_add(components=True) are grad_acc3_* and sens_acc_add(split=True): equal results
+    on one handle, and an add through one spelling shows in a get through the other.  4 x 3 x 2 cells, three systems of which
+    the middle one is masked out, a weight table with one zero entry; the summed accumulator is not touched by any of it."""
+    import emg3d_amd as em
+    from emg3d_amd import models
+    from emg3d_amd.solver import DeviceMG
+    grid = em.TensorMesh([[40., 50., 60., 70.], [30., 45., 65.], [55., 80.]], origin=(-110., -70., -60.))
+    model_grid = em.TensorMesh([[110., 110.], [140.], [60., 75.]], origin=(-110., -70., -60.))
+    assert tuple(grid.vnC) == (4, 3, 2)
+    sf = em.SourceField(grid, freq=freq)
+    rng = np.random.default_rng(7)
+    nsys, use = 3, np.array([1, 0, 1], dtype=np.int32)
+    W = rng.uniform(0.5, 2.0, (nsys, nsys))
+    W[2, 0] = 0.0
+
+    def rand():
+        a = rng.standard_normal(grid.nE)
+        return a if freq < 0 else a + 1j * rng.standard_normal(grid.nE)
+    model = em.Model(grid, rng.uniform(0.5, 2.0, grid.nC), mapping='Conductivity')
+    with DeviceMG.from_sigma_volume(grid, *models.sigma_volume(grid, model), smu0=sf.smu0) as dev:
+        dev.set_batch(nsys)
+        dev.bvec_alloc(1)
+        for b in range(nsys):
+            dev.bvec_set(0, b, rand())
+            dev.select(b)
+            dev.vec_set(dev.EFIELD, rand())
+        dev.set_model_grid(model_grid)
+        dev.set_regrid_factors(tuple(rng.uniform(0.5, 2.0, grid.vnC) for _ in range(3)),
+                               tuple(rng.uniform(0.5, 2.0, model_grid.vnC) for _ in range(3)))
+
+        def same(a, b):
+            return len(a) == len(b) == 3 and all(np.array_equal(x, y) for x, y in zip(a, b))
+
+        def both():
+            """The three accumulators through either spelling, on the handle's grid and on the model grid."""
+            new, old = dev.grad_acc_get(components=True), dev.grad_acc3_get()
+            assert isinstance(new, tuple) and same(new, old)
+            assert same(dev.grad_acc_get_model(components=True), dev.grad_acc3_get_model())
+            return old
+        dev.grad_acc_reset()
+        dev.grad_acc_add(0, sf.smu0, use)
+        one = dev.grad_acc_get()
+        assert np.abs(one).max() > 0
+        # the gradient: new spelling, then the same through the kept one, and an add through each on top of the other
+        dev.grad_acc_reset(components=True)
+        assert same(both(), [np.zeros(grid.nC)] * 3)
+        dev.grad_acc_add(0, sf.smu0, use, components=True)
+        new = both()
+        assert all(np.abs(x).max() > 0 for x in new)
+        dev.grad_acc3_reset()
+        assert same(both(), [np.zeros(grid.nC)] * 3)
+        dev.grad_acc3_add(0, sf.smu0, use)
+        assert same(both(), new)
+        dev.grad_acc_add(0, sf.smu0, use, components=True)
+        mixed = both()
+        dev.grad_acc_reset(components=True)
+        dev.grad_acc3_add(0, sf.smu0, use)
+        dev.grad_acc3_add(0, sf.smu0, use)
+        assert same(both(), mixed)
+        # the sensitivity diagonal likewise
+        dev.grad_acc3_reset()
+        dev.sens_acc_add(0, sf.smu0, use, use, W, components=True)
+        new = both()
+        assert all(np.abs(x).max() > 0 for x in new)
+        dev.grad_acc_reset(components=True)
+        dev.sens_acc_add(0, sf.smu0, use, use, W, split=True)
+        assert same(both(), new)
+        dev.sens_acc_add(0, sf.smu0, use, use, W, components=True)
+        mixed = both()
+        dev.grad_acc3_reset()
+        dev.sens_acc_add(0, sf.smu0, use, use, W, split=True)
+        dev.sens_acc_add(0, sf.smu0, use, use, W, split=True)
+        assert same(both(), mixed)
+        assert np.array_equal(dev.grad_acc_get(), one) and np.array_equal(dev.grad_acc_get(components=False), one)
+
+
 # ---- 2. + 4. against the reference fixture and against the per-pair path -----------------------------------------------------
 @pytest.fixture(scope="module")
 def fixture_run():

@@ -163,7 +163,9 @@ def test_rounding_yardstick():
 
 def test_kernel_uses_no_scratch(tmp_path):
     """The compiler's resource remarks for the four instantiations of k_sens_acc on gfx950: no scratch (the edge values of a cell
-    are indexed with compile-time constants only), and the VGPR counts DESIGN 8.8 states (needs hipcc, not a GPU)."""
+    are indexed with compile-time constants only), and the VGPR counts DESIGN 8.8 states (needs hipcc, not a GPU).  Likewise for the
+    other per-cell kernels that share its cell frame, k_gradient and k_gradient_acc: no scratch, and no more VGPRs than each
+    instantiation took when the frame was written out in every kernel."""
     import os
     import shutil
     import subprocess
@@ -177,14 +179,24 @@ def test_kernel_uses_no_scratch(tmp_path):
     for line in out.stderr.splitlines():
         if "Function Name:" in line:
             name = line.split("Function Name:")[1].split()[0]
-        elif name and "k_sens_acc" in name:
+        elif name and ("k_sens_acc" in name or "k_gradient" in name):
             for key in ("ScratchSize [bytes/lane]:", " VGPRs:"):
                 if key in line:
                     seen.setdefault(name, {})[key.strip()] = int(line.split(key)[1].split()[0])
     print(seen)
-    assert len(seen) == 4, seen
+    sens = {k: v for k, v in seen.items() if "k_sens_acc" in k}
+    assert len(sens) == 4, seen
     assert all(v["ScratchSize [bytes/lane]:"] == 0 for v in seen.values()), seen
-    assert all(v["VGPRs:"] <= (164 if "c128" in k else 88) for k, v in seen.items()), seen
+    assert all(v["VGPRs:"] <= (164 if "c128" in k else 88) for k, v in sens.items()), seen
+    # (kernel, scalar type, SPLIT) -> VGPRs; the mangled name carries k_gradient as 10k_gradientI, k_gradient_acc as 14k_gradient_accI
+    bounds = {("10k_gradientI", "4c128", 0): 60, ("10k_gradientI", "4c128", 1): 62, ("10k_gradientI", "d", 0): 40,
+              ("10k_gradientI", "d", 1): 40, ("14k_gradient_accI", "4c128", 0): 98, ("14k_gradient_accI", "4c128", 1): 116,
+              ("14k_gradient_accI", "d", 0): 72, ("14k_gradient_accI", "d", 1): 76}
+    for (kern, scalar, split), vgprs in bounds.items():
+        hit = [v for k, v in seen.items() if k.startswith(f"_Z{kern}{scalar}Lb{split}E")]
+        assert len(hit) == 1, (kern, scalar, split, seen)
+        assert hit[0]["VGPRs:"] <= vgprs, (kern, scalar, split, hit[0])
+    assert len(seen) == 12, seen
 
 
 def test_weights_and_shapes():
