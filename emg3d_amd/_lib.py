@@ -22,7 +22,7 @@ c_double = ctypes.c_double
 c_dp = ctypes.POINTER(ctypes.c_double)
 
 # include/emg3d_hip.h: EMG3D_HIP_ABI_VERSION -- a library built from another header version is refused at load
-ABI_VERSION = 113
+ABI_VERSION = 114
 
 # name -> (restype, argtypes); mirrors include/emg3d_hip.h one to one.
 SIGNATURES = {
@@ -46,6 +46,7 @@ SIGNATURES = {
     "emg3d_prolongation": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
     "emg3d_restrict_model": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_int]),
     "emg3d_sweep_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, ctypes.c_char_p, ctypes.POINTER(c_i64)]),
+    "emg3d_sweep_thm_zkeep": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, ctypes.POINTER(c_i64)]),
     "emg3d_sweep_fuse_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, ctypes.POINTER(c_i64),
                                       ctypes.POINTER(c_i64), c_i64]),
     "emg3d_mg_create": (c_int, [ctypes.POINTER(c_vp), c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp,
@@ -257,6 +258,17 @@ def sweep_plan(vnC, direction, dtype=np.complex128, ordering='colour', nsys=1, c
                                   1 if ordering == 'colour' else 0, int(nsys), int(cu_count), name, info), "emg3d_sweep_plan")
     return {"kernel": name.value.decode(), "lines_per_colour": info[0], "lines_per_wave": info[1], "rounds": info[2],
             "factor_kind": info[3], "split": bool(info[4]), "big_offsets": bool(info[5])}
+
+
+def sweep_thm_zkeep(vnC, direction, dtype=np.complex128, ordering='colour', nsys=1, cu_count=0):
+    """How many forward steps per half of a line keep their intermediate result in LDS where ``k_line_sweep_thm`` serves a level of
+    ``vnC`` cells along ``direction`` (1, 2, 3) -- ``emg3d_sweep_thm_zkeep``: shape logic only, runs without a GPU when
+    ``cu_count`` > 0.  All zero where another kernel serves."""
+    info = (c_i64 * 6)()
+    check(load().emg3d_sweep_thm_zkeep(dtype_code(dtype), int(vnC[0]), int(vnC[1]), int(vnC[2]), int(direction),
+                                       1 if ordering == 'colour' else 0, int(nsys), int(cu_count), info), "emg3d_sweep_thm_zkeep")
+    return {"cap": info[0], "dyn_lds_bytes": info[1], "static_lds_bytes": info[2], "half": info[3], "kept": info[4],
+            "lines_per_pair": info[5]}
 
 
 def sweep_fuse_plan(vnC, direction, npass, dtype=np.complex128, ordering='colour', nsys=1, cu_count=0, own=0, max_seg=0, budget=0):

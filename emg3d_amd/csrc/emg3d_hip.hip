@@ -537,6 +537,27 @@ static int sweep_plan_impl(i64 nx, i64 ny, i64 nz, int dir, int order, int nsys,
     return 0;
 }
 
+// emg3d_sweep_thm_zkeep: sweep_thm_zkeep of sweep_plan.hpp on a bare shape
+template <class T>
+static int thm_zkeep_impl(i64 nx, i64 ny, i64 nz, int dir, int order, int nsys, int cu_count, int64_t* info) {
+    SweepKnobs K;
+    if (cu_count > 0) K.simds = 4 * (i64)cu_count;
+    else sweep_device_knobs<T>(K, current_device());
+    K.order = order; K.nsys = nsys;
+    const SweepShape G{{nx, ny, nz}, (int)sizeof(T)};
+    const SweepPlan p = plan_sweep(K, G, dir - 1);
+    const i64 kz = sweep_thm_zkeep(K, G, dir - 1, p);
+    const bool thm = p.family == SweepFamily::thm;
+    const i64 n = G.nC[dir - 1], m = (n - 1) / 2, half = std::max(m, n - m - 2);
+    info[0] = kz;
+    info[1] = thm ? kz * sweep_thm_keep_step_bytes(p.inst_lpw, G.tsize) : 0;
+    info[2] = thm ? sweep_thm_static_lds(p.inst_lpw, G.tsize) : 0;
+    info[3] = thm ? half : 0;
+    info[4] = thm ? half - sweep_thm_keep_start((int)half, (int)kz, p.stages == 3 ? 3 : 2) : 0;
+    info[5] = thm ? p.inst_lpw : 0;
+    return 0;
+}
+
 // emg3d_sweep_fuse_plan: plan_fuse of sweep_plan.hpp on a bare shape, and its per-slab ranges
 template <class T>
 static int fuse_plan_impl(i64 nx, i64 ny, i64 nz, int dir, int order, int nsys, int cu_count, int npass, int own, int max_seg, i64 budget, int64_t* info,
@@ -934,6 +955,12 @@ int emg3d_sweep_plan(int dtype, int64_t nx, int64_t ny, int64_t nz, int dir, int
     if (nx < 2 || ny < 2 || nz < 2 || dir < 1 || dir > 3 || order < 0 || order > 1 || nsys < 1 || nsys > 64 || !name || !info) return -2;
     return dtype ? sweep_plan_impl<c128>(nx, ny, nz, dir, order, nsys, cu_count, name, info)
                  : sweep_plan_impl<double>(nx, ny, nz, dir, order, nsys, cu_count, name, info);
+}
+
+int emg3d_sweep_thm_zkeep(int dtype, int64_t nx, int64_t ny, int64_t nz, int dir, int order, int nsys, int cu_count, int64_t* info) {
+    if (nx < 2 || ny < 2 || nz < 2 || dir < 1 || dir > 3 || order < 0 || order > 1 || nsys < 1 || nsys > 64 || !info) return -2;
+    return dtype ? thm_zkeep_impl<c128>(nx, ny, nz, dir, order, nsys, cu_count, info)
+                 : thm_zkeep_impl<double>(nx, ny, nz, dir, order, nsys, cu_count, info);
 }
 
 int emg3d_sweep_fuse_plan(int dtype, int64_t nx, int64_t ny, int64_t nz, int dir, int order, int nsys, int cu_count, int npass, int own,

@@ -267,6 +267,15 @@ struct emg3d_mg {
 // dynamic LDS it needs -- more than 64 KB must be asked for per instantiation and device, once (tha_attrs, on the current device).
 static_assert(SWEEP_THA_LPW == THA_LPW && SWEEP_THA_RING == tha_ring_depth<3>() && SWEEP_THA_RING == tha_ring_depth<2>() &&
               SWEEP_THA_MAX_DYN_LDS == THA_MAX_DYN_LDS && SWEEP_THA_STATIC_LDS == THA_STATIC_LDS, "sweep_plan.hpp restates smooth_tha.hpp");
+// ... and the kept z of k_line_sweep_thm (sweep_thm_zkeep): asked for in the same place, with the device's LDS per workgroup
+template <class T, int LPW>
+constexpr bool sweep_thm_lds_agrees() {
+    return sweep_thm_static_lds(LPW, (int)sizeof(T)) == (i64)thm_static_lds<T, LPW>() &&
+           sweep_thm_keep_step_bytes(LPW, (int)sizeof(T)) == (i64)thm_keep_step_bytes<T, LPW>();
+}
+static_assert(sweep_thm_lds_agrees<double, 4>() && sweep_thm_lds_agrees<double, 8>() && sweep_thm_lds_agrees<double, 12>() &&
+              sweep_thm_lds_agrees<c128, 4>() && sweep_thm_lds_agrees<c128, 8>() && sweep_thm_lds_agrees<c128, 12>(),
+              "sweep_plan.hpp restates smooth_thm.hpp");
 template <class T>
 inline void sweep_device_knobs(SweepKnobs& K, int device) {
     int cus = 0, lds = 0;
@@ -275,6 +284,7 @@ inline void sweep_device_knobs(SweepKnobs& K, int device) {
     K.simds = 4 * (i64)cus;
     K.lds_limit = lds;
     K.tha_lds_granted = lds >= THA_MAX_DYN_LDS + THA_STATIC_LDS && tha_attrs<T>(THA_MAX_DYN_LDS);
+    K.thm_lds_granted = thm_attrs<T>(lds);
 }
 
 template <class T>
@@ -1330,7 +1340,6 @@ struct MG : emg3d_mg {
         L.fac[dir] = dalloc<T>(L.fac_lines[dir] * P.fac_entries);
         L.fac_mid[dir] = P.mid;
         L.fac_kind[dir] = P.fac_kind;
-        if (P.fac_kind == 3) thm_attrs();
         compute_factor(L, dir);
     }
     // (re)compute the cached factorisation of (level, direction) into its buffer: the model may have changed (set_smu0)
@@ -1415,21 +1424,20 @@ struct MG : emg3d_mg {
     // sweep-level parity tests report it instead of guessing from the grid size)
     char sweep_name[64] = "";
     char res_name[64] = "";            // the same for the most recent residual launch
-    // lab: k_line_sweep_thm can keep the last KL forward steps of a half in LDS (smooth_thm.hpp; KL by lines per pair of waves
-    // so that the workgroup stays within the CU's 160 KB).  Measured at 128^3: counted traffic 491 -> 453 MB per launch,
-    // launch 102.3 -> 103.7 us (profiles/HISTORY.md) -- the saving sits in steps during which every wave of the launch is
-    // off the memory system at the same time.  Off; EMG3D_THM_LIFO=1 switches it on in the lab build.
-    int thm_lifo = (int)LAB_ENV("EMG3D_THM_LIFO", 0);
-    // More than 64 KB of LDS per workgroup must be asked for, per kernel instantiation and device; done when the factor of
-    // a two-sided level is built, i.e. before the launches are captured into a graph.  (Only the lab build's LIFO variants need
-    // it; k_line_sweep_tha's dynamic LDS is asked for with the device's size: sweep_device_knobs.)
-    void thm_attrs() {
-#ifdef EMG3D_LAB
-        static bool done[64] = {false};
-        if (device < 0 || device >= 64 || done[device]) return;
-        done[device] = true;
-        thm_lifo_attrs<T>();
-#endif
+    // k_line_sweep_thm keeps the z of the last forward steps of a half in LDS instead of parking them in e (smooth_thm.hpp; how
+    // many: sweep_thm_zkeep, sweep_plan.hpp -- what fits beside the static LDS in the CU's 160 KB, 59 of a 128-block line's 63 steps
+    // per half at complex128).  The dynamic LDS was asked for per instantiation when the handle's knobs were filled
+    // (sweep_device_knobs: before any launch sequence is captured); a device that refused it runs with kz = 0, every step parked.
+    // Measured: profiles/thm_zkeep_ab.txt.
+    int thm_keep(const SweepPlan& P, const LineArgs<T>& a) {
+        const SweepShape G{{a.nC[0], a.nC[1], a.nC[2]}, (int)sizeof(T)};
+        const i64 kz = sweep_thm_zkeep(knobs, G, a.L, P);
+        const i64 granted = knobs.thm_lds_granted ? knobs.lds_limit - sweep_thm_static_lds(P.inst_lpw, (int)sizeof(T)) : 0;
+        if (kz < 0 || kz * sweep_thm_keep_step_bytes(P.inst_lpw, (int)sizeof(T)) > granted) {
+            fprintf(stderr, "emg3d_hip: k_line_sweep_thm would keep %lld steps in %lld bytes of LDS\n", (long long)kz, (long long)granted);
+            abort();
+        }
+        return (int)kz;
     }
     // One launch of n lines (a colour, or a hyperplane of the lexicographic order) with the kernel the plan names: the grid, and the
     // instantiation through sweep_launch.hpp.
@@ -1446,7 +1454,7 @@ struct MG : emg3d_mg {
         }
         case SweepFamily::thm: {        // a pair of waves per inst_lpw lines
             const i64 npairs = (n + P.inst_lpw - 1) / P.inst_lpw;
-            thm_launch<T>(P.stages, P.inst_lpw, thm_lifo != 0, a.zsep != 0, bgrid(rp_grid(npairs * 128)), stream, a);
+            thm_launch<T>(P.stages, P.inst_lpw, a.zsep != 0, thm_keep(P, a), bgrid(rp_grid(npairs * 128)), stream, a);
             break;
         }
         case SweepFamily::qpl:

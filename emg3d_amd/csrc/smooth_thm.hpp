@@ -14,6 +14,7 @@
 #pragma once
 #include <type_traits>
 #include "factor_m.hpp"
+#include "sweep_plan.hpp"      // sweep_thm_keep_start: the one phase split of the kernel and the planner
 
 static_assert(EMG_RP_BLOCK % 128 == 0, "k_line_sweep_thm pairs the waves of a workgroup: whole pairs only");
 
@@ -22,13 +23,17 @@ struct TmStep { T W[5]; T E[6]; T S; double zf[4]; double ihl0, ihl1; };
 template <class T>
 struct TmBack { T W[5]; T zi; double p0, p1, ihc; };
 
-// LIFO (KL > 0): what the backward pass needs again of the LAST KL forward steps of a half -- the 14 distinct entries
-// W[r][1..4] of the block inverse and the five z -- stays in LDS (the kernel runs one 256-thread workgroup per CU: 250
-// registers; 147 KB of the CU's 160 KB were idle) instead of going through HBM: those steps neither park z in e nor
-// read factor and z back.  Per wave and step 19 numbers x LPW lines (2.4 KB at 8 lines): 15 steps of the 63-64 of a
-// 128-block line.  Dynamic LDS: thm_lifo_bytes<T, LPW, KL>().
-template <class T, int LPW, int KL>
-constexpr size_t thm_lifo_bytes() { return (size_t)(EMG_RP_BLOCK / 64) * KL * 19 * LPW * sizeof(T); }
+// z keep (kz > 0, a launch argument): the forward results z of the LAST kz steps of a half stay in LDS until the backward pass
+// takes them again, instead of being parked in e and loaded back -- 2 x sizeof(T) of the bytes a block moves, and nobody outside
+// the wave reads a parked z.  Slot [wave][step][row 0..4][line] of T in dynamic LDS = [wave][step][lane]: a lane writes and
+// reads its own slot only (no barrier); the mirror lanes write nothing (they read lane 0's slot as they read row 0's z in e).
+// Per workgroup and step thm_keep_step_bytes() -- 2560 B at 8 complex lines: 59 steps beside the static LDS below in a CU's
+// 160 KB (the kernel runs one workgroup per CU at 250 registers), of a 128-block line's 63 per half.  The host chooses kz (sweep_plan.hpp: sweep_thm_zkeep, which restates the two
+// sizes here; mg.hpp asserts that they agree); kz = 0: every step parks in e.  Bit-identical either way.
+template <class T, int LPW>
+constexpr size_t thm_static_lds() { return ((size_t)(EMG_RP_BLOCK / 64) * 2 * 64 + (size_t)(EMG_RP_BLOCK / 128) * 3 * 6 * LPW) * sizeof(T); }
+template <class T, int LPW>
+constexpr size_t thm_keep_step_bytes() { return (size_t)(EMG_RP_BLOCK / 64) * 5 * LPW * sizeof(T); }
 
 // ZS: zeta formed from the width vectors instead of read (smooth_qc.hpp: level 0 of a model without mu_r, checked bit for
 // bit by the handle): zf[0], zf[2] then carry hL at the two cells of the step, zf[1], zf[3] are unused.
@@ -48,8 +53,8 @@ __device__ __forceinline__ void thm_args_burst(const LineArgs<T>& a) {
                  "s"(a.rs.hL), "s"(a.rs.hP), "s"(a.rs.hQ), "s"(a.L));
 }
 
-template <class T, int STAGES, int LPW, int KL = 0, bool ZS = false>
-__global__ __launch_bounds__(EMG_RP_BLOCK) void k_line_sweep_thm(LineArgs<T> a) {
+template <class T, int STAGES, int LPW, bool ZS = false>
+__global__ __launch_bounds__(EMG_RP_BLOCK) void k_line_sweep_thm(LineArgs<T> a, int kz) {
     typedef unsigned int u32;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -195,18 +200,14 @@ __global__ __launch_bounds__(EMG_RP_BLOCK) void k_line_sweep_thm(LineArgs<T> a) 
     T* const xy = xch[threadIdx.x >> 6][1];
     const int sl0 = g;
     __shared__ T jn[EMG_RP_BLOCK / 128][3][6 * LPW];     // middle join: [0] z of the right half, [1] y (6 rows), [2] x (6 rows)
-    // LIFO of the wave: [step][item 0..18][line]; items 0..3: W[0][1..4], 4..13: W[k][j] (1 <= j <= k <= 4), 14..18: z_r
+    // kept z of the wave: [step][lane] (lane = LPW * row + line; rows 0..4 only)
     extern __shared__ __attribute__((aligned(16))) char thm_dyn_lds[];
-    T* const lifo = reinterpret_cast<T*>(thm_dyn_lds) + (KL > 0 ? (threadIdx.x >> 6) * (KL * 19 * LPW) + g : 0);
-    // forward steps K1 .. K-1 (= backward steps KLe-1 .. 0) live in the LIFO; K1 is a multiple of the main loops' unroll
-    // (3), so that the loops below split into branch-free phases (a branch in a loop body costs the counted s_waitcnt)
-    const int K1 = (KL > 0) ? (K > KL ? ((K - KL + 2) / 3) * 3 : 0) : K;
+    T* const keep = reinterpret_cast<T*>(thm_dyn_lds) + (threadIdx.x >> 6) * (kz * 5 * LPW) + (rowact ? lane : 0);
+    // forward steps K1 .. K-1 (= backward steps KLe-1 .. 0) are kept; K1 is a multiple of the main loops' unroll (sweep_plan.hpp:
+    // sweep_thm_keep_start), so that the loops below split into branch-free phases (a branch in a loop body costs the counted
+    // s_waitcnt)
+    const int K1 = __builtin_amdgcn_readfirstlane(sweep_thm_keep_start(K, kz, STAGES == 3 ? 3 : 2));
     const int KLe = K - K1;
-    int li_w[4];
-#pragma unroll
-    for (int c = 1; c <= 4; ++c)
-        li_w[c - 1] = (rr == 0) ? c - 1 : (c <= rr ? 4 + (rr - 1) * rr / 2 + c - 1 : 4 + (c - 1) * c / 2 + rr - 1);
-    const int li_z = 14 + rr;
     // index of the row's own data for block ic of my half: row 0 by its L-cell, transverse rows by node - 1
     auto own_idx = [&](int ic) -> u32 {
         int v = t0 ? ic : (H ? ic - 1 : ic);
@@ -280,20 +281,17 @@ __global__ __launch_bounds__(EMG_RP_BLOCK) void k_line_sweep_thm(LineArgs<T> a) 
         const T su = (xu[sl0 + LPW] + xu[sl0 + 2 * LPW]) + (xu[sl0 + 3 * LPW] + xu[sl0 + 4 * LPW]);
         const T z = ((cur.W[0] * (Y0 - su) + cur.W[1] * Y1) + (cur.W[2] * Y2 + cur.W[3] * Y3)) + cur.W[4] * Y4;
         if constexpr (decltype(keep_)::value) {          // kept in LDS: no parking in e
-            if (rowact) {
-                T* const slot_ = lifo + (k_ - K1) * (19 * LPW);
-#pragma unroll
-                for (int c = 1; c <= 4; ++c)
-                    if (rr == 0 || c <= rr) slot_[li_w[c - 1] * LPW] = cur.W[c];
-                slot_[li_z * LPW] = z;
-            }
+            if (rowact) keep[(k_ - K1) * (5 * LPW)] = z;
         } else if (rowact) *reinterpret_cast<T*>(eWr + zst) = z;
         zst += dzst;
         zprev = z;
     };
     const std::false_type no_{};
     const std::true_type yes_{};
-    const std::integral_constant<bool, (KL > 0)> lifo_{};
+    // a step outside the branch-free loops: kept or parked by its number (wave-uniform branch)
+    auto fwd_any = [&](int ic_, const TmStep<T>& cur, int k_) {
+        if (k_ >= K1) fwd_step(ic_, cur, k_, yes_); else fwd_step(ic_, cur, k_, no_);
+    };
     auto forward = [&](auto ns) {
     if (K > 0) {
         if (STAGES == 3) {
@@ -309,37 +307,38 @@ __global__ __launch_bounds__(EMG_RP_BLOCK) void k_line_sweep_thm(LineArgs<T> a) 
                 load_step(fwd_block(k + 4), bufB, ns);
                 fwd_step(fwd_block(k + 2), bufC, k + 2, no_);
             }
-            if constexpr (KL > 0) {
-                for (; k + 3 <= K; k += 3) {
-                    load_step(fwd_block(k + 2), bufC, ns);
-                    fwd_step(fwd_block(k), bufA, k, yes_);
-                    load_step(fwd_block(k + 3), bufA, ns);
-                    fwd_step(fwd_block(k + 1), bufB, k + 1, yes_);
-                    load_step(fwd_block(k + 4), bufB, ns);
-                    fwd_step(fwd_block(k + 2), bufC, k + 2, yes_);
-                }
+            for (; k + 3 <= K && k >= K1; k += 3) {          // (k >= K1: not after a first loop that stopped short of K1 = K)
+                load_step(fwd_block(k + 2), bufC, ns);
+                fwd_step(fwd_block(k), bufA, k, yes_);
+                load_step(fwd_block(k + 3), bufA, ns);
+                fwd_step(fwd_block(k + 1), bufB, k + 1, yes_);
+                load_step(fwd_block(k + 4), bufB, ns);
+                fwd_step(fwd_block(k + 2), bufC, k + 2, yes_);
             }
-            if (k < K) fwd_step(fwd_block(k), bufA, k, lifo_);
-            if (k + 1 < K) fwd_step(fwd_block(k + 1), bufB, k + 1, lifo_);
+            if (k < K) fwd_any(fwd_block(k), bufA, k);
+            if (k + 1 < K) fwd_any(fwd_block(k + 1), bufB, k + 1);
         } else {
             TmStep<T> bufA, bufB;
             load_step(fwd_block(0), bufA, ns);
             int k = 0;
-            auto step2 = [&](int ic_, const TmStep<T>& cur, int k_) {
-                if (KL > 0 && k_ >= K1) fwd_step(ic_, cur, k_, yes_); else fwd_step(ic_, cur, k_, no_);
-            };
-            for (; k + 2 <= K - 1; k += 2) {
+            for (; k + 2 <= K - 1 && k + 2 <= K1; k += 2) {
                 load_step(fwd_block(k + 1), bufB, ns);
-                step2(fwd_block(k), bufA, k);
+                fwd_step(fwd_block(k), bufA, k, no_);
                 load_step(fwd_block(k + 2), bufA, ns);
-                step2(fwd_block(k + 1), bufB, k + 1);
+                fwd_step(fwd_block(k + 1), bufB, k + 1, no_);
+            }
+            for (; k + 2 <= K - 1 && k >= K1; k += 2) {
+                load_step(fwd_block(k + 1), bufB, ns);
+                fwd_step(fwd_block(k), bufA, k, yes_);
+                load_step(fwd_block(k + 2), bufA, ns);
+                fwd_step(fwd_block(k + 1), bufB, k + 1, yes_);
             }
             if (k + 1 <= K - 1) {
                 load_step(fwd_block(k + 1), bufB, ns);
-                step2(fwd_block(k), bufA, k);
-                step2(fwd_block(k + 1), bufB, k + 1);
+                fwd_any(fwd_block(k), bufA, k);
+                fwd_any(fwd_block(k + 1), bufB, k + 1);
             } else {
-                step2(fwd_block(k), bufA, k);
+                fwd_any(fwd_block(k), bufA, k);
             }
         }
     }
@@ -420,21 +419,24 @@ __global__ __launch_bounds__(EMG_RP_BLOCK) void k_line_sweep_thm(LineArgs<T> a) 
     // ----------------------------- backward --------------------------------
     // step k: left block m-1-k, right block m+2+k; the inner neighbour's l cell: left ic+1, right ic-1
     auto bwd_block = [&](int k) -> int { return H ? m + 2 + k : m - 1 - k; };
-    // src_: 1 = the step is in the LIFO, 2 = it is not, 0 = decide here (wave-uniform branch: transition iterations only)
+    // src_: 1 = the step's z is kept in LDS, 2 = it is parked in e, 0 = decide here (wave-uniform branch: transition iterations
+    // only).  The LDS read is issued here, steps ahead like the loads: LDS answers in order, so it has arrived by the time the
+    // exchange of an earlier step has been waited for and adds no wait of its own.
     auto load_bwd = [&](int ic_, TmBack<T>& d, int kb_, auto src_) {
         constexpr int SRC = decltype(src_)::value;
         const u32 icc = (u32)(ic_ < 0 ? 0 : (ic_ > n - 1 ? n - 1 : ic_));
-        if (KL > 0 && (SRC == 1 || (SRC == 0 && kb_ < KLe))) {      // the step's factor rows and z are in the LIFO
-            const T* const slot_ = lifo + (KLe - 1 - kb_) * (19 * LPW);
+        const u32 wb = __umul24(icc, wst);
 #pragma unroll
-            for (int c = 1; c <= 4; ++c) d.W[c] = slot_[li_w[c - 1] * LPW];
-            d.zi = slot_[li_z * LPW];
-        } else {
-            const u32 wb = __umul24(icc, wst);
-#pragma unroll
-            for (int c = 1; c < 5; ++c) d.W[c] = *(reinterpret_cast<const T*>(wB + (wb + wo[c])));
-            d.zi = *(reinterpret_cast<const T*>(eB + (so + __umul24(own_idx(ic_), ss))));
-        }
+        for (int c = 1; c < 5; ++c) d.W[c] = *(reinterpret_cast<const T*>(wB + (wb + wo[c])));
+        if constexpr (SRC == 1) d.zi = keep[(KLe - 1 - kb_) * (5 * LPW)];
+        else if constexpr (SRC == 2) d.zi = *(reinterpret_cast<const T*>(eB + (so + __umul24(own_idx(ic_), ss))));
+        else if (kb_ < KLe) {
+            // (the empty asm keeps the two arms two loads: merged into one load from a selected address they become a FLAT load,
+            // and with a flat load pending the loops that follow wait for vmcnt(0) once per iteration instead of the counted
+            // waits of their prefetch -- 3.5 us of a 90 us launch)
+            d.zi = keep[(KLe - 1 - kb_) * (5 * LPW)];
+            asm volatile("" ::: "memory");
+        } else d.zi = *(reinterpret_cast<const T*>(eB + (so + __umul24(own_idx(ic_), ss))));
         int ci = H ? (int)icc - 1 : (int)icc + 1;
         ci = ci < 0 ? 0 : (ci > n - 1 ? n - 1 : ci);
         const u32 zb = __umul24((u32)ci, zsL);
@@ -477,23 +479,21 @@ __global__ __launch_bounds__(EMG_RP_BLOCK) void k_line_sweep_thm(LineArgs<T> a) 
             load_bwd(bwd_block(0), bA, 0, any_);
             load_bwd(bwd_block(1), bB, 1, any_);
             int k = 0;
-            if constexpr (KL > 0) {
-                for (; k + 3 <= K && k + 4 < KLe; k += 3) {          // every load of the iteration from the LIFO
-                    load_bwd(bwd_block(k + 2), bC, k + 2, lds_);
-                    bwd_step(bwd_block(k), bA);
-                    load_bwd(bwd_block(k + 3), bA, k + 3, lds_);
-                    bwd_step(bwd_block(k + 1), bB);
-                    load_bwd(bwd_block(k + 4), bB, k + 4, lds_);
-                    bwd_step(bwd_block(k + 2), bC);
-                }
-                for (; k + 3 <= K && k + 2 < KLe; k += 3) {          // transition
-                    load_bwd(bwd_block(k + 2), bC, k + 2, any_);
-                    bwd_step(bwd_block(k), bA);
-                    load_bwd(bwd_block(k + 3), bA, k + 3, any_);
-                    bwd_step(bwd_block(k + 1), bB);
-                    load_bwd(bwd_block(k + 4), bB, k + 4, any_);
-                    bwd_step(bwd_block(k + 2), bC);
-                }
+            for (; k + 3 <= K && k + 4 < KLe; k += 3) {              // every z of the iteration from LDS
+                load_bwd(bwd_block(k + 2), bC, k + 2, lds_);
+                bwd_step(bwd_block(k), bA);
+                load_bwd(bwd_block(k + 3), bA, k + 3, lds_);
+                bwd_step(bwd_block(k + 1), bB);
+                load_bwd(bwd_block(k + 4), bB, k + 4, lds_);
+                bwd_step(bwd_block(k + 2), bC);
+            }
+            for (; k + 3 <= K && k + 2 < KLe; k += 3) {              // transition
+                load_bwd(bwd_block(k + 2), bC, k + 2, any_);
+                bwd_step(bwd_block(k), bA);
+                load_bwd(bwd_block(k + 3), bA, k + 3, any_);
+                bwd_step(bwd_block(k + 1), bB);
+                load_bwd(bwd_block(k + 4), bB, k + 4, any_);
+                bwd_step(bwd_block(k + 2), bC);
             }
             for (; k + 3 <= K; k += 3) {
                 load_bwd(bwd_block(k + 2), bC, k + 2, mem_);
@@ -509,10 +509,22 @@ __global__ __launch_bounds__(EMG_RP_BLOCK) void k_line_sweep_thm(LineArgs<T> a) 
             TmBack<T> bA, bB;
             load_bwd(bwd_block(0), bA, 0, any_);
             int k = 0;
-            for (; k + 2 <= K - 1; k += 2) {
+            for (; k + 2 <= K - 1 && k + 2 < KLe; k += 2) {          // every z of the iteration from LDS
+                load_bwd(bwd_block(k + 1), bB, k + 1, lds_);
+                bwd_step(bwd_block(k), bA);
+                load_bwd(bwd_block(k + 2), bA, k + 2, lds_);
+                bwd_step(bwd_block(k + 1), bB);
+            }
+            for (; k + 2 <= K - 1 && k + 1 < KLe; k += 2) {          // transition
                 load_bwd(bwd_block(k + 1), bB, k + 1, any_);
                 bwd_step(bwd_block(k), bA);
                 load_bwd(bwd_block(k + 2), bA, k + 2, any_);
+                bwd_step(bwd_block(k + 1), bB);
+            }
+            for (; k + 2 <= K - 1; k += 2) {
+                load_bwd(bwd_block(k + 1), bB, k + 1, mem_);
+                bwd_step(bwd_block(k), bA);
+                load_bwd(bwd_block(k + 2), bA, k + 2, mem_);
                 bwd_step(bwd_block(k + 1), bB);
             }
             if (k + 1 <= K - 1) {

@@ -12,11 +12,13 @@
 // (the 16-line instantiation only).  Workgroups of EMG_Q_BLOCK threads.
 template <class T> void qc_launch(int stages, int lpw, bool zsep, bool big, dim3 grid, hipStream_t st, const LineArgs<T>& a);
 
-// k_line_sweep_thm<T, stages, lpw, KL, zsep>: stages 3 | 2 (else 3); lines per pair of waves 4 | 12 (else 8); lifo (lab build only):
-// the last KL forward steps of a half kept in dynamic LDS.  Workgroups of EMG_RP_BLOCK threads.
-template <class T> void thm_launch(int stages, int lpw, bool lifo, bool zsep, dim3 grid, hipStream_t st, const LineArgs<T>& a);
-// lab build: asks for the LIFO instantiations' dynamic LDS (> 64 KB must be asked for per instantiation and device)
-template <class T> void thm_lifo_attrs();
+// k_line_sweep_thm<T, stages, lpw, zsep>: stages 3 | 2 (else 3); lines per pair of waves 4 | 12 (else 8); kz: the last kz forward
+// steps of a half keep their z in dynamic LDS (kz x thm_keep_step_bytes, which the caller has checked against the grant of thm_attrs).
+// Workgroups of EMG_RP_BLOCK threads.
+template <class T> void thm_launch(int stages, int lpw, bool zsep, int kz, dim3 grid, hipStream_t st, const LineArgs<T>& a);
+// asks, for every instantiation on the current device, for the dynamic LDS that fits beside its static LDS in lds_limit bytes (more
+// than 64 KB must be asked for per instantiation and device); false: refused (the caller launches with kz = 0)
+template <class T> bool thm_attrs(int lds_limit);
 
 // k_line_sweep_tha<T, helpers, zsep>: helper waves per half 3 (lab build: 2).  tha_attrs asks for max_dyn_lds bytes of dynamic LDS
 // for every instantiation on the current device; false: refused (the caller selects another kernel).

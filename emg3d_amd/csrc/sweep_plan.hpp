@@ -63,6 +63,7 @@ struct SweepKnobs {
     i64 lds_limit = 160 * 1024;         // LDS bytes per workgroup
     bool tha_lds_granted = true;        // k_line_sweep_tha's dynamic LDS (up to 135 680 B, + SWEEP_THA_STATIC_LDS static) was asked for and
                                         // granted; a device or runtime that refuses it gets the other kernels (sweep_tha_helpers -> 0)
+    bool thm_lds_granted = true;        // the same for k_line_sweep_thm's kept z (sweep_thm_zkeep below): refused, every step parks in e
     int order = 1, nsys = 1;            // 1: four-colour order, 0: lexicographic; batched systems per launch
     // EMG3D_BATCH_TUNE=1 (default 0): with batched systems, choose between the scan kernel and the chain kernels by the
     // lines a LAUNCH carries (lines x systems) instead of the lines of one system -- the scan kernel does 4 x the
@@ -81,6 +82,11 @@ struct SweepKnobs {
     bool use_twist = LAB_ENV("EMG3D_TWIST", 1) != 0;                    // two-sided factorisation below twist_max_lines
     i64 twist_max_lines_env = LAB_ENV("EMG3D_TWIST_MAX", 0);            // 0: q_min_lines()
     int tw_stages = (int)LAB_ENV("EMG3D_TW_STAGES", 0);                 // register prefetch depth of the two-sided kernels (0: 3)
+    // k_line_sweep_thm: forward steps of a half whose z stays in LDS (sweep_thm_zkeep): -1 as many as fit, 0 none, n at most n
+    i64 thm_zkeep = LAB_ENV("EMG3D_THM_ZKEEP", -1);
+    // (retired: the 19-numbers-per-row LIFO the z keep replaced.  The name is still read, and ignored, so that lab scripts and test
+    // cases that set it run the default path)
+    int thm_lifo_retired = (int)LAB_ENV("EMG3D_THM_LIFO", 0);
     // sweeps on parity-split working copies (the lines of one colour contiguous in memory): 0 never, 1 every level and
     // ordering, 2 (default) colour-ordered levels of >= split_min_cells
     int use_split = (int)LAB_ENV("EMG3D_SPLIT", 2);
@@ -370,6 +376,42 @@ inline SweepPlan plan_sweep(const SweepKnobs& K, const SweepShape& G, int dir) {
     return p;
 }
 
+// ---- kept z of k_line_sweep_thm (smooth_thm.hpp) ---------------------------------------------------------------------------------
+// The forward pass of a half leaves one z per row and step for the backward pass.  The last kz steps keep theirs in LDS instead of
+// parking them in e: 2 x tsize of the bytes a block moves (160 of ~790 B at complex128), in a kernel whose level-0 launch is priced
+// by its bytes.  Static LDS and bytes per kept step of a 256-thread workgroup at lpw lines per pair of waves
+// (smooth_thm.hpp: thm_static_lds, thm_keep_step_bytes; mg.hpp asserts that the two agree):
+constexpr i64 sweep_thm_static_lds(int lpw, int tsize) { return (4 * 2 * 64 + 2 * 3 * 6 * (i64)lpw) * tsize; }
+constexpr i64 sweep_thm_keep_step_bytes(int lpw, int tsize) { return 4 * 5 * (i64)lpw * tsize; }
+// First kept forward step of a half of K steps under the cap kz: a multiple of the main loops' unroll (3- / 2-stage prefetch: 3 / 2),
+// so that parked and kept steps run in branch-free loops of their own; K - result <= kz.  The kernel and the planner call this one.
+#if defined(__HIPCC__)
+#define SWEEP_HD __host__ __device__
+#else
+#define SWEEP_HD
+#endif
+SWEEP_HD inline int sweep_thm_keep_start(int K, int kz, int unroll) {
+    if (kz <= 0) return K;
+    if (K <= kz) return 0;
+    const int k1 = ((K - kz + unroll - 1) / unroll) * unroll;
+    return k1 < K ? k1 : K;
+}
+// The cap kz of a (level, direction): the longest half, or what fits beside the instantiation's static LDS in a workgroup's LDS;
+// 0 where another family serves or the device refused the dynamic LDS.  EMG3D_THM_ZKEEP (lab): -1 this, 0 off, n at most n.
+// The rule is the same for every launch: a full-depth keep fills the CU's LDS, so that a second workgroup cannot join the first on a
+// CU, but the launches of more than one round were measured faster with it, not slower (profiles/thm_zkeep_ab.txt, parent -> keep,
+// three alternating runs each): four batched systems at 128^3 (12 lines per pair, 3 rounds, 36 of 63 steps kept) 0.282 -> 0.242 ms per level-0 launch, 21.92 ->
+// 20.86 ms per cycle; 144^3 at 12 lines per pair (38 of 71 steps kept) 0.120 -> 0.111 ms per launch.  So there is no
+// restriction to one-round plans and no minimum kept share.
+inline i64 sweep_thm_zkeep(const SweepKnobs& K, const SweepShape& G, int dir, const SweepPlan& P) {
+    if (P.family != SweepFamily::thm || !K.thm_lds_granted || K.thm_zkeep == 0) return 0;
+    const i64 n = G.nC[dir], m = (n - 1) / 2, half = std::max(m, n - m - 2);
+    const i64 room = K.lds_limit - sweep_thm_static_lds(P.inst_lpw, G.tsize);
+    i64 kz = std::min(half, room / sweep_thm_keep_step_bytes(P.inst_lpw, G.tsize));
+    if (K.thm_zkeep > 0) kz = std::min(kz, K.thm_zkeep);
+    return std::max<i64>(kz, 0);
+}
+
 // ---- fused colour passes: how MG::smooth_line ISSUES a call on a level of short lines -----------------------------------------------
 // The colour passes of one smoothing call (7 for nu = 2: 4 nu less the colours repeated at the backward -> forward turn-arounds) are dependent launches of a
 // few microseconds each.  Where the plan below says so, ONE launch of the same scan kernel (smooth_qpl.hpp, FZ) runs all of them:
@@ -390,11 +432,6 @@ inline SweepPlan plan_sweep(const SweepKnobs& K, const SweepShape& G, int dir) {
 //     slab: every edge has exactly one owner, and the owner's copy of it is exact;
 //   copied in: the indices [lo(0) - 1, hi(0) + 1] of every component.
 constexpr int SWEEP_FUSE_MAX_PASSES = 16;      // (LineArgs::fseq: four bits per pass; nu = 2: 7 passes, nu = 3: 11, nu = 4: 14)
-#if defined(__HIPCC__)
-#define SWEEP_HD __host__ __device__
-#else
-#define SWEEP_HD
-#endif
 struct FuseGeom { int nX, own, nslabs, npass; };
 SWEEP_HD inline int fuse_x0(const FuseGeom& g, int k) { return 1 + k * g.own; }
 SWEEP_HD inline int fuse_x1(const FuseGeom& g, int k) { const int x = 1 + (k + 1) * g.own; return (k == g.nslabs - 1 || x > g.nX) ? g.nX : x; }

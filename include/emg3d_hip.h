@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 113
+#define EMG3D_HIP_ABI_VERSION 114
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -118,6 +118,15 @@ int emg3d_restrict_model(int is_complex, int64_t nx, int64_t ny, int64_t nz, voi
  * numbers per block, 3 mirrored two-sided, 4 compact 11 numbers), parity-split working copies (0 / 1), 64-bit field offsets (0 / 1). */
 int emg3d_sweep_plan(int dtype, int64_t nx, int64_t ny, int64_t nz, int dir, int order, int nsys, int cu_count, char* name,
                      int64_t* info);
+
+/* How many forward steps of a half of a line keep their intermediate result z in LDS where the two-sided chain kernel
+ * (k_line_sweep_thm) serves such a level -- csrc/sweep_plan.hpp, sweep_thm_zkeep; the arguments of emg3d_sweep_plan, shape logic only,
+ * callable without a GPU when cu_count > 0 (a device with 160 KB of LDS per workgroup).  The kept steps neither write z to the field
+ * nor read it back; results are bit-identical for every depth.
+ * info[6]: steps a half may keep (0: another kernel serves, or the device refused the LDS), dynamic LDS bytes of a launch, static LDS
+ * bytes of the instantiation, steps of the longest half, steps of that half actually kept (the first kept step is a multiple of the
+ * prefetch depth), lines per pair of waves.                                                                                        */
+int emg3d_sweep_thm_zkeep(int dtype, int64_t nx, int64_t ny, int64_t nz, int dir, int order, int nsys, int cu_count, int64_t* info);
 
 /* How a smoothing call of npass colour passes along dir is ISSUED on such a level (csrc/sweep_plan.hpp, plan_fuse): one launch per
  * pass, or -- levels of short lines that the scan kernel serves -- all passes in one launch of that kernel, a workgroup per slab of
