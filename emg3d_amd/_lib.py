@@ -22,7 +22,7 @@ c_double = ctypes.c_double
 c_dp = ctypes.POINTER(ctypes.c_double)
 
 # include/emg3d_hip.h: EMG3D_HIP_ABI_VERSION -- a library built from another header version is refused at load
-ABI_VERSION = 114
+ABI_VERSION = 115
 
 # name -> (restype, argtypes); mirrors include/emg3d_hip.h one to one.
 SIGNATURES = {
@@ -88,6 +88,8 @@ SIGNATURES = {
     "emg3d_mg_grad_acc3_add": (c_int, [c_vp, c_int, c_double, c_double, c_vp]),
     "emg3d_mg_grad_acc3_get": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "emg3d_mg_sens_acc_add": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_vp, c_int]),
+    "emg3d_mg_sens_rows_count": (c_i64, [c_vp, c_vp, c_int]),
+    "emg3d_mg_sens_rows": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_int, c_int, c_vp]),
     "emg3d_cells2edges": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "emg3d_mg_jvec_source": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_vp]),
     "emg3d_mg_jvec_source_b": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_vp, c_vp]),

@@ -1281,6 +1281,23 @@ int emg3d_mg_sens_acc_add(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double s
     });
 }
 
+int64_t emg3d_mg_sens_rows_count(const int32_t* use_fwd, const int32_t* use_adj, int nsys) {
+    if (!use_fwd || !use_adj || nsys < 1 || nsys > 64) return -2;
+    int64_t nf = 0, na = 0;
+    for (int b = 0; b < nsys; ++b) { nf += use_fwd[b] != 0; na += use_adj[b] != 0; }
+    return nf * na;
+}
+
+int emg3d_mg_sens_rows(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use_fwd, const int32_t* use_adj,
+                       int split, int on_model_grid, double* out) {
+    if (!mg || !use_fwd || !use_adj || !out) return -2;
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        const int st = m->sens_rows(fwd_bvec, smu0_re, smu0_im, use_fwd, use_adj, split != 0, on_model_grid != 0, out);
+        return st ? st : finish(m);
+    });
+}
+
 int emg3d_mg_jvec_source_b(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const double* vx, const double* vy,
                            const double* vz, const int32_t* use) {
     if (!mg || !use) return -2;

@@ -5,8 +5,9 @@
 //                   emg3d/optimize.py:176-199): -Re(lambda E s mu_0) on the edges, mapped to cells, components added;
 //   k_gradient_acc = the same for all systems of a batch in one launch, added into a per-cell accumulator in system order;
 //   k_sens_acc    = the survey sensitivity diagonal: W |row|^2 for all pairs of an adjoint and a forward system, into the same
-//                   accumulators (no counterpart in the reference).
-// The last three are the per-cell kernels: one thread per cell behind the same cell_frame, SPLIT = the sum of the three directions
+//                   accumulators (no counterpart in the reference);
+//   k_sens_rows   = the rows themselves, one per pair, into a planar row buffer (MG::sens_rows).
+// The last four are the per-cell kernels: one thread per cell behind the same cell_frame, SPLIT = the sum of the three directions
 // or the directions apart, launched through MG_CELL_LAUNCH (mg.hpp), the accumulators those of MG::cell_acc.
 // Gather form: one thread per CELL sums the contributions of its 12 edges in the order in which the reference's
 // loops (iz, iy, ix ascending, four statements per edge) add them -- deterministic and equal to the reference's
@@ -247,6 +248,59 @@ __global__ void __launch_bounds__(256) k_sens_acc(i64 n0, i64 n1, i64 n2, FieldL
         }
     }
     acc_store<SPLIT>(idx, acc, acc1, acc2, run, run1, run2);
+}
+
+// ---- explicit rows of J (optimize.SurveyJacobian.sensitivity_rows) ----------------------------------------------------------
+// One plane of a row is nC doubles; a complex value goes to two planes (re, then im), a real one to one.
+__device__ __forceinline__ void row_store(double* p, i64, double c) { p[0] = c; }
+__device__ __forceinline__ void row_store(double* p, i64 plane, c128 c) { p[0] = c.re; p[plane] = c.im; }
+
+// The rows k_sens_acc squares, kept: rows[p][dir][part][cell] = row (b_r, b_s) of J at the cell, p the rank of the pair in
+// k_sens_acc's LOOP ORDER (part of the contract: adjoint systems of `use_adj` ascending, outer; forward systems of `use_fwd`
+// ascending, inner) -- no weight table, every pair of the two masks is a row.  dir: one plane (c_x + c_y) + c_z, SPLIT: the three
+// c_x, c_y, c_z; part: re, im for c128, one plane for double; cells x fastest.  Planar, so that every plane is a real cell array
+// (volume_average_adjoint_launch takes it as it is) and a wave stores 64 consecutive doubles.  The same frame, offsets, loads and
+// sens_cell as k_sens_acc: row and |row|^2 round alike.  One thread per cell, every element written exactly once, no atomics, all
+// offsets 64-bit; the twelve lambda values of a receiver stay in registers across the inner loop.  Per launch the reads of
+// k_sens_acc, plus pairs * NDIR * sizeof(T) * nC bytes written.  `rows` must hold popcount(use_adj) * popcount(use_fwd) (masks
+// clipped to nsys bits) * NDIR * NPART * nC doubles.  The two trailing pointers are those of the per-cell launch and not used.
+template <class T, bool SPLIT>
+__global__ void __launch_bounds__(256) k_sens_rows(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* fwd, const T* adj, i64 nE, int nsys, unsigned long long use_fwd,
+                            unsigned long long use_adj, double sr, double si, const double* h0, const double* h1, const double* h2,
+                            double* rows, double*, double*) {
+    const i64 nC[3] = {n0, n1, n2};
+    i64 idx, j[3];
+    double vol;
+    if (!cell_frame(n0, n1, n2, h0, h1, h2, idx, j, vol)) return;
+    if (nsys < 64) {                    // (never a shift by 64: nsys = 64 with bit 63 set is a valid batch)
+        use_fwd &= (1ull << nsys) - 1ull;
+        use_adj &= (1ull << nsys) - 1ull;
+    }
+    constexpr i64 NDIR = SPLIT ? 3 : 1, NPART = (i64)(sizeof(T) / sizeof(double));
+    const i64 plane = n0 * n1 * n2;
+    CellEdges<i64> o;
+    cell_edge_offsets(j, fl, o);
+    double* dst = rows + idx;           // this cell in the first plane of pair p
+    for (unsigned long long ra = use_adj; ra; ra &= ra - 1ull) {          // (wave-uniform: the masks are kernel arguments)
+        const int br = __builtin_ctzll(ra);
+        CellEdges<T> lam;
+        cell_edge_load(adj + (i64)br * nE, o, lam);
+        for (unsigned long long rf = use_fwd; rf; rf &= rf - 1ull) {
+            const int bs = __builtin_ctzll(rf);
+            CellEdges<T> ev;
+            cell_edge_load(fwd + (i64)bs * nE, o, ev);
+            T cc[3];
+            sens_cell<T>(j, nC, vol, lam, ev, sr, si, cc);
+            if (SPLIT) {
+                row_store(dst, plane, cc[0]);
+                row_store(dst + NPART * plane, plane, cc[1]);
+                row_store(dst + 2 * NPART * plane, plane, cc[2]);
+            } else {
+                row_store(dst, plane, (cc[0] + cc[1]) + cc[2]);
+            }
+            dst += NDIR * NPART * plane;
+        }
+    }
 }
 
 // ---- the transpose: cells -> edges (J v of optimize.Jacobian) ---------------------------------------------------------------

@@ -1097,6 +1097,70 @@ struct MG : emg3d_mg {
         return err;
     }
 
+    // ------------------------------------------- explicit rows of J (emg3d_mg_sens_rows, k_sens_rows)
+    // Two buffers of doubles of the handle's own: row_buf[0] = [pairs][dir][part][nC], what the kernel writes; row_buf[1] =
+    // [pairs][dir][part][nM], the same planes on the model grid.  Optional memory (quiet, as try_alloc and the batched vectors): each
+    // grows to the largest call so far -- the old block is given back first (its contents are never needed again) --, is counted in
+    // `bytes` and freed with the handle; a buffer that does not fit answers hipErrorOutOfMemory and leaves the handle usable (with
+    // no buffer of that kind).  ALWAYS A BLOCK OF ITS OWN (raw_alloc), whatever its size, never a piece of an arena chunk: release()
+    // gives back whole blocks only, and the first piece of a chunk has the chunk's address -- releasing it would free the chunk
+    // under every piece carved after it.
+    double* row_buf[2] = {nullptr, nullptr};
+    i64 row_cap[2] = {0, 0};
+    double* row_ensure(int which, i64 n) {
+        if (row_cap[which] >= n) return row_buf[which];
+        if (row_buf[which]) {
+            hipStreamSynchronize(stream);
+            release(row_buf[which]);                // (its `allocs` entry is this block alone, with the size counted below)
+            row_buf[which] = nullptr; row_cap[which] = 0;
+        }
+        const size_t nb = (((size_t)std::max<i64>(n, 1) * sizeof(double)) + 255) & ~(size_t)255;
+        alloc_quiet = true;
+        row_buf[which] = (double*)raw_alloc(nb);
+        alloc_quiet = false;
+        if (row_buf[which]) { row_cap[which] = n; bytes += (i64)nb; }
+        return row_buf[which];
+    }
+    static i64 bit_count(unsigned long long v) { i64 n = 0; for (; v; v &= v - 1ull) ++n; return n; }
+    // out (host) <- the rows of all pairs (adjoint system of use_adj, forward system of use_fwd) in k_sens_rows's order, planes
+    // [p][dir][part][cells]: ONE launch into row_buf[0]; on_model: every plane through volume_average_adjoint_launch with the
+    // factors of its direction (one plane after the other through the scratch mgl.t) into row_buf[1]; then ONE copy to the host.
+    // The summed form on the model grid is Q_x (.) A^T (F_x (.) (c_x + c_y + c_z)): right only if the three directions share
+    // their factors, -2 otherwise.  -2 too: a bad fwd_bvec (a saved copy, as sens_acc_add), an empty mask.  -7: on_model without
+    // model grid or factors.
+    int sens_rows(int fwd_bvec, double sr, double si, const int32_t* use_fwd, const int32_t* use_adj, int split, int on_model, double* out) {
+        const T* fwd = saved_bvec(fwd_bvec);
+        const unsigned long long uf = use_bits(use_fwd), ua = use_bits(use_adj);
+        if (!fwd || !uf || !ua) return -2;
+        if (on_model) {
+            if (!mgl.set || !mgl.factors) return -7;
+            if (!split && (mgl.F[1] != mgl.F[0] || mgl.F[2] != mgl.F[0] || mgl.Q[1] != mgl.Q[0] || mgl.Q[2] != mgl.Q[0])) return -2;
+        }
+        Level<T>& L = *lv0;
+        const i64 ndir = split ? 3 : 1, npart = (i64)(sizeof(T) / sizeof(double));
+        const i64 planes = bit_count(uf) * bit_count(ua) * ndir * npart;        // <= 64 * 64 * 6
+        double* rb = row_ensure(0, planes * L.nCells);
+        if (!rb) return broken ? err : (int)hipErrorOutOfMemory;
+        double* mb = on_model ? row_ensure(1, planes * mgl.nM) : nullptr;
+        if (on_model && !mb) return broken ? err : (int)hipErrorOutOfMemory;
+        e_to_ref(L);
+        double* a[3] = {rb, nullptr, nullptr};
+        MG_CELL_LAUNCH(*this, k_sens_rows, split, a, fwd, (const T*)L.e, L.nE, nsys, uf, ua, sr, si);
+        if (on_model) {
+            VolAvgAdjAxes ax;
+            for (int q = 0; q < 3; ++q) { ax.iptr[q] = mgl.iptr[q]; ax.out[q] = mgl.out[q]; ax.w[q] = mgl.w[q]; }
+            for (i64 q = 0; q < planes && !broken; ++q) {
+                const int k = (int)((q / npart) % ndir);
+                volume_average_adjoint_launch(stream, mb + q * mgl.nM, mgl.t, rb + q * L.nCells, mgl.F[k], mgl.Q[k], nullptr,
+                                              (const double*)L.h[0], (const double*)L.h[1], (const double*)L.h[2], mgl.n, L.nC, ax);
+            }
+        }
+        check_launch();
+        if (err) return err;
+        const hipError_t st = d2h(out, on_model ? mb : rb, (size_t)(planes * (on_model ? mgl.nM : L.nCells)) * sizeof(double));
+        return st == hipSuccess ? 0 : (int)st;
+    }
+
     // ------------------------------------------------------------ smoothers
     // ---- working copies: x<->y transpose and parity split ------------------
     // bt: the batch of a FIELD array (model arrays are shared by the systems: Batch())

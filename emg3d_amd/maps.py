@@ -420,6 +420,43 @@ def sensitivity_diagonal(grid, fwd, adj, smu0, weights, components=False, dtype=
     return out if components else out[0]
 
 
+def sensitivity_rows(grid, fwd, adj, smu0, components=False, dtype=np.float64):
+    """Host restatement (plain numpy) of what ``DeviceMG.sens_rows`` returns: the rows whose weighted squares
+    :func:`sensitivity_diagonal` sums.  Row ``p`` belongs to the pair ``(b_adj, b_fwd) = divmod(p, n_fwd)`` -- the kernel's order:
+    adjoint systems outer, forward systems inner, both ascending -- and is ``(c_x + c_y) + c_z`` with ``c_c =
+    edges2cellaverages_c((adj[b_adj] * fwd[b_fwd]) * smu0)`` and the cell volumes ``(hx * hy) * hz`` of ``grid``, the statements per
+    cell in the kernel's order (``_edges2cellaverages_host``).  ``fwd``: ``(n_fwd, nE)``, ``adj``: ``(n_adj, nE)`` fields
+    ``[fx|fy|fz]`` (both real or complex).  ``dtype``: the real type everything is evaluated in (``np.longdouble``: the yardstick of
+    the tests); the rows are complex of that precision if a field or ``smu0`` is complex.  Returns an array of shape ``(n_adj *
+    n_fwd, ndir) + grid.vnC``, ``ndir`` = 1, or 3 with ``components=True``: ``c_x, c_y, c_z`` apart."""
+    rtype = np.dtype(dtype)
+    fwd, adj = np.atleast_2d(np.asarray(fwd)), np.atleast_2d(np.asarray(adj))
+    cplx = np.iscomplexobj(fwd) or np.iscomplexobj(adj) or np.iscomplexobj(smu0)
+    ftype = np.result_type(rtype, np.complex64) if cplx else rtype
+    nx, ny, nz = (int(n) for n in grid.vnC)
+    shapes = ((nx, ny + 1, nz + 1), (nx + 1, ny, nz + 1), (nx + 1, ny + 1, nz))
+    off = np.cumsum([0] + [int(np.prod(s)) for s in shapes])
+    if fwd.shape[1] != off[3] or adj.shape[1] != off[3]:
+        raise ValueError(f"sensitivity_rows: fields of {off[3]} edges are needed; provided: {fwd.shape}, {adj.shape}.")
+    hx, hy, hz = (np.asarray(h, dtype=np.float64).astype(rtype) for h in grid.h)
+    vol = (hx[:, None, None] * hy[None, :, None]) * hz[None, None, :]
+    s = ftype.type(smu0) if cplx else rtype.type(np.real(smu0))
+    fwd, adj = fwd.astype(ftype), adj.astype(ftype)
+    ndir = 3 if components else 1
+    rows = np.zeros((adj.shape[0] * fwd.shape[0], ndir, nz, ny, nx), dtype=ftype).transpose(0, 1, 4, 3, 2)      # every row F-ordered
+    for ba in range(adj.shape[0]):
+        for bf in range(fwd.shape[0]):
+            prod = (adj[ba] * fwd[bf]) * s
+            cc = _edges2cellaverages_host([prod[off[c]:off[c + 1]].reshape(shapes[c], order='F') for c in range(3)], vol)
+            p = ba * fwd.shape[0] + bf
+            if components:
+                for c in range(3):
+                    rows[p, c] = cc[c]
+            else:
+                rows[p, 0] = (cc[0] + cc[1]) + cc[2]
+    return rows
+
+
 # --------------------------------------------------------------------------
 # Property maps
 # --------------------------------------------------------------------------

@@ -735,7 +735,7 @@ class SurveyJacobian(_JacobianBase):
         self.dtype = np.dtype(np.complex128 if cplx else np.float64)
         self._held = None
         self.synthetic = self.forward_info = self.info = self.jvec_info = self.partial = None
-        self.sensitivity_info = self.sensitivity_partial = None
+        self.sensitivity_info = self.sensitivity_partial = self.rows_info = self.rows_info_imag = None
 
     # ---- the model grid ------------------------------------------------------------------------------------------------
     # With ``model_grid`` the model lives there and reaches ``grid`` through ``model.interpolate2grid(model_grid, grid)``: volume
@@ -841,7 +841,7 @@ class SurveyJacobian(_JacobianBase):
                 dev.set_mask(_first(n, nb))
                 dev.bvec_copy(self._slot[j] + c, dev.EFIELD)
         self.info = self.jvec_info = self.partial = self._chain = None
-        self.sensitivity_info = self.sensitivity_partial = None
+        self.sensitivity_info = self.sensitivity_partial = self.rows_info = self.rows_info_imag = None
         if self.model_grid is not None:
             self._refresh_factors(handles)
 
@@ -1047,7 +1047,8 @@ class SurveyJacobian(_JacobianBase):
         conductivity -- for frequency shards to add.  Deterministic for a given ``batch``; another ``batch`` adds the same
         non-negative terms in another order.  Nothing is allocated but the handle's weight table; works after ``set_model``.
 
-        With ``model_grid`` it raises ``ValueError``: the diagonal on the model grid is not ``A^T`` of this one."""
+        With ``model_grid`` it raises ``ValueError``: the diagonal on the model grid is not ``A^T`` of this one; there
+        ``sensitivity_rows(i_freq, mapped=True)`` gives the rows on the model grid, and the diagonal is ``sum_d W_d |row_d|^2``."""
         mapped = _mapped(mapped)
         if self.model_grid is not None:
             raise ValueError(self._no_diagonal_on_model_grid)
@@ -1096,6 +1097,89 @@ class SurveyJacobian(_JacobianBase):
         if mapped:
             out = tuple(d * d * o for d, o in zip(self._chain_factors(), out))
         return out if components else out[0]
+
+    # ---- the rows of J ------------------------------------------------------------------------------------------------
+    def _row_selection(self, i_freq, receivers):
+        """``(i_freq, receiver indices)`` of ``sensitivity_rows`` after their checks (no device call)."""
+        if isinstance(i_freq, (bool, np.bool_)) or not isinstance(i_freq, (int, np.integer)) or not 0 <= i_freq < self.n_freq:
+            raise ValueError(f"`i_freq` must be an index into `freqs`, 0 .. {self.n_freq - 1}; provided: {i_freq!r}.")
+        if receivers is None:
+            return int(i_freq), list(range(self.n_rec))
+        recs = np.asarray(receivers)
+        if recs.ndim != 1 or recs.size < 1 or recs.dtype.kind not in 'iu' or recs.min() < 0 or recs.max() >= self.n_rec:
+            raise ValueError(f"`receivers` must be a list of receiver indices, 0 .. {self.n_rec - 1} (at least one); provided: "
+                             f"{receivers!r}.")
+        return int(i_freq), [int(r) for r in recs]
+
+    def sensitivity_rows(self, i_freq, receivers=None, components=False, mapped=False):
+        """The rows of ``J`` themselves, for all sources and the receivers ``receivers`` (a list of indices into ``rec``, any order,
+        kept; default: all) at ``freqs[i_freq]``: an array ``rows[i_src, k] + cells``, ``k`` the position in ``receivers``, cells of
+        shape ``grid.vnC`` (F-ordered) -- ``model_grid.vnC`` with ``model_grid`` --, ``complex128`` for a frequency and ``float64``
+        for a Laplace-domain entry of ``freqs``.
+
+        DEFINITION.  Row ``(s, r)`` is ``J_dj = jtvec(e_d) + i jtvec(i e_d)`` for the datum ``d = (s, i_freq, r)`` (``e_d``: one at
+        ``d``, zero elsewhere; Laplace domain: ``jtvec(e_d)``) -- the row whose squares ``sensitivity_diagonal`` sums, and the
+        derivative of datum ``d``: ``jvec(v)[s, i_freq, r] == sum_j rows[s, k][j] v[j]``.
+
+        ``components``, ``mapped``, anisotropic models and ``model_grid`` follow ``jtvec``: ``components=True`` gives a tuple of three
+        such arrays, the rows with respect to sigma_x, sigma_y, sigma_z; ``mapped=True`` multiplies every direction by its chain factor
+        (and adds the three unless ``components``; all of this is linear, so an anisotropic model needs no cross terms); with
+        ``model_grid``, ``mapped=False`` is refused as everywhere, and the device applies ``Q (.) A^T (F (.) .)`` to the real and
+        the imaginary part of every row and direction, so that only model-grid-sized rows cross PCIe.
+
+        The loop is that of ``sensitivity_diagonal``: the selected receivers in chunks of the handle's width ``min(batch, n_src)``,
+        unit rows through the adjoint sources ``jtvec`` builds (every ``receiver_interpolation``, ``adjoint`` and ``electric``), one
+        batched solve per chunk, then ONE ``DeviceMG.sens_rows`` per parked chunk of forward fields, whose real part is
+        ``jtvec(e_d)`` for every source of the chunk, bit for bit.  For a frequency the chunk is then solved a second time with the
+        rows ``i e_d`` -- the very solves of ``jtvec(i e_d)`` -- and the real part of that ``sens_rows`` is the imaginary part of
+        the rows: the definition holds to the last bit, at ``2 n_rec`` solves for all ``n_src n_rec`` rows (``n_rec`` in the Laplace
+        domain; ``2 n_src n_rec`` through ``jtvec``).  The imaginary part of the first solve's product is the same quantity, but
+        not the same bits: the solve of a rotated right-hand side differs from the rotated solution by rounding that leaves the
+        solver amplified (1e-14 .. 3e-13 of a row's largest magnitude at ``tol = 1e-8``), and it is not used.  ``rows_info[k]``
+        is the solver's info dict of receiver ``receivers[k]``'s solve for ``e_d``, ``rows_info_imag[k]`` of that for ``i e_d``
+        (``None`` in the Laplace domain).
+
+        The result is allocated before the first solve (``n_src * len(receivers)`` rows: 16 bytes per cell and row); the device
+        keeps one chunk's rows
+        (``min(batch, n_src)^2`` of them at most) in a buffer of the handle's own that grows to the largest call so far.  If that
+        buffer does not fit, ``HipLibraryError`` names the bytes needed and free: use a smaller ``batch``, or fewer ``receivers`` per
+        call.  Works after ``set_model``; deterministic."""
+        mapped = self._mapped_or_refuse(mapped)
+        j, recs = self._row_selection(i_freq, receivers)
+        handles = self._require_open()
+        ns, nb, nk = self.n_src, self._nb, len(recs)
+        spec = self._specs[j]
+        three = components or (mapped and self.model.case != 0)
+        on_model = self.model_grid is not None
+        nout = 3 if components else 1
+        out = [np.empty((ns, nk) + self._vnM[::-1], dtype=spec.dtype).transpose(0, 1, 4, 3, 2) for _ in range(nout)]    # rows F-ordered
+        chain = self._chain_factors() if mapped and not on_model else None
+        dev, smu0 = handles.target(spec), spec.smu0
+        real = dev.dtype.kind != 'c'
+        infos = [[None] * nk for _ in range(1 if real else 2)]
+        for k0 in range(0, nk, nb):
+            n = min(nb, nk - k0)
+            for part, unit in enumerate((1.0,) if real else (1.0, 1j)):        # e_d, then i e_d: jtvec's solves, jtvec's products
+                w = np.zeros((n, self.n_rec), dtype=dev.dtype)
+                for b in range(n):
+                    w[b, recs[k0 + b]] = unit
+                self._adjoint_sources(dev, smu0, np.conj(w), n)
+                infos[part][k0:k0 + n] = self._solve(dev, self.freqs[j], n)[:n]
+                dest = out if real else [(o.real, o.imag)[part] for o in out]       # views into the rows
+                for c, (i0, nsrc) in enumerate(self._chunks):
+                    got = dev.sens_rows(self._slot[j] + c, smu0, _first(nsrc, nb), _first(n, nb), components=three,
+                                        model_grid=on_model)
+                    for b in range(n):
+                        for s in range(nsrc):
+                            parts = [g.real for g in got[b * nsrc + s]]         # pair p = b * nsrc + s: adjoint systems outer
+                            if chain is not None:
+                                parts = [d * g for d, g in zip(chain, parts)]
+                            if three and not components:
+                                parts = [(parts[0] + parts[1]) + parts[2]]
+                            for q, g in enumerate(parts):
+                                dest[q][i0 + s, k0 + b] = g
+        self.rows_info, self.rows_info_imag = infos[0], None if real else infos[1]
+        return tuple(out) if components else out[0]
 
 
 def jvec(grid, model, src, freq, rec, v, **kwargs):

@@ -71,6 +71,7 @@ class DeviceMG:
         self._vnC = tuple(int(n) for n in grid.vnC)
         self._alias = self._zeta = self._epsr = None        # (from_model_parts: what set_model compares a new model with)
         self._vnM = None                                    # (set_model_grid: the cells of the model grid)
+        self._factors_shared = None                         # (set_regrid_factors: do the three directions share F and Q?)
         hx, hy, hz = (np.ascontiguousarray(h, dtype=np.float64) for h in grid.h)
         return hx, hy, hz, np.ascontiguousarray(grid.origin, dtype=np.float64)
 
@@ -340,6 +341,53 @@ class DeviceMG:
                          f"sens_acc_add: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy), or the "
                          f"accumulator was never reset (grad_acc{'3' if components else ''}_reset).")
 
+    # ---- explicit rows of J: what sens_acc_add squares, kept (optimize.SurveyJacobian.sensitivity_rows) ----
+    def sens_rows(self, fwd_bvec, smu0, use_fwd, use_adj, components=False, model_grid=False):
+        """The rows of all pairs of an adjoint system (``use_adj[b_adj] != 0``; ``lambda`` = system ``b_adj``'s field) and a forward
+        system (``use_fwd[b_fwd] != 0``; ``E`` = slice ``b_fwd`` of the batched vector ``fwd_bvec``, a saved copy): an array of shape
+        ``(n_pairs, ndir) + vnC``, ``complex128`` on a complex handle and ``float64`` otherwise, cells F-ordered.  Pair ``p`` is the
+        ``p``-th in the order of ``sens_acc_add`` (adjoint systems ascending, outer; forward systems ascending, inner); ``ndir`` = 1:
+        ``(c_x + c_y) + c_z``, ``components=True``: 3, the ``c_c = edges2cellaverages_c(s mu_0 lambda E)`` apart.  One launch
+        (``emg3d_mg_sens_rows``), entry for entry the values whose squares ``sens_acc_add`` sums.  ``model_grid=True``: every real and
+        imaginary part as ``Q_c (.) A^T (F_c (.) .)`` on the model grid of ``set_model_grid`` (shape ``(n_pairs, ndir) + vnM``),
+        formed on the device so that only those cross PCIe; without ``components`` the three directions must share their factors.
+        The device keeps the rows in a buffer of the handle's own that grows to the largest call so far (``device_bytes``); the real
+        and imaginary planes it sends are combined here."""
+        a = complex(smu0)
+        uf, ua = self._use_flags(use_fwd, "sens_rows"), self._use_flags(use_adj, "sens_rows")
+        pairs = int(self._lib.emg3d_mg_sens_rows_count(_lib.ptr(uf), _lib.ptr(ua), self.nsys))
+        if pairs < 1:
+            raise ValueError("sens_rows: `use_fwd` and `use_adj` must each name at least one system.")
+        if model_grid and self._vnM is None:
+            raise RuntimeError("sens_rows: the handle has no model grid or no regrid factors (set_model_grid, set_regrid_factors).")
+        if model_grid and not components and self._factors_shared is False:
+            raise ValueError("sens_rows: model_grid=True without components needs regrid factors that the three directions share "
+                             "(set_regrid_factors with the same F and the same Q for x, y, z); ask for components=True and add.")
+        cells = self._vnM if model_grid else self._vnC
+        n = int(np.prod(cells))
+        ndir, npart = (3 if components else 1), (2 if self.dtype == np.complex128 else 1)
+        buf = np.empty((pairs, ndir, npart, n))
+        before = self.device_bytes
+        st = self._lib.emg3d_mg_sens_rows(self._h, int(fwd_bvec), a.real, a.imag, _lib.ptr(uf), _lib.ptr(ua), int(bool(components)),
+                                          int(bool(model_grid)), _lib.ptr(buf))
+        if st == 2:         # hipErrorOutOfMemory: a row buffer did not fit; the handle is still usable
+            need = pairs * ndir * npart * 8 * (self.nC + (n if model_grid else 0))
+            mi = _lib.mem_info(self.device)
+            raise _lib.HipLibraryError(
+                f"sens_rows: the rows of {pairs} pairs need up to {need} bytes of device memory beside the {before} the handle holds, "
+                f"{mi['free'] + mi['pooled_on_device']} bytes are free; ask for fewer pairs per call (SurveyJacobian: a smaller "
+                "`batch` or fewer `receivers`).")
+        if st == -7:
+            self._require_model_grid(st, "emg3d_mg_sens_rows")
+        self._check_bvec(st, "emg3d_mg_sens_rows",
+                         f"sens_rows: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy).")
+        if npart == 2:
+            out = np.empty((pairs, ndir, n), dtype=self.dtype)
+            out.real, out.imag = buf[:, :, 0], buf[:, :, 1]
+        else:
+            out = buf.reshape(pairs, ndir, n)
+        return out.reshape((pairs, ndir) + tuple(cells)[::-1]).transpose(0, 1, 4, 3, 2)         # every row F-ordered
+
     # ---- the accumulators on a model grid (optimize.SurveyJacobian(model_grid=)) ----
     def set_model_grid(self, model_grid):
         """Link the handle to the grid the model lives on (``emg3d_mg_set_model_grid``): the segment tables of volume averaging
@@ -382,6 +430,7 @@ class DeviceMG:
         if st == -2:
             raise ValueError("set_regrid_factors: the directions must share factors as in the handle's first call.")
         self._require_model_grid(st, "emg3d_mg_set_regrid_factors")
+        self._factors_shared = all(a is arrs[0] for arrs in (F, Q) for a in arrs)
 
     def grad_acc_get_model(self, components=False):
         """``Q_x (.) A^T (F_x (.) acc)`` of the accumulator of ``grad_acc_add`` (``emg3d_mg_grad_acc_get_model``; ``A``: volume

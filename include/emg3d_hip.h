@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 114
+#define EMG3D_HIP_ABI_VERSION 115
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -303,6 +303,26 @@ int emg3d_mg_grad_acc3_get(emg3d_mg_t* mg, double* out_x, double* out_y, double*
  *                 accumulator that was never reset, a weight that is not finite.                                           */
 int emg3d_mg_sens_acc_add(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use_fwd,
                           const int32_t* use_adj, const double* weights, int split);
+/* Explicit rows of J (optimize.SurveyJacobian.sensitivity_rows): what sens_acc_add squares, kept.  Every pair of an adjoint system
+ * (use_adj[b_adj] != 0) and a forward system (use_fwd[b_fwd] != 0) is a row; pair number p is its rank in sens_acc_add's loop order
+ * (adjoint systems ascending, outer; forward systems ascending, inner); there is no weight table.  Fields as for sens_acc_add:
+ * lambda = slice b_adj of the level-0 field array, E = slice b_fwd of the batched vector `fwd_bvec` (a saved copy).
+ *   sens_rows_count: the number of pairs of two masks of nsys flags (1 <= nsys <= 64), pure host arithmetic; -2 for bad arguments.
+ *   sens_rows      : out (host) <- [p][dir][part][cell] doubles, planar: dir = one plane (c_x + c_y) + c_z, split != 0: the three
+ *                    c_x, c_y, c_z; part = re, im for a complex128 handle, one plane for a float64 handle; cells F-ordered.  `out`
+ *                    holds sens_rows_count * (split ? 3 : 1) * (complex ? 2 : 1) * cells doubles.  ONE launch writes all rows into
+ *                    a buffer of the handle's own, every element once, no atomics; entry for entry the value whose square
+ *                    sens_acc_add adds.  on_model_grid != 0 (needs emg3d_mg_set_model_grid and emg3d_mg_set_regrid_factors, -7
+ *                    otherwise): every plane y becomes Q_dir (.) A^T (F_dir (.) y) on the model grid (cells = nM) with the launch
+ *                    of grad_acc(3)_get_model, one plane after the other, into a second buffer; without split the factors of
+ *                    direction x are used, which is the row only if the three directions share their factors (-2 otherwise).
+ *                    Then ONE copy to the host.  The two buffers are optional memory like the batched vectors: each grows to the
+ *                    largest call so far, is counted by emg3d_mg_device_bytes and freed with the handle; one that does not fit
+ *                    answers hipErrorOutOfMemory (2) and the handle stays usable.  -2: a bad fwd_bvec (fwd_bvec < 0 included: a
+ *                    saved copy, not the live field), a mask without a used system.                                            */
+int64_t emg3d_mg_sens_rows_count(const int32_t* use_fwd, const int32_t* use_adj, int nsys);
+int emg3d_mg_sens_rows(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use_fwd, const int32_t* use_adj,
+                       int split, int on_model_grid, double* out);
 
 /* ---- sensitivity products (optimize.Jacobian) --------------------------------------------------------------------
  * The reference (v0.17.0) has the gradient only; these are the pieces of J v and J^T w with J = d(data) / d(conductivity) for
