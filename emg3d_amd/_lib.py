@@ -22,7 +22,7 @@ c_double = ctypes.c_double
 c_dp = ctypes.POINTER(ctypes.c_double)
 
 # include/emg3d_hip.h: EMG3D_HIP_ABI_VERSION -- a library built from another header version is refused at load
-ABI_VERSION = 115
+ABI_VERSION = 116
 
 # name -> (restype, argtypes); mirrors include/emg3d_hip.h one to one.
 SIGNATURES = {
@@ -90,6 +90,18 @@ SIGNATURES = {
     "emg3d_mg_sens_acc_add": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_vp, c_int]),
     "emg3d_mg_sens_rows_count": (c_i64, [c_vp, c_vp, c_int]),
     "emg3d_mg_sens_rows": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_int, c_int, c_vp]),
+    "emg3d_rows_create": (c_int, [c_int, c_i64, c_i64, ctypes.POINTER(c_vp)]),
+    "emg3d_rows_destroy": (None, [c_vp]),
+    "emg3d_rows_bytes": (c_i64, [c_vp]),
+    "emg3d_rows_set": (c_int, [c_vp, c_i64, c_vp]),
+    "emg3d_rows_get": (c_int, [c_vp, c_i64, c_vp]),
+    "emg3d_rows_set_chain": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "emg3d_mg_sens_rows_park": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int]),
+    "emg3d_rows_gram": (c_int, [c_vp, c_vp, c_vp]),
+    "emg3d_rows_matvec": (c_int, [c_vp, c_vp, c_vp]),
+    "emg3d_rows_rmatvec": (c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "emg3d_rows_gram_plan": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "emg3d_rows_gram_job": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64)]),
     "emg3d_cells2edges": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "emg3d_mg_jvec_source": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_vp]),
     "emg3d_mg_jvec_source_b": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_vp, c_vp]),
@@ -292,4 +304,20 @@ def sweep_fuse_plan(vnC, direction, npass, dtype=np.complex128, ordering='colour
             r = ranges[per * k:per * (k + 1)]
             out["slabs"].append({"own": (r[0], r[1]), "edges": (r[2], r[3]),
                                  "live": [(r[4 + 2 * p], r[5 + 2 * p]) for p in range(int(npass))]})
+    return out
+
+
+def rows_gram_plan(n_rows, n_cols):
+    """The geometry of the Gram launch of a row store of ``n_rows`` x ``n_cols`` (``emg3d_rows_gram_plan``): host arithmetic, runs
+    without a GPU.  ``slab``, the columns of a K-slab, follows from ``n_cols`` alone; a workgroup owns one slab and one job, a pair
+    of row blocks ``ba >= bb`` of ``block`` rows; ``jobs`` lists their rows ``(a0, a1, b0, b1)``, half open (``a0 == b0``: a diagonal
+    job, which computes the 16 x 16 tile pairs ``ta >= tb`` of its block only)."""
+    info = (c_i64 * 8)()
+    check(load().emg3d_rows_gram_plan(int(n_rows), int(n_cols), info), "emg3d_rows_gram_plan")
+    out = {"block": info[0], "kstep": info[1], "slab": info[2], "nslab": info[3], "nblocks": info[4], "njobs": info[5],
+           "grid": info[6], "lds_bytes": info[7], "tile": 16, "jobs": []}
+    rect = (c_i64 * 4)()
+    for job in range(info[5]):
+        check(load().emg3d_rows_gram_job(int(n_rows), job, rect), "emg3d_rows_gram_job")
+        out["jobs"].append(tuple(rect))
     return out

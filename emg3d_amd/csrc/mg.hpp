@@ -23,6 +23,7 @@
 #include "stencil.hpp"
 #include "gradient.hpp"        // k_gradient_acc, k_sens_acc (acc_add, sens_acc_add)
 #include "regrid.hpp"          // k_volume_average_adjoint (regrid_acc)
+#include "rows.hpp"            // rows_park (sens_rows_park): the row store is a unit of its own
 #include "smooth_qpl.hpp"
 #include "smooth_qc.hpp"
 #include "smooth_thm.hpp"
@@ -1129,6 +1130,25 @@ struct MG : emg3d_mg {
     // their factors, -2 otherwise.  -2 too: a bad fwd_bvec (a saved copy, as sens_acc_add), an empty mask.  -7: on_model without
     // model grid or factors.
     int sens_rows(int fwd_bvec, double sr, double si, const int32_t* use_fwd, const int32_t* use_adj, int split, int on_model, double* out) {
+        SensRowsOnDevice d;
+        const int rc = sens_rows_device(fwd_bvec, sr, si, use_fwd, use_adj, split, on_model, d);
+        if (rc) return rc;
+        const hipError_t st = d2h(out, d.planes, (size_t)(d.pairs * d.ndir * d.npart * d.ncells) * sizeof(double));
+        return st == hipSuccess ? 0 : (int)st;
+    }
+    // The same rows, parked in a row store instead of copied to the host (emg3d_mg_sens_rows_park, csrc/rows.hpp: rows_park): plane
+    // part = 0 of pair p into store row dest[p], on this handle's stream; the caller synchronises it.
+    int sens_rows_park(int fwd_bvec, double sr, double si, const int32_t* use_fwd, const int32_t* use_adj, int split, int on_model,
+                       emg3d_rows* rows, const int32_t* dest, int chain, int sum3) {
+        SensRowsOnDevice d;
+        const int rc = sens_rows_device(fwd_bvec, sr, si, use_fwd, use_adj, split, on_model, d);
+        if (rc) return rc;
+        return rows_park(rows, stream, device, d.planes, d.pairs, (int)d.ndir, (int)d.npart, d.ncells, dest, chain, sum3);
+    }
+    // what both share: the checks, the launches, and where the planes [p][dir][part][ncells] lie afterwards
+    struct SensRowsOnDevice { const double* planes = nullptr; i64 pairs = 0, ndir = 0, npart = 0, ncells = 0; };
+    int sens_rows_device(int fwd_bvec, double sr, double si, const int32_t* use_fwd, const int32_t* use_adj, int split, int on_model,
+                         SensRowsOnDevice& res) {
         const T* fwd = saved_bvec(fwd_bvec);
         const unsigned long long uf = use_bits(use_fwd), ua = use_bits(use_adj);
         if (!fwd || !uf || !ua) return -2;
@@ -1157,8 +1177,9 @@ struct MG : emg3d_mg {
         }
         check_launch();
         if (err) return err;
-        const hipError_t st = d2h(out, on_model ? mb : rb, (size_t)(planes * (on_model ? mgl.nM : L.nCells)) * sizeof(double));
-        return st == hipSuccess ? 0 : (int)st;
+        res.planes = on_model ? mb : rb;
+        res.pairs = planes / (ndir * npart); res.ndir = ndir; res.npart = npart; res.ncells = on_model ? mgl.nM : L.nCells;
+        return 0;
     }
 
     // ------------------------------------------------------------ smoothers

@@ -1,0 +1,64 @@
+// Device-resident row store (csrc/rows.hip): rows of J parked in HBM, and the dense products a data-space method takes from them.
+// This header is what the two translation units share: the geometry of the Gram launch (host arithmetic, also exported as
+// emg3d_rows_gram_plan / emg3d_rows_gram_job) and the one entry the multigrid handle calls (emg3d_mg_sens_rows_park).
+#pragma once
+#include "common.hpp"
+
+struct emg3d_rows;      // the C ABI's emg3d_rows_t
+
+// ---- geometry of k_rows_gram --------------------------------------------------------------------------------------------
+// The store is cut into row blocks of ROWS_BLOCK rows (8 tiles of 16) and into K-slabs of `slab` columns.  A workgroup owns one
+// slab and one JOB = one pair of row blocks (ba >= bb): job = ba (ba + 1) / 2 + bb.  A diagonal job (ba == bb) accumulates the 36
+// tile pairs ta >= tb of its block, an off-diagonal job all 64; both deal them to the 8 waves as t = wave + 8 i, so that a wave
+// holds at most 8 accumulators of 4 f64 per lane (64 VGPRs) -- a 256 x 256 off-diagonal pair of panels would need the whole
+// register file of a compute unit.  The slab length is a function of n_cols ALONE (never of n_rows, the device or a row's
+// position): the summation order of every element of G follows from n_cols.
+constexpr int ROWS_BLOCK = 128;         // rows per block
+constexpr int ROWS_TILE = 16;           // MFMA tile edge
+constexpr int ROWS_KSTEP = 16;          // columns staged per step (4 MFMA k-steps of 4)
+constexpr int ROWS_LD = 145;            // LDS row length of a staged [k][row] tile, doubles: 145 = 17 mod 32, so that the four k of an
+                                        // operand read (16 rows each) fall on disjoint banks but one, and the 16 k of a staging write
+                                        // (one row each) on 16 different ones
+constexpr int ROWS_WAVES = 8;
+constexpr i64 ROWS_SLAB_MIN = 2048;     // columns
+constexpr i64 ROWS_SLABS_MAX = 256;     // at most this many slabs: slab = max(ROWS_SLAB_MIN, ceil(n_cols / 256) rounded up to 16)
+
+struct RowsGramPlan {
+    i64 slab = 0, nslab = 0, nblk = 0, njobs = 0, lds_bytes = 0;
+};
+inline i64 rows_slab_len(i64 n_cols) {
+    const i64 per = (n_cols + ROWS_SLABS_MAX - 1) / ROWS_SLABS_MAX;
+    const i64 s = (per + ROWS_KSTEP - 1) / ROWS_KSTEP * ROWS_KSTEP;
+    return s > ROWS_SLAB_MIN ? s : ROWS_SLAB_MIN;
+}
+inline RowsGramPlan rows_gram_plan(i64 n_rows, i64 n_cols) {
+    RowsGramPlan p;
+    p.slab = rows_slab_len(n_cols);
+    p.nslab = (n_cols + p.slab - 1) / p.slab;
+    p.nblk = (n_rows + ROWS_BLOCK - 1) / ROWS_BLOCK;
+    p.njobs = p.nblk * (p.nblk + 1) / 2;
+    p.lds_bytes = 2 * (i64)ROWS_KSTEP * ROWS_LD * (i64)sizeof(double);
+    return p;
+}
+// job -> its pair of row blocks
+HD void rows_job_blocks(i64 job, i64& ba, i64& bb) {
+    ba = 0;
+    while ((ba + 1) * (ba + 2) / 2 <= job) ++ba;
+    bb = job - ba * (ba + 1) / 2;
+}
+// tile pair number t of a job -> its tiles (ta: rows of G, tb: columns of G); false: the job has no such pair
+HD bool rows_job_tile(bool diag, int t, int& ta, int& tb) {
+    if (!diag) { ta = t >> 3; tb = t & 7; return t < 64; }
+    ta = 0;
+    while ((ta + 1) * (ta + 2) / 2 <= t) ++ta;
+    tb = t - ta * (ta + 1) / 2;
+    return t < 36;
+}
+
+// Store row dest[p] <- plane part = 0 of pair p of `src` = [pairs][ndir][npart][ncells] doubles (device; the layout of k_sens_rows and
+// of its model-grid image), on `stream`; dest[p] < 0 skips the pair.  chain != 0: direction q times the store's chain factor q
+// (emg3d_rows_set_chain); sum3 != 0: one plane (p0 + p1) + p2 of the (scaled) directions.  -2: a store of another size than
+// (sum3 ? 1 : ndir) * ncells columns, a dest[p] >= n_rows, sum3 without three directions, chain without factors of ncells
+// entries, another device.  The caller synchronises `stream` before it returns (dest is read asynchronously).
+int rows_park(emg3d_rows* rows, hipStream_t stream, int device, const double* src, i64 pairs, int ndir, int npart, i64 ncells,
+              const int32_t* dest, int chain, int sum3);

@@ -686,6 +686,9 @@ class SurveyJacobian(_JacobianBase):
     * ``gauss_newton(v, weights)``: both products chunk by chunk -- ``jvec_source_b``, solve, data, ``set_receiver_adjoint_b`` with
       ``conj(weights * data)``, solve, ``grad_acc_add`` -- so that every chunk's forward fields are visited once.  ``weights`` are
       real and broadcast to the data shape; a NaN in ``weights`` or in the data means "no datum".
+    * ``sensitivity_diagonal``, ``sensitivity_rows``, ``park_rows``: ``diag(J^H W J)``, the rows of ``J`` on the host, and the same
+      rows parked in HBM (a ``RowStore``: ``J C_m J^T``, ``C_m J^T y`` and ``J v`` on the device), from ``n_rec`` resp. ``2 n_rec``
+      solves per frequency; see there.
 
     SUMMATION ORDER (part of the contract): ``G_f`` is the sequential sum of the pairs' gradients (``DeviceMG.gradient`` of the
     pair, i.e. ``-Jacobian.jtvec``) over the sources in ascending order starting from zero, formed by the kernel; the result is
@@ -734,6 +737,7 @@ class SurveyJacobian(_JacobianBase):
         cplx = any(sp.dtype.kind == 'c' for sp in self._specs)
         self.dtype = np.dtype(np.complex128 if cplx else np.float64)
         self._held = None
+        self._stores = []           # the row stores of park_rows, closed with the handles
         self.synthetic = self.forward_info = self.info = self.jvec_info = self.partial = None
         self.sensitivity_info = self.sensitivity_partial = self.rows_info = self.rows_info_imag = None
 
@@ -861,6 +865,9 @@ class SurveyJacobian(_JacobianBase):
         return self
 
     def close(self):
+        for store in self._stores:
+            store.close()
+        self._stores = []
         if self._held is not None:
             self._held.close()
             self._held = None
@@ -1180,6 +1187,201 @@ class SurveyJacobian(_JacobianBase):
                                 dest[q][i0 + s, k0 + b] = g
         self.rows_info, self.rows_info_imag = infos[0], None if real else infos[1]
         return tuple(out) if components else out[0]
+
+    def park_rows(self, data=None, components=False, mapped=False):
+        """The rows of ``sensitivity_rows`` for the selected data of the WHOLE survey, parked in HBM instead of returned: a
+        ``RowStore`` whose ``gram``, ``matvec``, ``rmatvec`` and ``step`` run on the device, so that no row crosses PCIe.
+
+        ``data``: a boolean array broadcast to ``(n_src, n_freq, n_rec)``, the data whose rows are kept (default: all).  A receiver
+        with no selected datum at a frequency is not solved for.  The rows are REAL: a datum at a frequency gives two, the real and
+        the imaginary part of its row of ``J`` (``part`` 0 and 1); a Laplace-domain datum gives one.  Their order is ``(i_freq,
+        i_src, i_rec, part)`` ascending over the selected data, and ``store.index`` is the ``(n_rows, 4)`` table of it.
+
+        The loop is that of ``sensitivity_rows``, frequency by frequency: the same chunks of receivers, the same adjoint sources,
+        the same two solves per chunk (``e_d``, then ``i e_d``), the same parked forward fields, and ``DeviceMG.sens_rows_park``
+        where that calls ``sens_rows`` -- the same launches into the handle's row buffer, then one that writes the real parts into
+        their store rows with the chain factors and the sum of the directions applied in the order the host applies them:
+        ``store.row(i)`` equals the matching real or imaginary part of ``sensitivity_rows(...)`` bit for bit.  ``components``,
+        ``mapped``, anisotropic models and ``model_grid`` follow ``sensitivity_rows``, refusals included; the chain factors are
+        uploaded once per call.  ``store.info[j][r]`` holds the solver info dicts ``(of e_d, of i e_d)`` of receiver ``r`` at
+        ``freqs[j]`` (the second ``None`` in the Laplace domain), ``None`` for a receiver that was not solved for.
+
+        The store is ONE block of ``n_rows * n_cols * 8`` bytes (``n_cols``: the cells of a row, times three with ``components``),
+        checked against the free device memory before anything is solved: ``HipLibraryError`` names the bytes needed and free.
+        It is a SNAPSHOT of the model at the time of the call: ``set_model`` leaves it valid as such -- it keeps returning the rows
+        of the model it was parked for -- and a new ``park_rows`` gives those of the new model.  ``store.close()`` frees it; the
+        ``SurveyJacobian`` closes its stores when it closes."""
+        mapped = self._mapped_or_refuse(mapped)
+        handles = self._require_open()
+        shape = (self.n_src, self.n_freq, self.n_rec)
+        if data is None:
+            sel = np.ones(shape, dtype=bool)
+        else:
+            data = np.asarray(data)
+            if data.dtype != np.bool_:
+                raise TypeError(f"`data` must be a boolean array; provided dtype: {data.dtype}.")
+            try:
+                sel = np.broadcast_to(data, shape)
+            except ValueError:
+                raise ValueError(f"`data` must be broadcastable to the data shape {shape}; provided: {data.shape}.") from None
+        nb = self._nb
+        three = components or (mapped and self.model.case != 0)
+        on_model = self.model_grid is not None
+        real = [spec.dtype.kind != 'c' for spec in self._specs]
+        index = np.array([(j, s, r, part) for j in range(self.n_freq) for s in range(self.n_src) for r in range(self.n_rec)
+                          if sel[s, j, r] for part in range(1 if real[j] else 2)], dtype=np.int64).reshape(-1, 4)
+        if index.shape[0] < 1:
+            raise ValueError("`data` selects no datum.")
+        row_of = {tuple(int(x) for x in key): i for i, key in enumerate(index)}
+        ncell = int(np.prod(self._vnM))
+        store = RowStore(solver.DeviceRows(index.shape[0], (3 if components else 1) * ncell, device=self.device), index, shape,
+                         self._vnM, bool(components), real)
+        try:
+            chain = mapped and not on_model
+            if chain:
+                store.rows.set_chain(self._chain_factors())
+            for j, spec in enumerate(self._specs):
+                recs = [r for r in range(self.n_rec) if sel[:, j, r].any()]
+                if not recs:
+                    continue
+                dev, smu0 = handles.target(spec), spec.smu0
+                got = {r: [None, None] for r in recs}
+                for k0 in range(0, len(recs), nb):
+                    n = min(nb, len(recs) - k0)
+                    for part, unit in enumerate((1.0,) if real[j] else (1.0, 1j)):     # e_d, then i e_d: sensitivity_rows' solves
+                        w = np.zeros((n, self.n_rec), dtype=dev.dtype)
+                        for b in range(n):
+                            w[b, recs[k0 + b]] = unit
+                        self._adjoint_sources(dev, smu0, np.conj(w), n)
+                        infos = self._solve(dev, self.freqs[j], n)
+                        for b in range(n):
+                            got[recs[k0 + b]][part] = infos[b]
+                        for c, (i0, nsrc) in enumerate(self._chunks):
+                            dest = np.array([row_of.get((j, i0 + s, recs[k0 + b], part), -1) for b in range(n) for s in range(nsrc)],
+                                            dtype=np.int32)         # pair p = b * nsrc + s: adjoint systems outer
+                            if (dest >= 0).any():
+                                dev.sens_rows_park(self._slot[j] + c, smu0, _first(nsrc, nb), _first(n, nb), store.rows, dest,
+                                                   components=three, model_grid=on_model, chain=chain,
+                                                   sum3=three and not components)
+                for r, pair in got.items():
+                    store.info[j][r] = tuple(pair)
+        except BaseException:
+            store.close()
+            raise
+        self._stores.append(store)
+        return store
+
+
+class RowStore:
+    """Rows of a survey's ``J`` parked on the device (``SurveyJacobian.park_rows``), and the products of a data-space method over
+    them.  The rows are real and ordered as ``index`` says: ``index[i] = (i_freq, i_src, i_rec, part)``, ``part`` 0 the real and 1
+    the imaginary part of the datum's row; ``n_rows`` of them.  ``info[j][r]``: the solver info dicts of receiver ``r`` at
+    frequency ``j`` (``None``: not solved for).  A "stacked" vector has one real entry per row (``stack`` / ``data`` convert from
+    and to complex data arrays); cells are arrays of the shape ``sensitivity_rows`` gives its rows, a tuple of three for a store
+    parked with ``components=True``.  A snapshot of the model it was parked for; a context manager, ``close()`` frees the device
+    block."""
+
+    def __init__(self, rows, index, shape, vnM, components, real):
+        self.rows, self.index, self.components = rows, index, components
+        self.n_rows = index.shape[0]
+        self._shape, self._vnM, self._real = shape, tuple(vnM), list(real)
+        self._ncell = int(np.prod(vnM))
+        self.info = [[None] * shape[2] for _ in range(shape[1])]
+
+    def close(self):
+        self.rows.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def device_bytes(self):
+        return self.rows.device_bytes
+
+    # ---- cells <-> the columns [dir][cell] of a store row ---------------------------------------------------------------------------
+    def _columns(self, x, name):
+        """Cells (an array of the rows' shape; with a ``components`` store a 3-tuple of them, ``None`` = zero, or one array for all
+        three) -> ``n_cols`` doubles."""
+        def flat(a):
+            if a is None:
+                return np.zeros(self._ncell)
+            a = np.asarray(a)
+            if np.iscomplexobj(a):
+                raise TypeError(f"`{name}` must be real.")
+            if a.shape != self._vnM:
+                raise ValueError(f"`{name}` must have shape {self._vnM}; provided: {a.shape}.")
+            return a.astype(np.float64, copy=False).ravel(order='F')
+        if isinstance(x, (tuple, list)):
+            if not self.components or len(x) != 3 or all(a is None for a in x):
+                raise ValueError(f"`{name}`: a 3-tuple (x, y, z), not all None, needs a store parked with components=True.")
+            return np.concatenate([flat(a) for a in x])
+        return np.concatenate([flat(x)] * 3) if self.components else flat(x)
+
+    def _cells(self, cols):
+        parts = tuple(c.reshape(self._vnM, order='F') for c in cols.reshape(-1, self._ncell))
+        return parts if self.components else parts[0]
+
+    def _stacked(self, y, name):
+        y = np.asarray(y)
+        if y.shape == self._shape:
+            return self.stack(y)
+        if y.shape != (self.n_rows,) or np.iscomplexobj(y):
+            raise ValueError(f"`{name}` must be a real vector of {self.n_rows} entries (one per row) or a data array of shape "
+                             f"{self._shape}; provided: {y.shape}, {y.dtype}.")
+        return np.ascontiguousarray(y, dtype=np.float64)
+
+    # ---- stacked real vectors <-> complex data --------------------------------------------------------------------------------------
+    def stack(self, d):
+        """A data array ``(n_src, n_freq, n_rec)`` -> the stacked real vector: entry ``i`` is the real (``part`` 0) or imaginary
+        (``part`` 1) part of the datum ``index[i]``; a real array gives its value to both parts (weights)."""
+        d = np.asarray(d)
+        if d.shape != self._shape:
+            raise ValueError(f"the data must have shape (n_src, n_freq, n_rec) = {self._shape}; provided: {d.shape}.")
+        j, s, r, part = self.index.T
+        v = d[s, j, r]
+        if not np.iscomplexobj(v):
+            return np.ascontiguousarray(v, dtype=np.float64)
+        return np.where(part == 0, v.real, v.imag)
+
+    def data(self, y):
+        """The inverse of ``stack``: a stacked real vector -> ``(n_src, n_freq, n_rec)`` complex data (NaN where no datum was
+        selected; the imaginary part of a Laplace-domain datum is zero)."""
+        y = np.asarray(y, dtype=np.float64)
+        if y.shape != (self.n_rows,):
+            raise ValueError(f"`y` must have {self.n_rows} entries (one per row); provided: {y.shape}.")
+        out = np.full(self._shape, np.nan, dtype=np.complex128)
+        j, s, r, part = self.index.T
+        out[s, j, r] = 0.0
+        np.add.at(out, (s, j, r), np.where(part == 0, y, 1j * y))
+        return out
+
+    # ---- rows and products ----------------------------------------------------------------------------------------------------------
+    def row(self, i):
+        """Row ``i`` on the host, cells shaped as the rows of ``sensitivity_rows`` (a tuple of three with ``components``)."""
+        return self._cells(self.rows.get_row(i))
+
+    def gram(self, cm=None):
+        """``J C_m J^T`` over the stacked rows, ``(n_rows, n_rows)``; ``cm``: the diagonal of ``C_m`` as cells (default: one).
+        ``DeviceRows.gram``: deterministic and exactly symmetric."""
+        return self.rows.gram(None if cm is None else self._columns(cm, 'cm'))
+
+    def matvec(self, v):
+        """``J v`` as a stacked real vector (``data`` folds it); ``v``: cells, as ``jvec`` takes them.  No solve."""
+        return self.rows.matvec(self._columns(v, 'v'))
+
+    def rmatvec(self, y, cm=None):
+        """``C_m J^T y`` as cells; ``y``: a stacked real vector, or a data array (``stack``)."""
+        return self._cells(self.rows.rmatvec(self._stacked(y, 'y'), None if cm is None else self._columns(cm, 'cm')))
+
+    def step(self, residual, weights, cm=None, damping=0.0):
+        """The data-space Gauss-Newton step ``dm = C_m J^T (J C_m J^T + damping W^-1)^-1 r``, by definition
+        ``rmatvec(np.linalg.solve(gram(cm) + damping * np.diag(1 / w), r), cm)`` with ``r`` and ``w`` the stacked ``residual`` and
+        ``weights`` (stacked vectors or data arrays)."""
+        r, w = self._stacked(residual, 'residual'), self._stacked(weights, 'weights')
+        return self.rmatvec(np.linalg.solve(self.gram(cm) + damping * np.diag(1 / w), r), cm)
 
 
 def jvec(grid, model, src, freq, rec, v, **kwargs):

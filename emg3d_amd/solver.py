@@ -388,6 +388,43 @@ class DeviceMG:
             out = buf.reshape(pairs, ndir, n)
         return out.reshape((pairs, ndir) + tuple(cells)[::-1]).transpose(0, 1, 4, 3, 2)         # every row F-ordered
 
+    def sens_rows_park(self, fwd_bvec, smu0, use_fwd, use_adj, rows, dest, components=False, model_grid=False, chain=False,
+                       sum3=False):
+        """``sens_rows`` up to its copy to the host, the real part of pair ``p`` written into row ``dest[p]`` of the ``DeviceRows``
+        ``rows`` instead (``emg3d_mg_sens_rows_park``; ``dest[p] < 0`` skips the pair): the same arguments, the same checks, the same
+        launches into the handle's row buffers, then one launch that parks.  A store row's columns are ``[dir][cell]``;
+        ``chain=True`` multiplies direction ``q`` by ``rows``' chain factor ``q`` (``DeviceRows.set_chain``), ``sum3=True`` (needs
+        ``components``) writes the one plane ``(p0 + p1) + p2`` of the (scaled) directions -- the operations of
+        ``SurveyJacobian.sensitivity_rows`` in their order, so that a parked row is that row bit for bit.  The handle's stream is
+        synchronised before the call returns."""
+        a = complex(smu0)
+        uf, ua = self._use_flags(use_fwd, "sens_rows_park"), self._use_flags(use_adj, "sens_rows_park")
+        pairs = int(self._lib.emg3d_mg_sens_rows_count(_lib.ptr(uf), _lib.ptr(ua), self.nsys))
+        d = np.ascontiguousarray(dest, dtype=np.int32)
+        if pairs < 1 or d.shape != (pairs,):
+            raise ValueError(f"sens_rows_park: `use_fwd` and `use_adj` name {pairs} pairs (at least one is needed), `dest` has shape "
+                             f"{d.shape}.")
+        if model_grid and self._vnM is None:
+            raise RuntimeError("sens_rows_park: the handle has no model grid or no regrid factors (set_model_grid, set_regrid_factors).")
+        if model_grid and not components and self._factors_shared is False:
+            raise ValueError("sens_rows_park: model_grid=True without components needs regrid factors that the three directions share.")
+        before = self.device_bytes
+        st = self._lib.emg3d_mg_sens_rows_park(self._h, int(fwd_bvec), a.real, a.imag, _lib.ptr(uf), _lib.ptr(ua), int(bool(components)),
+                                               int(bool(model_grid)), rows._h, _lib.ptr(d), int(bool(chain)), int(bool(sum3)))
+        if st == 2:         # hipErrorOutOfMemory: a row buffer did not fit; the handle is still usable
+            n = int(np.prod(self._vnM if model_grid else self._vnC))
+            need = pairs * (3 if components else 1) * (2 if self.dtype == np.complex128 else 1) * 8 * (self.nC + (n if model_grid else 0))
+            mi = _lib.mem_info(self.device)
+            raise _lib.HipLibraryError(
+                f"sens_rows_park: the rows of {pairs} pairs need up to {need} bytes of device memory beside the {before} the handle "
+                f"holds, {mi['free'] + mi['pooled_on_device']} bytes are free; ask for fewer pairs per call (SurveyJacobian: a smaller "
+                "`batch`).")
+        if st == -7:
+            self._require_model_grid(st, "emg3d_mg_sens_rows_park")
+        self._check_bvec(st, "emg3d_mg_sens_rows_park",
+                         f"sens_rows_park: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy), or the "
+                         "store does not fit the rows (its device, its columns, a destination row, its chain factors).")
+
     # ---- the accumulators on a model grid (optimize.SurveyJacobian(model_grid=)) ----
     def set_model_grid(self, model_grid):
         """Link the handle to the grid the model lives on (``emg3d_mg_set_model_grid``): the segment tables of volume averaging
@@ -830,6 +867,121 @@ class DeviceMG:
     def stream_ptr(self):
         """The handle's HIP stream (``hipStream_t`` as an integer) for ``torch.cuda.ExternalStream``."""
         return int(self._lib.emg3d_mg_stream(self._h) or 0)
+
+
+class DeviceRows:
+    """A row store on the device (``emg3d_rows_*``): ``n_rows`` x ``n_cols`` doubles, row-major, in ONE block of HBM of its own, and
+    the dense products a data-space method takes from rows that stay there -- ``gram`` (``R diag(cm) R^T`` on the f64 matrix cores),
+    ``matvec`` (``R v``) and ``rmatvec`` (``cm (.) R^T y``).  It belongs to no ``DeviceMG``: the handles of a survey park into one
+    store (``DeviceMG.sens_rows_park``); ``set_row`` fills it from the host.  Creating it checks its bytes against the device's free
+    memory first: a store that cannot fit raises ``HipLibraryError`` with the bytes needed and free, and nothing was allocated.
+    Every product is deterministic (no atomics; the column slabs follow from ``n_cols`` alone): see ``gram``.  A context manager;
+    ``close()`` frees the block."""
+
+    def __init__(self, n_rows, n_cols, device=0):
+        self._lib = _lib.load()
+        self._h = None
+        self.n_rows, self.n_cols, self.device = int(n_rows), int(n_cols), int(device)
+        if self.n_rows < 1 or self.n_cols < 1:
+            raise ValueError(f"DeviceRows: `n_rows` and `n_cols` must be at least 1; provided: {n_rows!r}, {n_cols!r}.")
+        h = ctypes.c_void_p()
+        st = self._lib.emg3d_rows_create(self.device, self.n_rows, self.n_cols, ctypes.byref(h))
+        if st == 2:         # hipErrorOutOfMemory, from the check before the allocation or from the allocation itself
+            mi = _lib.mem_info(self.device)
+            raise _lib.HipLibraryError(
+                f"DeviceRows: {self.n_rows} rows of {self.n_cols} columns need {self.n_rows * self.n_cols * 8} bytes of device memory "
+                f"in one block, {mi['free'] + mi['pooled_on_device']} bytes are free; park fewer data per store (SurveyJacobian."
+                "park_rows: a `data` mask, or a `model_grid`).")
+        _lib.check(st, "emg3d_rows_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self._lib.emg3d_rows_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _open(self):
+        if not self._h:
+            raise RuntimeError("DeviceRows: the store is closed.")
+        return self._h
+
+    def _vector(self, a, n, what):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != (n,):
+            raise ValueError(f"DeviceRows.{what} must have shape {(n,)}; provided: {a.shape}.")
+        return a
+
+    @property
+    def device_bytes(self):
+        """The bytes of the block (256-byte aligned); plus those of the chain factors once ``set_chain`` was called, and of the
+        products' workspace (operands, slab partials, results), which grows to the largest product so far and is kept."""
+        return int(self._lib.emg3d_rows_bytes(self._open()))
+
+    def _row(self, i):
+        if isinstance(i, (bool, np.bool_)) or not isinstance(i, (int, np.integer)) or not 0 <= i < self.n_rows:
+            raise IndexError(f"DeviceRows: row {i!r} is outside 0 .. {self.n_rows - 1}.")
+        return int(i)
+
+    def set_row(self, i, row):
+        """Row ``i`` <- ``row`` (``n_cols`` doubles of the host)."""
+        r = self._vector(row, self.n_cols, "set_row: `row`")
+        _lib.check(self._lib.emg3d_rows_set(self._open(), self._row(i), _lib.ptr(r)), "emg3d_rows_set")
+
+    def get_row(self, i):
+        """Row ``i`` on the host."""
+        out = np.empty(self.n_cols)
+        _lib.check(self._lib.emg3d_rows_get(self._open(), self._row(i), _lib.ptr(out)), "emg3d_rows_get")
+        return out
+
+    def set_chain(self, factors):
+        """Three arrays of ``n`` doubles kept on the device for ``DeviceMG.sens_rows_park(chain=True)``; ``None`` frees them."""
+        if factors is None:
+            _lib.check(self._lib.emg3d_rows_set_chain(self._open(), 0, None, None, None), "emg3d_rows_set_chain")
+            return
+        f = [np.ascontiguousarray(np.asarray(a).ravel(order='F'), dtype=np.float64) for a in factors]
+        if len(f) != 3 or any(a.shape != f[0].shape for a in f):
+            raise ValueError("DeviceRows.set_chain: `factors` must be three arrays of one size.")
+        _lib.check(self._lib.emg3d_rows_set_chain(self._open(), f[0].size, *(_lib.ptr(a) for a in f)), "emg3d_rows_set_chain")
+
+    def gram(self, cm=None):
+        """``G = R diag(cm) R^T``, ``(n_rows, n_rows)``: ``G[a, b] = sum_j R[a, j] cm[j] R[b, j]``; ``cm``: ``n_cols`` doubles, default
+        all one.  ``k_rows_gram`` on ``v_mfma_f64_16x16x4_f64``, the partial sums of the column slabs added in ascending order by a
+        second pass.  The same bits at every call; ``G == G.T`` exactly; without ``cm`` a store with its rows permuted gives the
+        permuted ``G`` bit for bit (with ``cm`` the factor multiplies the row of the smaller index, which a permutation may change:
+        then bit for bit only where the products ``cm[j] R[b, j]`` are exact, to rounding otherwise)."""
+        c = None if cm is None else self._vector(cm, self.n_cols, "gram: `cm`")
+        out = np.empty((self.n_rows, self.n_rows))
+        _lib.check(self._lib.emg3d_rows_gram(self._open(), None if c is None else _lib.ptr(c), _lib.ptr(out)), "emg3d_rows_gram")
+        return out
+
+    def matvec(self, v):
+        """``R v``, ``n_rows`` doubles: per row and column slab a fixed tree, the slabs added in ascending order (deterministic)."""
+        v = self._vector(v, self.n_cols, "matvec: `v`")
+        out = np.empty(self.n_rows)
+        _lib.check(self._lib.emg3d_rows_matvec(self._open(), _lib.ptr(v), _lib.ptr(out)), "emg3d_rows_matvec")
+        return out
+
+    def rmatvec(self, y, cm=None):
+        """``cm (.) R^T y``, ``n_cols`` doubles: per column ``acc = acc + y[i] * R[i, j]`` over the rows ascending, then
+        ``cm[j] * acc`` (no ``cm``: ``acc``), every operation rounded once -- bit for bit that loop in numpy."""
+        y = self._vector(y, self.n_rows, "rmatvec: `y`")
+        c = None if cm is None else self._vector(cm, self.n_cols, "rmatvec: `cm`")
+        out = np.empty(self.n_cols)
+        _lib.check(self._lib.emg3d_rows_rmatvec(self._open(), _lib.ptr(y), None if c is None else _lib.ptr(c), _lib.ptr(out)),
+                   "emg3d_rows_rmatvec")
+        return out
 
 
 class FrequencyHandles:

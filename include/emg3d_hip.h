@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 115
+#define EMG3D_HIP_ABI_VERSION 116
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -323,6 +323,57 @@ int emg3d_mg_sens_acc_add(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double s
 int64_t emg3d_mg_sens_rows_count(const int32_t* use_fwd, const int32_t* use_adj, int nsys);
 int emg3d_mg_sens_rows(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use_fwd, const int32_t* use_adj,
                        int split, int on_model_grid, double* out);
+
+/* ---- row store (solver.DeviceRows, optimize.SurveyJacobian.park_rows) ----------------------------------------------
+ * n_rows x n_cols doubles, row-major, on one device, in ONE block of its own (a quiet allocation, never a piece of a handle's
+ * arena), and the dense products a data-space method takes from rows of J that stay in HBM.  A store belongs to no handle: the
+ * handles of a survey (complex128 for its frequencies, float64 for its Laplace-domain entries) park into the same store.
+ *   rows_create   : checks n_rows * n_cols * 8 bytes (rounded up to 256) against emg3d_hip_mem_info (free + what the handles' pool
+ *                   holds on that device) BEFORE it allocates: a store that cannot fit answers hipErrorOutOfMemory (2) without an
+ *                   attempt.  -2: n_rows < 1, n_cols < 1, out NULL.
+ *   rows_bytes    : the block's bytes; plus those of the chain factors once set, and of the products' workspace (operands, slab
+ *                   partials, results: one more block, at most 256 MiB of partials, that grows to the largest product so far and is
+ *                   kept, because allocating it per call costs more than the kernels).
+ *   rows_set / rows_get: row i <- / -> n_cols doubles of the host.  -2: i outside 0 .. n_rows - 1, a NULL pointer.
+ *   rows_set_chain: three arrays of n doubles (host), kept on the device for sens_rows_park(chain != 0); n = 0 frees them.
+ *   sens_rows_park: emg3d_mg_sens_rows up to its copy to the host -- the same checks (-2, -7, 2), the same launch into the handle's
+ *                   row buffer, the same model-grid launches --, then ONE launch (k_rows_park) writes plane part = 0 (the real part)
+ *                   of pair p into store row dest[p]; dest[p] < 0 skips the pair; no two pairs may name the same row.  A store row's
+ *                   columns are [dir][cell], cells F-ordered: n_cols = cells (split = 0, or sum3) or 3 * cells.  chain != 0:
+ *                   direction q is written as chain_q[cell] * value; sum3 != 0 (needs split): one plane (p0 + p1) + p2 of the (scaled)
+ *                   directions.  No contraction: with the operations of SurveyJacobian.sensitivity_rows in their order, a parked
+ *                   row equals the row that returns, bit for bit.  The handle's stream is synchronised before the call returns, so
+ *                   every later operation of the store sees the rows.  -2 also: a store on another device or of another n_cols, a
+ *                   dest[p] >= n_rows, chain without factors of `cells` entries.
+ *   rows_gram     : G (host, n_rows^2 doubles) <- R diag(cm) R^T, G[a][b] = sum_j R[a][j] cm[j] R[b][j]; cm: n_cols doubles (host) or
+ *                   NULL (= 1).  k_rows_gram: v_mfma_f64_16x16x4_f64, one workgroup per K-slab of columns and pair of row blocks
+ *                   (rows_gram_plan), cm multiplied into one operand while staging; the slab partials are summed in ascending slab
+ *                   order by k_rows_gram_reduce, which writes the lower triangle and its mirror.  No atomics: G is the same bits
+ *                   at every call, G == G^T exactly, and the slab partition follows from n_cols alone, so that without cm (or with a
+ *                   cm whose products cm[j] R[b][j] are exact) a store with its rows permuted gives the permuted G bit for bit; with
+ *                   a general cm the factor sits on the row of the smaller index, and a permuted pair agrees to rounding only.
+ *   rows_matvec   : out (host, n_rows) <- R v, v: n_cols doubles (host); per row and slab a fixed tree, the slab partials summed in
+ *                   ascending order: deterministic.
+ *   rows_rmatvec  : out (host, n_cols) <- cm (.) R^T y: per column acc = acc + y[i] * R[i][j] over the rows ascending, then
+ *                   cm[j] * acc (cm NULL: acc), every operation rounded once -- bit for bit that loop on the host.
+ *   rows_gram_plan: host arithmetic, needs no GPU.  out[8] <- rows per block, columns staged per step, columns per K-slab, slabs,
+ *                   row blocks, jobs (pairs of row blocks ba >= bb), workgroups (jobs * slabs), LDS bytes per workgroup.  The slab
+ *                   length is a function of n_cols alone.  rows_gram_job: out[4] <- the rows [a0, a1) x [b0, b1) of job `job`; a
+ *                   diagonal job (a0 == b0) computes the 16 x 16 tile pairs ta >= tb of its block only.  -2: bad arguments.   */
+typedef struct emg3d_rows emg3d_rows_t;
+int emg3d_rows_create(int device, int64_t n_rows, int64_t n_cols, emg3d_rows_t** out);
+void emg3d_rows_destroy(emg3d_rows_t* rows);
+int64_t emg3d_rows_bytes(const emg3d_rows_t* rows);
+int emg3d_rows_set(emg3d_rows_t* rows, int64_t i, const double* host);
+int emg3d_rows_get(emg3d_rows_t* rows, int64_t i, double* host);
+int emg3d_rows_set_chain(emg3d_rows_t* rows, int64_t n, const double* cx, const double* cy, const double* cz);
+int emg3d_mg_sens_rows_park(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use_fwd, const int32_t* use_adj,
+                            int split, int on_model_grid, emg3d_rows_t* rows, const int32_t* dest, int chain, int sum3);
+int emg3d_rows_gram(emg3d_rows_t* rows, const double* cm, double* G);
+int emg3d_rows_matvec(emg3d_rows_t* rows, const double* v, double* out);
+int emg3d_rows_rmatvec(emg3d_rows_t* rows, const double* y, const double* cm, double* out);
+int emg3d_rows_gram_plan(int64_t n_rows, int64_t n_cols, int64_t* out);
+int emg3d_rows_gram_job(int64_t n_rows, int64_t job, int64_t* out);
 
 /* ---- sensitivity products (optimize.Jacobian) --------------------------------------------------------------------
  * The reference (v0.17.0) has the gradient only; these are the pieces of J v and J^T w with J = d(data) / d(conductivity) for
