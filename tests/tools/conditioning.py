@@ -10,9 +10,6 @@ import sys, os
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", ".."))
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "..", "tests"))
-import emg3d_amd as em
-import bench
-from oracle import oracle
 from reduced_line import LineSys, axes
 
 LD = np.longdouble
@@ -77,6 +74,9 @@ def main():
     fixed = [tuple(int(v) for v in t.split(',')) for t in sys.argv[3].split(';')] if len(sys.argv) > 3 else None
     if fixed:
         nlines = len(fixed)
+    import emg3d_amd as em          # (here, not at the top: tests/test_oracle_truth.py imports the elimination orders without a GPU stack)
+    import bench
+    from oracle import oracle
     grid, model, sfield, cycle = bench.build_problem(em, wl, 1.0)
     vm = em.VolumeModel(grid, model, sfield)
     from test_gpu_fullsize import _smooth_field
