@@ -22,7 +22,7 @@ c_double = ctypes.c_double
 c_dp = ctypes.POINTER(ctypes.c_double)
 
 # include/emg3d_hip.h: EMG3D_HIP_ABI_VERSION -- a library built from another header version is refused at load
-ABI_VERSION = 116
+ABI_VERSION = 117
 
 # name -> (restype, argtypes); mirrors include/emg3d_hip.h one to one.
 SIGNATURES = {
@@ -102,6 +102,11 @@ SIGNATURES = {
     "emg3d_rows_rmatvec": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "emg3d_rows_gram_plan": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64)]),
     "emg3d_rows_gram_job": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "emg3d_rows_smooth_plan": (c_int, [c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_i64)]),
+    "emg3d_smooth3d": (c_int, [c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
+                               c_vp]),
+    "emg3d_rows_smooth": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
+    "emg3d_rows_clone": (c_int, [c_vp, ctypes.POINTER(c_vp)]),
     "emg3d_cells2edges": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "emg3d_mg_jvec_source": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_vp]),
     "emg3d_mg_jvec_source_b": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_vp, c_vp]),
@@ -321,3 +326,48 @@ def rows_gram_plan(n_rows, n_cols):
         check(load().emg3d_rows_gram_job(int(n_rows), job, rect), "emg3d_rows_gram_job")
         out["jobs"].append(tuple(rect))
     return out
+
+
+def rows_smooth_plan(shape, axis):
+    """How the library smooths arrays of ``shape`` = ``(nx, ny, nz)`` along ``axis`` (0, 1, 2) -- ``emg3d_rows_smooth_plan``: host
+    arithmetic, runs without a GPU.  ``path`` 0: a line stays in LDS between its sweeps and passes, 1: one thread per line through
+    HBM; ``workgroups`` is per array (a launch over ``n`` arrays has ``n`` times as many)."""
+    info = (c_i64 * 6)()
+    check(load().emg3d_rows_smooth_plan(int(shape[0]), int(shape[1]), int(shape[2]), int(axis), info), "emg3d_rows_smooth_plan")
+    return {"path": info[0], "lines_per_workgroup": info[1], "lds_bytes": info[2], "workgroups": info[3], "min_lines": info[4],
+            "lines": info[5]}
+
+
+def factor_ptrs(factors, shape):
+    """The nine factor pointers of ``emg3d_smooth3d`` / ``emg3d_rows_smooth`` from ``factors`` = per axis ``(lo, cp, inv)`` or ``None``;
+    -> (pointers, the arrays that must outlive the call)."""
+    if len(factors) != 3:
+        raise ValueError("`factors` must have one entry per axis: (lo, cp, inv) or None.")
+    ptrs, keep = [], []
+    for f, n in zip(factors, shape):
+        if f is None:
+            ptrs += [None, None, None]
+            continue
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in f]
+        if len(arrs) != 3 or any(a.shape != (int(n),) for a in arrs):
+            raise ValueError(f"the factors of an axis must be three arrays (lo, cp, inv) of its {int(n)} cells.")
+        keep += arrs
+        ptrs += [ptr(a) for a in arrs]
+    return ptrs, keep
+
+
+def smooth3d(data, shape, factors, passes, scale=None, scale_after=False, device=0):
+    """``emg3d_smooth3d`` on ``data``, ``(n_arrays, nx * ny * nz)`` doubles (each array x fastest), in place: ``L^T`` (``scale_after``
+    False) or ``L`` of maps.SmoothingCovariance; ``scale``: ``nx * ny * nz`` doubles or None."""
+    nx, ny, nz = (int(n) for n in shape)
+    if data.dtype != np.float64 or not data.flags.c_contiguous or data.ndim != 2 or data.shape[1] != nx * ny * nz:
+        raise ValueError(f"`data` must be C-contiguous float64 of shape (n_arrays, {nx * ny * nz}).")
+    ptrs, keep = factor_ptrs(factors, (nx, ny, nz))
+    w = None
+    if scale is not None:
+        w = np.ascontiguousarray(scale, dtype=np.float64)
+        if w.shape != (nx * ny * nz,):
+            raise ValueError(f"`scale` must have {nx * ny * nz} entries; provided: {w.shape}.")
+    check(load().emg3d_smooth3d(int(device), data.shape[0], nx, ny, nz, None if w is None else ptr(w), *ptrs, int(passes),
+                                1 if scale_after else 0, ptr(data)), "emg3d_smooth3d")
+    return data

@@ -6,6 +6,7 @@
 //   k_rows_gram_reduce    the slab partials summed in ascending slab order, the lower triangle mirrored
 //   k_rows_matvec(_reduce) R v: per (row, slab) a fixed tree, the slab partials summed in ascending order
 //   k_rows_rmatvec        cm (.) R^T y: one thread per column, rows ascending, no contraction
+//   k_rows_smooth_*       the smoothing model covariance: tridiagonal line solves over every row, in place (rows_cov.hpp)
 //
 // No floating-point atomics anywhere: every result is a fixed expression of the store, of n_cols and of the operands.
 #include "../../include/emg3d_hip.h"
@@ -14,6 +15,7 @@
 #include <new>
 
 #include "rows.hpp"
+#include "rows_cov.hpp"
 
 struct emg3d_rows {
     int device = 0;
@@ -448,4 +450,97 @@ int emg3d_rows_rmatvec(emg3d_rows_t* r, const double* y, const double* cm, doubl
     st = launched();
     if (st) { (void)hipStreamSynchronize(r->stream); return st; }
     return to_host(r, out, dout, (size_t)r->n_cols * sizeof(double));
+}
+
+// ====================================================================================================== smoothing covariance
+int emg3d_rows_smooth_plan(int64_t nx, int64_t ny, int64_t nz, int axis, int64_t* out) {
+    if (nx < 1 || ny < 1 || nz < 1 || axis < 0 || axis > 2 || !out) return -2;
+    const RowsSmoothPlan p = rows_smooth_plan(nx, ny, nz, axis);
+    out[0] = p.path; out[1] = p.lines; out[2] = p.lds_bytes; out[3] = p.wg; out[4] = SMOOTH_LINES_MIN; out[5] = p.nl;
+    return 0;
+}
+
+namespace {
+// the factors of an axis come as three arrays or as none
+bool smooth_factors_ok(const double* const (&h)[3][3]) {
+    for (int ax = 0; ax < 3; ++ax)
+        if ((h[ax][0] != nullptr) != (h[ax][1] != nullptr) || (h[ax][0] != nullptr) != (h[ax][2] != nullptr)) return false;
+    return true;
+}
+}  // namespace
+
+int emg3d_smooth3d(int device, int64_t n_arrays, int64_t nx, int64_t ny, int64_t nz, const double* scale, const double* lo_x,
+                   const double* cp_x, const double* inv_x, const double* lo_y, const double* cp_y, const double* inv_y,
+                   const double* lo_z, const double* cp_z, const double* inv_z, int passes, int scale_after, double* data) {
+    const double* const h[3][3] = {{lo_x, cp_x, inv_x}, {lo_y, cp_y, inv_y}, {lo_z, cp_z, inv_z}};
+    if (n_arrays < 1 || nx < 1 || ny < 1 || nz < 1 || passes < 1 || !data || !smooth_factors_ok(h)) return -2;
+    if (ny > (((int64_t)1 << 59) / nx) || nz > (((int64_t)1 << 59) / (nx * ny)) || n_arrays > (((int64_t)1 << 59) / (nx * ny * nz))) return -2;
+    HIP_TRY(hipSetDevice(device));
+    const i64 dims[3] = {nx, ny, nz};
+    const size_t cells = (size_t)(nx * ny * nz), total = cells * (size_t)n_arrays;
+    double *d_data = nullptr, *d_w = nullptr, *d_f = nullptr;
+    DEV_ALLOC(d_data, total * sizeof(double));
+    DEV_ALLOC(d_w, (scale ? cells : 1) * sizeof(double));
+    DEV_ALLOC(d_f, (size_t)3 * (size_t)(nx + ny + nz) * sizeof(double));
+    HIP_TRY(hipMemcpy(d_data, data, total * sizeof(double), hipMemcpyHostToDevice));
+    if (scale) HIP_TRY(hipMemcpy(d_w, scale, cells * sizeof(double), hipMemcpyHostToDevice));
+    SmoothFactors f;
+    double* next = d_f;
+    for (int ax = 0; ax < 3; ++ax)
+        for (int q = 0; q < 3 && h[ax][0]; ++q) {
+            HIP_TRY(hipMemcpy(next, h[ax][q], (size_t)dims[ax] * sizeof(double), hipMemcpyHostToDevice));
+            f.p[ax][q] = next;
+            next += dims[ax];
+        }
+    const int st = smooth_run(nullptr, d_data, n_arrays, nx, ny, nz, 1, scale ? d_w : nullptr, f, passes, scale_after);
+    HIP_TRY(hipDeviceSynchronize());
+    if (st) return st;
+    HIP_TRY(hipMemcpy(data, d_data, total * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int emg3d_rows_smooth(emg3d_rows_t* r, int64_t nx, int64_t ny, int64_t nz, int planes, const double* scale, const double* lo_x,
+                      const double* cp_x, const double* inv_x, const double* lo_y, const double* cp_y, const double* inv_y,
+                      const double* lo_z, const double* cp_z, const double* inv_z, int passes) {
+    const double* const h[3][3] = {{lo_x, cp_x, inv_x}, {lo_y, cp_y, inv_y}, {lo_z, cp_z, inv_z}};
+    if (!r || nx < 1 || ny < 1 || nz < 1 || planes < 1 || passes < 1 || !smooth_factors_ok(h)) return -2;
+    // (no product before it is known to fit: nx ny nz <= n_cols, and planes divides n_cols)
+    if (nx > r->n_cols || ny > r->n_cols / nx || nz > r->n_cols / (nx * ny)) return -2;
+    if (r->n_cols % planes != 0 || nx * ny * nz != r->n_cols / planes) return -2;
+    if (r->n_rows > (((int64_t)1 << 59) / planes)) return -2;           // (the number of arrays, n_rows * planes)
+    ROWS_TRY(hipSetDevice(r->device));
+    const i64 dims[3] = {nx, ny, nz};
+    size_t sizes[10] = {scale ? (size_t)r->n_cols : 1};
+    for (int ax = 0; ax < 3; ++ax)
+        for (int q = 0; q < 3; ++q) sizes[1 + 3 * ax + q] = h[ax][0] ? (size_t)dims[ax] : 1;
+    double* w[10];      // scale, then lo, cp, inv per axis
+    if (!carve(r, sizes, w)) return (int)hipErrorOutOfMemory;
+    if (scale) { const int st = to_device(r, w[0], scale, (size_t)r->n_cols * sizeof(double)); if (st) return st; }
+    SmoothFactors f;
+    for (int ax = 0; ax < 3; ++ax)
+        for (int q = 0; q < 3 && h[ax][0]; ++q) {
+            const int st = to_device(r, w[1 + 3 * ax + q], h[ax][q], (size_t)dims[ax] * sizeof(double));
+            if (st) return st;
+            f.p[ax][q] = w[1 + 3 * ax + q];
+        }
+    const int st = smooth_run(r->stream, r->R, r->n_rows * planes, nx, ny, nz, planes, scale ? w[0] : nullptr, f, passes, 0);
+    if (st) { (void)hipStreamSynchronize(r->stream); return st; }
+    ROWS_TRY(hipStreamSynchronize(r->stream));
+    return 0;
+}
+
+int emg3d_rows_clone(emg3d_rows_t* r, emg3d_rows_t** out) {
+    if (!r || !out) return -2;
+    const int st = emg3d_rows_create(r->device, r->n_rows, r->n_cols, out);     // (the same memory check, the same answers)
+    if (st) return st;
+    emg3d_rows* c = *out;
+    const hipError_t cp = hipMemcpyAsync(c->R, r->R, (size_t)r->n_rows * (size_t)r->n_cols * sizeof(double), hipMemcpyDeviceToDevice, r->stream);
+    const hipError_t sy = cp == hipSuccess ? hipStreamSynchronize(r->stream) : cp;
+    if (sy != hipSuccess) {
+        (void)hipGetLastError();
+        emg3d_rows_destroy(c);
+        *out = nullptr;
+        return (int)sy;
+    }
+    return 0;
 }

@@ -458,6 +458,177 @@ def sensitivity_rows(grid, fwd, adj, smu0, components=False, dtype=np.float64):
 
 
 # --------------------------------------------------------------------------
+# Smoothing model covariance
+# --------------------------------------------------------------------------
+def smoothing_matrix(h, ell):
+    """One axis of ``SmoothingCovariance``: the symmetric tridiagonal ``T = I + ell^2 H^-1/2 D^T diag(1/d) D H^-1/2`` of the cell
+    widths ``h`` and the correlation length ``ell`` as ``(diag, off)``, float64 -- ``off[i] = -ell^2 / (d[i] sqrt(h[i] h[i+1]))``,
+    ``diag[i] = 1 + ell^2 / (h[i] d[i-1]) + ell^2 / (h[i] d[i])`` with ``d[i] = (h[i] + h[i+1]) / 2`` and the term whose ``d``
+    does not exist dropped (Neumann ends)."""
+    h = np.asarray(h, dtype=np.float64)
+    n = h.size
+    ell = np.float64(ell)
+    diag, off = np.ones(n), np.zeros(max(n - 1, 0))
+    d = [(h[i] + h[i + 1]) / 2 for i in range(n - 1)]
+    for i in range(n - 1):
+        off[i] = -(ell * ell) / (d[i] * np.sqrt(h[i] * h[i + 1]))
+    for i in range(n):
+        t = np.float64(1.0)
+        if i > 0:
+            t = t + (ell * ell) / (h[i] * d[i - 1])
+        if i < n - 1:
+            t = t + (ell * ell) / (h[i] * d[i])
+        diag[i] = t
+    return diag, off
+
+
+def smoothing_factors(h, ell):
+    """The factors ``(lo, cp, inv)`` of ``smoothing_matrix(h, ell)`` for the line solve of ``SmoothingCovariance``, computed once, in
+    NumPy float64 scalars, in this order: ``inv[0] = 1 / diag[0]``; ``lo[i] = off[i-1]``, ``inv[i] = 1 / (diag[i] - off[i-1]
+    cp[i-1])`` for ``i >= 1``; ``cp[i] = off[i] inv[i]`` for ``i < n - 1``; ``lo[0] = cp[n-1] = 0``.  ``None`` where ``T = I``
+    (one cell, or ``ell = 0``): the axis is skipped."""
+    diag, off = smoothing_matrix(h, ell)
+    n = diag.size
+    if n == 1 or ell == 0:
+        return None
+    lo, cp, inv = np.zeros(n), np.zeros(n), np.zeros(n)
+    inv[0] = 1 / diag[0]
+    for i in range(n):
+        if i >= 1:
+            lo[i] = off[i - 1]
+            inv[i] = 1 / (diag[i] - off[i - 1] * cp[i - 1])
+        if i < n - 1:
+            cp[i] = off[i] * inv[i]
+    return lo, cp, inv
+
+
+def smooth_lines_host(a, axis, factors, passes=1):
+    """``passes`` line solves in a row along ``axis`` of the float64 array ``a``, IN PLACE: sequential Thomas, vectorised over the
+    lines, every element through the same scalar operations, each rounded once -- ``a[0] *= inv[0]``; ``a[i] = (a[i] - lo[i]
+    a[i-1]) inv[i]`` upwards; ``a[i] = a[i] - cp[i] a[i+1]`` downwards.  The reference the device equals bit for bit."""
+    lo, cp, inv = factors
+    v = np.moveaxis(a, axis, 0)
+    n = v.shape[0]
+    for _ in range(passes):
+        v[0] = v[0] * inv[0]
+        for i in range(1, n):
+            v[i] = (v[i] - lo[i] * v[i - 1]) * inv[i]
+        for i in range(n - 2, -1, -1):
+            v[i] = v[i] - cp[i] * v[i + 1]
+    return a
+
+
+class SmoothingCovariance:
+    """A smoothing model covariance ``C = L L^T`` on the cells of ``grid``, as tridiagonal line solves along x, y and z.
+
+    Per axis ``S_axis = T^-1`` is one implicit diffusion step with the correlation length of that axis (``smoothing_matrix``:
+    symmetric positive definite, smallest eigenvalue 1, on a uniform grid the discrete ``exp(-|x| / ell')`` family); the three act
+    on different Kronecker factors, so ``S = S_z S_y S_x`` is symmetric.  With ``w`` the standard deviations per cell and ``p =
+    passes``: ``L = diag(w) S^p``, ``L^T = S^p diag(w)``, ``C = diag(w) S^2p diag(w)``.
+
+    ``lengths``: a scalar or ``(lx, ly, lz)`` in metres, ``>= 0``; ``std``: a scalar, an array of ``grid.vnC``, or a 3-tuple of
+    those (one per direction, for the three planes of a ``components`` row store; there is no cross-direction covariance);
+    ``passes``: an int ``>= 1``.  ``factors``: per axis ``(lo, cp, inv)`` (``smoothing_factors``), ``None`` for an axis that is
+    skipped (one cell or length 0).
+
+    ``sqrt_t(v)`` is ``L^T v``: ``w * v``, then for x, y, z in this order the solve ``passes`` times in a row on every line of the
+    axis; ``sqrt(v)`` is ``L v``: the same sweeps, then ``w *``; ``apply(v) = sqrt(sqrt_t(v))`` is ``C v``.  ``v``: an array of
+    ``grid.vnC``, or a 3-tuple of them.  They run on the device (``emg3d_smooth3d``, ``k_rows_smooth_*``); ``host=True`` runs the
+    numpy loop ``smooth_lines_host`` instead, which the device equals bit for bit.  They are stateless: every plane is uploaded,
+    smoothed and downloaded on its own, on ``device`` (the constructor's, default 0, or the method's ``device=``; a ``RowStore``
+    made by ``with_covariance`` passes its store's device); the result does not depend on the device.  The order of the axes
+    changes the last bits, so it is part of the contract."""
+
+    def __init__(self, grid, lengths, std=1.0, passes=1, device=0):
+        self.grid, self.device = grid, int(device)
+        self.vnC = tuple(int(n) for n in grid.vnC)
+        ln = np.asarray(lengths, dtype=np.float64)
+        if ln.shape not in ((), (3,)) or not np.all(np.isfinite(ln)) or np.any(ln < 0):
+            raise ValueError(f"`lengths` must be a scalar or (lx, ly, lz), finite and >= 0; provided: {lengths!r}.")
+        self.lengths = tuple(float(x) for x in np.broadcast_to(ln, (3,)))
+        if isinstance(passes, (bool, np.bool_)) or not isinstance(passes, (int, np.integer)) or passes < 1:
+            raise ValueError(f"`passes` must be an int >= 1; provided: {passes!r}.")
+        self.passes = int(passes)
+        self.std = std
+        if isinstance(std, (tuple, list)):
+            if len(std) != 3:
+                raise ValueError(f"`std` as a tuple must have three entries (one per direction); provided: {len(std)}.")
+            self._w = tuple(self._std_plane(s) for s in std)
+        else:
+            self._w = self._std_plane(std)
+        self.factors = tuple(smoothing_factors(h, ell) for h, ell in zip(grid.h, self.lengths))
+
+    def _std_plane(self, s):
+        """One plane of `std` as F-ordered doubles; None for the scalar 1 (a product with 1 is exact: the same bits)."""
+        s = np.asarray(s, dtype=np.float64)
+        if s.shape not in ((), self.vnC) or not np.all(np.isfinite(s)) or np.any(s < 0):
+            raise ValueError(f"`std` must be a scalar or an array of shape {self.vnC} (or a 3-tuple of those), finite and >= 0; "
+                             f"provided shape: {s.shape}.")
+        if s.shape == () and s == 1.0:
+            return None
+        return np.ascontiguousarray(np.broadcast_to(s, self.vnC).ravel(order='F'))
+
+    def scale(self, planes):
+        """The standard deviations as the columns ``[plane][cell]`` (cells F-ordered) of a row of ``planes`` planes, or ``None``
+        where they are all the scalar 1."""
+        if isinstance(self._w, tuple):
+            if planes != 3:
+                raise ValueError("a `std` per direction (a 3-tuple) needs three planes: a 3-tuple `v`, a `components` row store.")
+            w = self._w
+        else:
+            w = (self._w,) * planes
+        if all(p is None for p in w):
+            return None
+        return np.concatenate([np.ones(int(np.prod(self.vnC))) if p is None else p for p in w])
+
+    def _run(self, v, scale_after, host, device=None):
+        three = isinstance(v, (tuple, list))
+        parts = list(v) if three else [v]
+        if three and len(parts) != 3:
+            raise ValueError(f"`v` as a tuple must have three entries; provided: {len(parts)}.")
+        ncell = int(np.prod(self.vnC))
+        cols = []
+        for a in parts:
+            a = np.asarray(a)
+            if np.iscomplexobj(a):
+                raise TypeError("`v` must be real.")
+            if a.shape != self.vnC:
+                raise ValueError(f"`v` must have shape {self.vnC} (or be a 3-tuple of such arrays); provided: {a.shape}.")
+            cols.append(np.array(a, dtype=np.float64).ravel(order='F'))        # (a copy: the caller's array stays)
+        w = self.scale(len(parts))
+        out = []
+        for q, a in enumerate(cols):
+            wq = None if w is None else w[q * ncell:(q + 1) * ncell]
+            if host:
+                if wq is not None and not scale_after:
+                    a = wq * a
+                a3 = a.reshape(self.vnC, order='F')
+                for axis, f in enumerate(self.factors):
+                    if f is not None:
+                        smooth_lines_host(a3, axis, f, self.passes)
+                a = a3.ravel(order='F')
+                if wq is not None and scale_after:
+                    a = wq * a
+            else:
+                a = _lib.smooth3d(a.reshape(1, ncell), self.vnC, self.factors, self.passes, scale=wq, scale_after=scale_after,
+                                  device=self.device if device is None else int(device))[0]
+            out.append(a.reshape(self.vnC, order='F'))
+        return tuple(out) if three else out[0]
+
+    def sqrt_t(self, v, host=False, device=None):
+        """``L^T v = S^p (w * v)``."""
+        return self._run(v, False, host, device)
+
+    def sqrt(self, v, host=False, device=None):
+        """``L v = w * S^p v``."""
+        return self._run(v, True, host, device)
+
+    def apply(self, v, host=False, device=None):
+        """``C v = L (L^T v)``."""
+        return self.sqrt(self.sqrt_t(v, host=host, device=device), host=host, device=device)
+
+
+# --------------------------------------------------------------------------
 # Property maps
 # --------------------------------------------------------------------------
 class _Map:

@@ -1287,6 +1287,7 @@ class RowStore:
         self._shape, self._vnM, self._real = shape, tuple(vnM), list(real)
         self._ncell = int(np.prod(vnM))
         self.info = [[None] * shape[2] for _ in range(shape[1])]
+        self.cov = None             # with_covariance: the rows are those of B = J L
 
     def close(self):
         self.rows.close()
@@ -1363,25 +1364,75 @@ class RowStore:
         """Row ``i`` on the host, cells shaped as the rows of ``sensitivity_rows`` (a tuple of three with ``components``)."""
         return self._cells(self.rows.get_row(i))
 
+    def _refuse_cm(self, cm, what):
+        if self.cov is not None and cm is not None:
+            raise ValueError(f"RowStore.{what}: this store holds B = J L of a SmoothingCovariance (with_covariance), which is its model "
+                             "covariance; a diagonal `cm` on top of it is not J C_m J^T -- use the store it was made from.")
+
     def gram(self, cm=None):
         """``J C_m J^T`` over the stacked rows, ``(n_rows, n_rows)``; ``cm``: the diagonal of ``C_m`` as cells (default: one).
-        ``DeviceRows.gram``: deterministic and exactly symmetric."""
+        ``DeviceRows.gram``: deterministic and exactly symmetric.  On a store made by ``with_covariance``: ``J C J^T = B B^T``
+        (``cm`` is refused)."""
+        self._refuse_cm(cm, 'gram')
         return self.rows.gram(None if cm is None else self._columns(cm, 'cm'))
 
     def matvec(self, v):
         """``J v`` as a stacked real vector (``data`` folds it); ``v``: cells, as ``jvec`` takes them.  No solve."""
+        if self.cov is not None:
+            raise ValueError("RowStore.matvec: this store holds B = J L of a SmoothingCovariance (with_covariance), and B v is not "
+                             "J v -- use the store it was made from.")
         return self.rows.matvec(self._columns(v, 'v'))
 
     def rmatvec(self, y, cm=None):
-        """``C_m J^T y`` as cells; ``y``: a stacked real vector, or a data array (``stack``)."""
-        return self._cells(self.rows.rmatvec(self._stacked(y, 'y'), None if cm is None else self._columns(cm, 'cm')))
+        """``C_m J^T y`` as cells; ``y``: a stacked real vector, or a data array (``stack``).  On a store made by
+        ``with_covariance``: ``C J^T y = cov.sqrt(B^T y)``, on the store's device (``cm`` is refused)."""
+        self._refuse_cm(cm, 'rmatvec')
+        out = self._cells(self.rows.rmatvec(self._stacked(y, 'y'), None if cm is None else self._columns(cm, 'cm')))
+        return out if self.cov is None else self.cov.sqrt(out, device=self.rows.device)
 
     def step(self, residual, weights, cm=None, damping=0.0):
         """The data-space Gauss-Newton step ``dm = C_m J^T (J C_m J^T + damping W^-1)^-1 r``, by definition
         ``rmatvec(np.linalg.solve(gram(cm) + damping * np.diag(1 / w), r), cm)`` with ``r`` and ``w`` the stacked ``residual`` and
-        ``weights`` (stacked vectors or data arrays)."""
+        ``weights`` (stacked vectors or data arrays).  On a store made by ``with_covariance`` ``C_m`` is its covariance (``cm`` is
+        refused)."""
+        self._refuse_cm(cm, 'step')
         r, w = self._stacked(residual, 'residual'), self._stacked(weights, 'weights')
         return self.rmatvec(np.linalg.solve(self.gram(cm) + damping * np.diag(1 / w), r), cm)
+
+    def with_covariance(self, cov, inplace=False):
+        """A ``RowStore`` whose rows are ``B = J L`` for the smoothing covariance ``cov = L L^T`` (``maps.SmoothingCovariance``):
+        row ``d`` of ``B`` is ``L^T j_d``, every row smoothed in place on the device (``DeviceRows.smooth``, ``k_rows_smooth_*``: per
+        axis the store is read once and written once) and equal, bit for bit, to ``cov.sqrt_t(row, host=True)``.  On it ``gram()``
+        is ``J C J^T = B B^T`` (the products without ``cm``, with their bitwise contracts), ``rmatvec(y)`` is ``C J^T y =
+        cov.sqrt(B^T y)``, ``step`` the data-space step with ``C_m = C``, ``row(i)`` row ``i`` of ``B``; ``cm`` arguments,
+        ``matvec`` and a second ``with_covariance`` are refused.  Same ``index`` and ``info``; the attribute ``cov``.
+
+        ``inplace=False`` clones the store first (a second block of the same size, checked against the free memory): the original
+        stays valid and the caller owns the new store (a context manager; ``close()``).  ``inplace=True`` converts this store, costs
+        no second block and returns it.  ``cov``'s grid must have the shape of the store's rows (the model grid for a ``mapped``
+        store of a ``model_grid``); every plane of a ``components`` store is smoothed on its own, with the matching entry of a
+        3-tuple ``std``."""
+        if self.cov is not None:
+            raise ValueError("RowStore.with_covariance: this store already holds B = J L of a covariance; a second one would give "
+                             "J L L' -- use the store it was made from.")
+        if tuple(getattr(cov, 'vnC', ())) != self._vnM:
+            raise ValueError(f"RowStore.with_covariance: `cov` must be a SmoothingCovariance on a grid of the rows' shape {self._vnM}; "
+                             f"provided: {getattr(cov, 'vnC', None)}.")
+        planes = 3 if self.components else 1
+        scale = cov.scale(planes)
+        if inplace:
+            new = self
+        else:
+            new = RowStore(self.rows.clone(), self.index, self._shape, self._vnM, self.components, self._real)
+            new.info = self.info
+        try:
+            new.rows.smooth(self._vnM, planes, cov.factors, cov.passes, scale=scale)
+        except BaseException:
+            if not inplace:
+                new.close()
+            raise
+        new.cov = cov
+        return new
 
 
 def jvec(grid, model, src, freq, rec, v, **kwargs):

@@ -983,6 +983,40 @@ class DeviceRows:
                    "emg3d_rows_rmatvec")
         return out
 
+    def clone(self):
+        """A second store of the same size on the same device with the same rows (a device-to-device copy; chain factors are not
+        copied).  The memory check of a new store: one that cannot fit raises ``HipLibraryError`` and nothing was allocated."""
+        new = object.__new__(DeviceRows)
+        new._lib, new._h = self._lib, None
+        new.n_rows, new.n_cols, new.device = self.n_rows, self.n_cols, self.device
+        h = ctypes.c_void_p()
+        st = self._lib.emg3d_rows_clone(self._open(), ctypes.byref(h))
+        if st == 2:
+            mi = _lib.mem_info(self.device)
+            raise _lib.HipLibraryError(
+                f"DeviceRows.clone: a second store of {self.n_rows} rows of {self.n_cols} columns needs "
+                f"{self.n_rows * self.n_cols * 8} bytes of device memory in one block, {mi['free'] + mi['pooled_on_device']} bytes "
+                "are free; convert the store in place instead.")
+        _lib.check(st, "emg3d_rows_clone")
+        new._h = h
+        return new
+
+    def smooth(self, shape, planes, factors, passes, scale=None):
+        """Every row <- ``L^T`` row of ``maps.SmoothingCovariance``, in place (``emg3d_rows_smooth``, ``k_rows_smooth_*``): a row is
+        ``planes`` arrays of ``shape`` = ``(nx, ny, nz)``, x fastest, each smoothed on its own; ``factors``: per axis ``(lo, cp,
+        inv)`` or ``None`` (skipped); ``scale``: ``n_cols`` doubles multiplied in first, or ``None``.  Bit for bit the numpy loop of
+        ``SmoothingCovariance.sqrt_t(host=True)`` on every row."""
+        shape = tuple(int(n) for n in shape)
+        if len(shape) != 3:
+            raise ValueError(f"DeviceRows.smooth: `shape` must be (nx, ny, nz); provided: {shape}.")
+        ptrs, keep = _lib.factor_ptrs(factors, shape)
+        w = None if scale is None else self._vector(scale, self.n_cols, "smooth: `scale`")
+        st = self._lib.emg3d_rows_smooth(self._open(), *shape, int(planes), None if w is None else _lib.ptr(w), *ptrs, int(passes))
+        if st == -2:
+            raise ValueError(f"DeviceRows.smooth: {planes} planes of shape {shape} are not the {self.n_cols} columns of a row, or "
+                             f"`passes` = {passes!r} is less than 1 (emg3d_rows_smooth: -2).")
+        _lib.check(st, "emg3d_rows_smooth")
+
 
 class FrequencyHandles:
     """The handles of a loop over frequencies on one grid and model: one ``DeviceMG`` per dtype (and optional extra ``key``),

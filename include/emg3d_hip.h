@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 116
+#define EMG3D_HIP_ABI_VERSION 117
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -374,6 +374,38 @@ int emg3d_rows_matvec(emg3d_rows_t* rows, const double* v, double* out);
 int emg3d_rows_rmatvec(emg3d_rows_t* rows, const double* y, const double* cm, double* out);
 int emg3d_rows_gram_plan(int64_t n_rows, int64_t n_cols, int64_t* out);
 int emg3d_rows_gram_job(int64_t n_rows, int64_t job, int64_t* out);
+
+/* ---- smoothing model covariance (maps.SmoothingCovariance, optimize.RowStore.with_covariance) ----------------------
+ * C = L L^T with L = diag(w) S^p, S = S_z S_y S_x, S_axis = T^-1 one implicit diffusion step along an axis: T the symmetric
+ * tridiagonal matrix I + ell^2 H^-1/2 D^T diag(1/d) D H^-1/2 of the axis' cell widths h, centre distances d and correlation
+ * length ell (Neumann ends; smallest eigenvalue 1).  The caller factorises T once on the host (maps.SmoothingCovariance: lo, cp,
+ * inv, n doubles per axis) and the library solves one line a[0 .. n-1] by sequential Thomas, every operation rounded once:
+ *     a[0] = a[0] * inv[0];   a[i] = (a[i] - lo[i] * a[i-1]) * inv[i], i = 1 .. n-1;   a[i] = a[i] - cp[i] * a[i+1], i = n-2 .. 0.
+ * L^T on an array of nx x ny x nz doubles (x fastest): a = w * a if a scale is given; then for x, y, z in this order the solve
+ * `passes` times in a row on every line of the axis.  L runs the same sweeps and multiplies by w last.  An axis whose three
+ * factor pointers are NULL, or of length 1, is skipped.  The result equals that loop in numpy BIT FOR BIT whichever kernel runs
+ * it (k_rows_smooth_*: a line stays in LDS between its sweeps and passes, so that an axis reads and writes the data once; a line
+ * that no LDS holds goes one thread per line through HBM).
+ *   rows_smooth_plan: host arithmetic, needs no GPU.  out[6] <- path of `axis` (0, 1, 2 = x, y, z) on arrays of nx x ny x nz: 0 the
+ *                     line is resident in LDS, 1 through HBM; lines per workgroup; LDS bytes per workgroup; workgroups PER ARRAY
+ *                     (a launch has that many times the number of arrays); the least lines a workgroup of path 0 takes (path 1
+ *                     is chosen exactly when the LDS cannot hold that many); lines per array.  -2: bad arguments.
+ *   smooth3d        : stateless: data (host, n_arrays arrays back to back) is uploaded, smoothed by the same kernels and
+ *                     downloaded.  scale: nx * ny * nz doubles (host) for every array, or NULL; scale_after = 0: L^T, 1: L.
+ *                     -2: a size < 1, passes < 1, data NULL, an axis with some but not all of its factors.
+ *   rows_smooth     : L^T on every row of a store in place; a row is `planes` arrays of nx x ny x nz, each smoothed on its own;
+ *                     scale: n_cols doubles (host) or NULL.  Factors and scale go through the store's workspace; runs on the
+ *                     store's stream, synchronised before it returns.  -2: nx * ny * nz * planes != n_cols, passes < 1, ...
+ *   rows_clone      : *out <- a second store of the same size on the same device with the same rows (device to device; the chain
+ *                     factors are not copied).  The memory check and the answers of rows_create.                             */
+int emg3d_rows_smooth_plan(int64_t nx, int64_t ny, int64_t nz, int axis, int64_t* out);
+int emg3d_smooth3d(int device, int64_t n_arrays, int64_t nx, int64_t ny, int64_t nz, const double* scale, const double* lo_x,
+                   const double* cp_x, const double* inv_x, const double* lo_y, const double* cp_y, const double* inv_y,
+                   const double* lo_z, const double* cp_z, const double* inv_z, int passes, int scale_after, double* data);
+int emg3d_rows_smooth(emg3d_rows_t* rows, int64_t nx, int64_t ny, int64_t nz, int planes, const double* scale, const double* lo_x,
+                      const double* cp_x, const double* inv_x, const double* lo_y, const double* cp_y, const double* inv_y,
+                      const double* lo_z, const double* cp_z, const double* inv_z, int passes);
+int emg3d_rows_clone(emg3d_rows_t* rows, emg3d_rows_t** out);
 
 /* ---- sensitivity products (optimize.Jacobian) --------------------------------------------------------------------
  * The reference (v0.17.0) has the gradient only; these are the pieces of J v and J^T w with J = d(data) / d(conductivity) for
