@@ -22,7 +22,7 @@ c_double = ctypes.c_double
 c_dp = ctypes.POINTER(ctypes.c_double)
 
 # include/emg3d_hip.h: EMG3D_HIP_ABI_VERSION -- a library built from another header version is refused at load
-ABI_VERSION = 117
+ABI_VERSION = 118
 
 # name -> (restype, argtypes); mirrors include/emg3d_hip.h one to one.
 SIGNATURES = {
@@ -106,7 +106,11 @@ SIGNATURES = {
     "emg3d_smooth3d": (c_int, [c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
                                c_vp]),
     "emg3d_rows_smooth": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
+    "emg3d_rows_smooth_l": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
     "emg3d_rows_clone": (c_int, [c_vp, ctypes.POINTER(c_vp)]),
+    "emg3d_rows_project_plan": (c_int, [c_i64, c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "emg3d_rows_project": (c_int, [c_vp, c_vp, c_i64, c_vp]),
+    "emg3d_rows_colsumsq": (c_int, [c_vp, c_vp, c_vp]),
     "emg3d_cells2edges": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "emg3d_mg_jvec_source": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_vp]),
     "emg3d_mg_jvec_source_b": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_vp, c_vp]),
@@ -326,6 +330,17 @@ def rows_gram_plan(n_rows, n_cols):
         check(load().emg3d_rows_gram_job(int(n_rows), job, rect), "emg3d_rows_gram_job")
         out["jobs"].append(tuple(rect))
     return out
+
+
+def rows_project_plan(n_rows, m, n_cols):
+    """The geometry of ``emg3d_rows_project`` for ``Y[m x n_cols] = M[m x n_rows] R`` (``emg3d_rows_project_plan``): host arithmetic,
+    runs without a GPU, and is what the launch itself calls.  A workgroup owns a panel of ``cols`` columns and a block of ``block``
+    output rows and walks the source in steps of ``kstep`` rows; ``passes`` blocks, each one pass over the source; ``panels``
+    follows from ``n_cols`` alone; ``last_rows``: the rows the last block's kernel covers (32, 64, 128 or ``block``)."""
+    info = (c_i64 * 8)()
+    check(load().emg3d_rows_project_plan(int(n_rows), int(m), int(n_cols), info), "emg3d_rows_project_plan")
+    return {"block": info[0], "cols": info[1], "kstep": info[2], "passes": info[3], "grid": info[4], "lds_bytes": info[5],
+            "panels": info[6], "last_rows": info[7], "tile": 16}
 
 
 def rows_smooth_plan(shape, axis):

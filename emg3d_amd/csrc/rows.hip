@@ -6,6 +6,9 @@
 //   k_rows_gram_reduce    the slab partials summed in ascending slab order, the lower triangle mirrored
 //   k_rows_matvec(_reduce) R v: per (row, slab) a fixed tree, the slab partials summed in ascending order
 //   k_rows_rmatvec        cm (.) R^T y: one thread per column, rows ascending, no contraction
+//   k_rows_project        Y = M R into another store: per (panel of columns, block of output rows) one workgroup on the f64 MFMA, one
+//                         accumulation chain over the source's rows per element, each element written once
+//   k_rows_colsumsq       sum_i s[i] R[i][j]^2: one thread per column, rows ascending, no contraction
 //   k_rows_smooth_*       the smoothing model covariance: tridiagonal line solves over every row, in place (rows_cov.hpp)
 //
 // No floating-point atomics anywhere: every result is a fixed expression of the store, of n_cols and of the operands.
@@ -278,6 +281,122 @@ __global__ void __launch_bounds__(256) k_rows_rmatvec(const double* __restrict__
     out[j] = cm ? cm[j] * acc : acc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- project
+// Y[m x n_cols] = M[m x n_rows] R[n_rows x n_cols], the contraction over the ROWS of the store: every column is on its own, there is
+// no split over k, no partial and no second pass.  grid (panels), 256 threads = 4 waves; one launch per block of output rows
+// (row0), NT the row tiles per wave (rows.hpp).  Mt is M transposed, [n_rows][m]: the slice of a step is then read along the output
+// rows, as the slice of R is read along its columns -- 64 contiguous doubles per wave both -- and both are written to LDS as they
+// are read: As[k][i], Bs[k][j].  Lane l takes A[i = l & 15][k = l >> 4] = As[4 kk + k][16 t + i] and B[k = l >> 4][j = l & 15] =
+// Bs[4 kk + k][16 c + j]; result register r of lane l is D[(l >> 4) + 4 r][l & 15] (the f64 map), so that 16 lanes write 128
+// contiguous bytes of one row of Y.  Element (i, j) is ONE chain over k = 0 .. n_rows - 1 in groups of four, ascending, padded
+// with zeros to a multiple of 16.  Nothing in the loop is conditional: every load of a step comes from a clamped address and is
+// selected to zero where it lies past n_rows, m or n_cols (so that a NaN next door never enters a product); the next step's loads
+// (clamped too: the step after the last reads the last row again and drops it) are issued before the MFMAs and staged after them.
+// NT = 8 asks for two workgroups per compute unit: its 128 accumulator registers and the operands then share the 256 a lane may
+// have (no scratch; without the bound the compiler takes 318 and one workgroup).
+template <int NT>
+__global__ void __launch_bounds__(PROJ_THREADS, NT == 8 ? 2 : 1) k_rows_project(const double* __restrict__ R, const double* __restrict__ Mt,
+                                                               double* __restrict__ Y, i64 n_rows, i64 m, i64 n_cols, i64 row0) {
+    constexpr int BR = 32 * NT, LDA = BR + PROJ_PAD, LDB = PROJ_COLS + PROJ_PAD;
+    constexpr int NA = PROJ_KSTEP * BR / PROJ_THREADS, KA = PROJ_THREADS / BR;      // values of M per thread and step; k between them
+    constexpr int NB = PROJ_KSTEP * PROJ_COLS / PROJ_THREADS, KB = PROJ_THREADS / PROJ_COLS;
+    __shared__ double As[PROJ_KSTEP * LDA];
+    __shared__ double Bs[PROJ_KSTEP * LDB];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const i64 col0 = (i64)blockIdx.x * PROJ_COLS;
+    const int ra = (wave & 1) * (16 * NT), cb = (wave >> 1) * 32;
+    d4 acc[NT][2];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) { acc[t][0] = (d4){0.0, 0.0, 0.0, 0.0}; acc[t][1] = (d4){0.0, 0.0, 0.0, 0.0}; }
+
+    // staging: element e = tid + 256 q of the 16 x 64 slice of R is (k = e / 64, j = e % 64), of the 16 x BR slice of Mt (k = e / BR, i = e % BR)
+    const int bj = tid & (PROJ_COLS - 1), bk = tid / PROJ_COLS;
+    const int ai = tid & (BR - 1), ak = tid / BR;
+    const bool cin = col0 + bj < n_cols, iin = row0 + ai < m;
+    const double* rp = R + (cin ? col0 + bj : n_cols - 1);
+    const double* mp = Mt + (iin ? row0 + ai : m - 1);
+    const i64 klast = n_rows - 1;
+    double va[NA], vb[NB];
+    auto fetch = [&](i64 k0) {
+#pragma unroll
+        for (int q = 0; q < NB; ++q) { const i64 k = k0 + bk + KB * q; vb[q] = rp[(k < klast ? k : klast) * n_cols]; }
+#pragma unroll
+        for (int q = 0; q < NA; ++q) { const i64 k = k0 + ak + KA * q; va[q] = mp[(k < klast ? k : klast) * m]; }
+    };
+    auto stage = [&](i64 k0) {
+#pragma unroll
+        for (int q = 0; q < NB; ++q) Bs[(bk + KB * q) * LDB + bj] = (cin & (k0 + bk + KB * q < n_rows)) ? vb[q] : 0.0;
+#pragma unroll
+        for (int q = 0; q < NA; ++q) As[(ak + KA * q) * LDA + ai] = (iin & (k0 + ak + KA * q < n_rows)) ? va[q] : 0.0;
+    };
+    fetch(0);
+    const int fk = lane >> 4, fi = lane & 15;
+    for (i64 k0 = 0; k0 < n_rows; k0 += PROJ_KSTEP) {
+        __syncthreads();            // the previous step's operand reads are done
+        stage(k0);
+        __syncthreads();
+        fetch(k0 + PROJ_KSTEP);
+        __builtin_amdgcn_sched_barrier(0);          // (the loads are issued here, ahead of the MFMAs that hide their latency, not after them)
+#pragma unroll
+        for (int kk = 0; kk < PROJ_KSTEP / 4; ++kk) {
+            const int k = 4 * kk + fk;
+            double fa[NT], fb[2];           // all operands of this k first, then the MFMAs back to back
+            fb[0] = Bs[k * LDB + cb + fi];
+            fb[1] = Bs[k * LDB + cb + 16 + fi];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) fa[t] = As[k * LDA + ra + 16 * t + fi];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                acc[t][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[t], fb[0], acc[t][0], 0, 0, 0);
+                acc[t][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[t], fb[1], acc[t][1], 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const i64 col = col0 + cb + 16 * c + fi;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const i64 row = row0 + ra + 16 * t + fk + 4 * r;
+                if (row < m && col < n_cols) Y[row * n_cols + col] = acc[t][c][r];
+            }
+        }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- colsumsq
+// one thread per column: acc = acc + s[i] * (R[i][j] * R[i][j]) (S) or acc + R[i][j] * R[i][j], rows ascending, every operation
+// rounded once; the loads of COLSUM_U rows are issued before the chain that consumes them
+constexpr int COLSUM_U = 8;
+template <bool S>
+__global__ void __launch_bounds__(256) k_rows_colsumsq(const double* __restrict__ R, const double* __restrict__ s, double* __restrict__ out,
+                                                       i64 n_rows, i64 n_cols) {
+#pragma clang fp contract(off)
+    const i64 j = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n_cols) return;
+    const double* p = R + j;
+    double acc = 0.0;
+    i64 r = 0;
+    for (; r + COLSUM_U <= n_rows; r += COLSUM_U) {
+        double v[COLSUM_U];
+#pragma unroll
+        for (int k = 0; k < COLSUM_U; ++k) v[k] = p[(r + k) * n_cols];
+#pragma unroll
+        for (int k = 0; k < COLSUM_U; ++k) {
+            const double q = v[k] * v[k];
+            acc = S ? acc + s[r + k] * q : acc + q;
+        }
+    }
+    for (; r < n_rows; ++r) {
+        const double v = p[r * n_cols];
+        const double q = v * v;
+        acc = S ? acc + s[r] * q : acc + q;
+    }
+    out[j] = acc;
+}
+
 }  // namespace
 
 // ====================================================================================================== C ABI
@@ -452,6 +571,66 @@ int emg3d_rows_rmatvec(emg3d_rows_t* r, const double* y, const double* cm, doubl
     return to_host(r, out, dout, (size_t)r->n_cols * sizeof(double));
 }
 
+int emg3d_rows_project_plan(int64_t n_rows, int64_t m, int64_t n_cols, int64_t* out) {
+    if (n_rows < 1 || m < 1 || n_cols < 1 || !out) return -2;
+    const RowsProjectPlan p = rows_project_plan(n_rows, m, n_cols);
+    out[0] = PROJ_BLOCK; out[1] = PROJ_COLS; out[2] = PROJ_KSTEP; out[3] = p.passes; out[4] = p.wg; out[5] = p.lds_bytes;
+    out[6] = p.panels; out[7] = p.last_rows;
+    return 0;
+}
+
+int emg3d_rows_project(emg3d_rows_t* r, const double* M, int64_t m, emg3d_rows_t* dst) {
+    if (!r || !M || !dst || m < 1 || dst == r || dst->device != r->device || dst->n_rows != m || dst->n_cols != r->n_cols) return -2;
+    if (dst->R == r->R || m > (((int64_t)1 << 59) / r->n_rows)) return -2;
+    const RowsProjectPlan p = rows_project_plan(r->n_rows, m, r->n_cols);
+    if (p.panels > (i64)0x7fffffff) return -2;
+    ROWS_TRY(hipSetDevice(r->device));
+    const size_t nm = (size_t)m * (size_t)r->n_rows;
+    double* w[1];       // M transposed
+    if (!carve(r, {nm}, w)) return (int)hipErrorOutOfMemory;
+    double* mt = new (std::nothrow) double[nm];
+    if (!mt) return -3;
+    for (i64 i = 0; i < m; ++i)
+        for (i64 k = 0; k < r->n_rows; ++k) mt[k * m + i] = M[i * r->n_rows + k];
+    int st = to_device(r, w[0], mt, nm * sizeof(double));       // (synchronised: mt may go)
+    delete[] mt;
+    if (st) return st;
+    for (i64 b = 0; b < p.passes; ++b) {
+        const i64 row0 = b * PROJ_BLOCK;
+        const i64 cover = b + 1 < p.passes ? PROJ_BLOCK : p.last_rows;
+        const dim3 grid((unsigned)p.panels), block(PROJ_THREADS);
+        if (cover == 32)
+            hipLaunchKernelGGL(k_rows_project<1>, grid, block, 0, r->stream, (const double*)r->R, (const double*)w[0], dst->R, r->n_rows, m, r->n_cols, row0);
+        else if (cover == 64)
+            hipLaunchKernelGGL(k_rows_project<2>, grid, block, 0, r->stream, (const double*)r->R, (const double*)w[0], dst->R, r->n_rows, m, r->n_cols, row0);
+        else if (cover == 128)
+            hipLaunchKernelGGL(k_rows_project<4>, grid, block, 0, r->stream, (const double*)r->R, (const double*)w[0], dst->R, r->n_rows, m, r->n_cols, row0);
+        else
+            hipLaunchKernelGGL(k_rows_project<8>, grid, block, 0, r->stream, (const double*)r->R, (const double*)w[0], dst->R, r->n_rows, m, r->n_cols, row0);
+    }
+    st = launched();
+    if (st) { (void)hipStreamSynchronize(r->stream); return st; }
+    ROWS_TRY(hipStreamSynchronize(r->stream));
+    return 0;
+}
+
+int emg3d_rows_colsumsq(emg3d_rows_t* r, const double* s, double* out) {
+    if (!r || !out) return -2;
+    ROWS_TRY(hipSetDevice(r->device));
+    if ((r->n_cols + 255) / 256 > 0x7fffffff) return -2;
+    double* w[2];       // s, result
+    if (!carve(r, {s ? (size_t)r->n_rows : 1, (size_t)r->n_cols}, w)) return (int)hipErrorOutOfMemory;
+    double *ds = w[0], *dout = w[1];
+    int st = s ? to_device(r, ds, s, (size_t)r->n_rows * sizeof(double)) : 0;
+    if (st) return st;
+    const dim3 grid((unsigned)((r->n_cols + 255) / 256));
+    if (s) hipLaunchKernelGGL(k_rows_colsumsq<true>, grid, dim3(256), 0, r->stream, (const double*)r->R, (const double*)ds, dout, r->n_rows, r->n_cols);
+    else hipLaunchKernelGGL(k_rows_colsumsq<false>, grid, dim3(256), 0, r->stream, (const double*)r->R, (const double*)nullptr, dout, r->n_rows, r->n_cols);
+    st = launched();
+    if (st) { (void)hipStreamSynchronize(r->stream); return st; }
+    return to_host(r, out, dout, (size_t)r->n_cols * sizeof(double));
+}
+
 // ====================================================================================================== smoothing covariance
 int emg3d_rows_smooth_plan(int64_t nx, int64_t ny, int64_t nz, int axis, int64_t* out) {
     if (nx < 1 || ny < 1 || nz < 1 || axis < 0 || axis > 2 || !out) return -2;
@@ -499,10 +678,10 @@ int emg3d_smooth3d(int device, int64_t n_arrays, int64_t nx, int64_t ny, int64_t
     return 0;
 }
 
-int emg3d_rows_smooth(emg3d_rows_t* r, int64_t nx, int64_t ny, int64_t nz, int planes, const double* scale, const double* lo_x,
-                      const double* cp_x, const double* inv_x, const double* lo_y, const double* cp_y, const double* inv_y,
-                      const double* lo_z, const double* cp_z, const double* inv_z, int passes) {
-    const double* const h[3][3] = {{lo_x, cp_x, inv_x}, {lo_y, cp_y, inv_y}, {lo_z, cp_z, inv_z}};
+namespace {
+// L^T (scale_after == 0) or L (1) on every row of a store, in place: the body of emg3d_rows_smooth and emg3d_rows_smooth_l
+int rows_smooth(emg3d_rows* r, i64 nx, i64 ny, i64 nz, int planes, const double* scale, const double* const (&h)[3][3], int passes,
+                int scale_after) {
     if (!r || nx < 1 || ny < 1 || nz < 1 || planes < 1 || passes < 1 || !smooth_factors_ok(h)) return -2;
     // (no product before it is known to fit: nx ny nz <= n_cols, and planes divides n_cols)
     if (nx > r->n_cols || ny > r->n_cols / nx || nz > r->n_cols / (nx * ny)) return -2;
@@ -523,10 +702,25 @@ int emg3d_rows_smooth(emg3d_rows_t* r, int64_t nx, int64_t ny, int64_t nz, int p
             if (st) return st;
             f.p[ax][q] = w[1 + 3 * ax + q];
         }
-    const int st = smooth_run(r->stream, r->R, r->n_rows * planes, nx, ny, nz, planes, scale ? w[0] : nullptr, f, passes, 0);
+    const int st = smooth_run(r->stream, r->R, r->n_rows * planes, nx, ny, nz, planes, scale ? w[0] : nullptr, f, passes, scale_after);
     if (st) { (void)hipStreamSynchronize(r->stream); return st; }
     ROWS_TRY(hipStreamSynchronize(r->stream));
     return 0;
+}
+}  // namespace
+
+int emg3d_rows_smooth(emg3d_rows_t* r, int64_t nx, int64_t ny, int64_t nz, int planes, const double* scale, const double* lo_x,
+                      const double* cp_x, const double* inv_x, const double* lo_y, const double* cp_y, const double* inv_y,
+                      const double* lo_z, const double* cp_z, const double* inv_z, int passes) {
+    const double* const h[3][3] = {{lo_x, cp_x, inv_x}, {lo_y, cp_y, inv_y}, {lo_z, cp_z, inv_z}};
+    return rows_smooth(r, nx, ny, nz, planes, scale, h, passes, 0);
+}
+
+int emg3d_rows_smooth_l(emg3d_rows_t* r, int64_t nx, int64_t ny, int64_t nz, int planes, const double* scale, const double* lo_x,
+                        const double* cp_x, const double* inv_x, const double* lo_y, const double* cp_y, const double* inv_y,
+                        const double* lo_z, const double* cp_z, const double* inv_z, int passes) {
+    const double* const h[3][3] = {{lo_x, cp_x, inv_x}, {lo_y, cp_y, inv_y}, {lo_z, cp_z, inv_z}};
+    return rows_smooth(r, nx, ny, nz, planes, scale, h, passes, 1);
 }
 
 int emg3d_rows_clone(emg3d_rows_t* r, emg3d_rows_t** out) {

@@ -55,6 +55,39 @@ HD bool rows_job_tile(bool diag, int t, int& ta, int& tb) {
     return t < 36;
 }
 
+// ---- geometry of k_rows_project (Y = M R) ---------------------------------------------------------------------------------
+// The result is cut into PANELS of PROJ_COLS columns and into BLOCKS of PROJ_BLOCK output rows; a workgroup (4 waves) owns one
+// panel of one block and walks all n_rows of the source in steps of PROJ_KSTEP, its accumulators in registers: wave w holds the
+// row tiles (w & 1) NT .. + NT - 1 and the column tiles 2 (w >> 1), + 1 of its 32 NT x 64 piece, NT = 8 for a full block -- 16
+// accumulators of 4 f64 per lane, half the registers of a lane at two workgroups per compute unit.  A block with at most 128,
+// 64 or 32 live output rows -- the last or only one -- runs the instantiation NT = 4, 2 or 1, which stages and multiplies those
+// rows only.  Every block is one pass over the source: 256 output rows (the rows of a store against themselves: K^-1 R) read it
+// once.  The panels are a function of n_cols ALONE, and an element's accumulation chain of neither: see emg3d_rows_project.
+constexpr int PROJ_BLOCK = 256;         // output rows per block
+constexpr int PROJ_COLS = 64;           // columns per workgroup
+constexpr int PROJ_KSTEP = 16;          // source rows staged per step (4 MFMA k-steps of 4)
+constexpr int PROJ_THREADS = 256;
+constexpr int PROJ_PAD = 16;            // LDS row lengths are 64 + 16 (the slice of R) and 32 NT + 16 (the slice of M) doubles, all
+                                        // = 16 mod 32: the two k of a 32-lane half of an operand read (16 doubles each) fall on the
+                                        // two halves of the 32 eight-byte bank slots, and a staging write is 64 doubles in a row
+
+struct RowsProjectPlan {
+    i64 passes = 0, panels = 0, wg = 0, ksteps = 0, last_rows = 0, lds_bytes = 0;
+};
+// rows that the instantiation for a block of `live` output rows covers
+inline i64 rows_project_cover(i64 live) { return live <= 32 ? 32 : live <= 64 ? 64 : live <= 128 ? 128 : PROJ_BLOCK; }
+inline i64 rows_project_lds(i64 cover) { return (i64)PROJ_KSTEP * ((cover + PROJ_PAD) + (PROJ_COLS + PROJ_PAD)) * (i64)sizeof(double); }
+inline RowsProjectPlan rows_project_plan(i64 n_rows, i64 m, i64 n_cols) {
+    RowsProjectPlan p;
+    p.passes = (m + PROJ_BLOCK - 1) / PROJ_BLOCK;
+    p.panels = (n_cols + PROJ_COLS - 1) / PROJ_COLS;
+    p.wg = p.passes * p.panels;
+    p.ksteps = (n_rows + PROJ_KSTEP - 1) / PROJ_KSTEP;
+    p.last_rows = rows_project_cover(m - (p.passes - 1) * PROJ_BLOCK);
+    p.lds_bytes = rows_project_lds(p.passes > 1 ? PROJ_BLOCK : p.last_rows);
+    return p;
+}
+
 // Store row dest[p] <- plane part = 0 of pair p of `src` = [pairs][ndir][npart][ncells] doubles (device; the layout of k_sens_rows and
 // of its model-grid image), on `stream`; dest[p] < 0 skips the pair.  chain != 0: direction q times the store's chain factor q
 // (emg3d_rows_set_chain); sum3 != 0: one plane (p0 + p1) + p2 of the (scaled) directions.  -2: a store of another size than

@@ -581,6 +581,38 @@ class SmoothingCovariance:
             return None
         return np.concatenate([np.ones(int(np.prod(self.vnC))) if p is None else p for p in w])
 
+    def diagonal(self):
+        """``diag(C)``, the prior variances, as cells (an array of ``grid.vnC``; a 3-tuple of them where ``std`` is one, as
+        ``scale``).  ``C = diag(w) S^2p diag(w)`` with ``S = S_z (x) S_y (x) S_x``, so ``diag(C) = w^2 (d_z (x) d_y (x) d_x)``
+        with ``d_axis = diag(S_axis^2p)``: per axis the dense inverse of ``smoothing_matrix(h, ell)`` (a tridiagonal solve of the
+        identity in ``np.longdouble``, on the host -- an axis has a few hundred cells at most), ``S_axis^p`` by repeated products
+        and, ``S_axis`` being symmetric, the row sums of its squares: positive by construction.  A skipped axis (length 0, or
+        one cell) contributes ones."""
+        d = []
+        for h, ell, f in zip(self.grid.h, self.lengths, self.factors):
+            n = np.asarray(h).size
+            if f is None:
+                d.append(np.ones(n))
+                continue
+            dg, off = (a.astype(np.longdouble) for a in smoothing_matrix(h, ell))
+            X = np.eye(n, dtype=np.longdouble)          # T X = I by elimination without pivoting (T is diagonally dominant)
+            c = np.zeros(n, dtype=np.longdouble)
+            for i in range(n):
+                piv = dg[i] - off[i - 1] * c[i - 1] if i else dg[0]
+                X[i] = (X[i] - off[i - 1] * X[i - 1]) / piv if i else X[0] / piv
+                if i < n - 1:
+                    c[i] = off[i] / piv
+            for i in range(n - 2, -1, -1):
+                X[i] = X[i] - c[i] * X[i + 1]
+            Sp = X
+            for _ in range(self.passes - 1):
+                Sp = Sp @ X
+            d.append(np.asarray((Sp * Sp).sum(axis=1), dtype=np.float64))
+        kron = d[0][:, None, None] * d[1][None, :, None] * d[2][None, None, :]
+        planes = [kron.copy() if w is None else (w * w).reshape(self.vnC, order='F') * kron
+                  for w in (self._w if isinstance(self._w, tuple) else (self._w,))]
+        return tuple(planes) if isinstance(self._w, tuple) else planes[0]
+
     def _run(self, v, scale_after, host, device=None):
         three = isinstance(v, (tuple, list))
         parts = list(v) if three else [v]

@@ -1399,6 +1399,69 @@ class RowStore:
         r, w = self._stacked(residual, 'residual'), self._stacked(weights, 'weights')
         return self.rmatvec(np.linalg.solve(self.gram(cm) + damping * np.diag(1 / w), r), cm)
 
+    def project(self, M):
+        """``M R`` as a ``solver.DeviceRows`` of ``m`` rows that the caller owns (a context manager; ``close()``); ``M``: ``(m,
+        n_rows)`` real, ``R`` the stacked rows of this store, of any kind.  ``DeviceRows.project``: the product over the rows of
+        the store on the f64 matrix cores, deterministic, every element one accumulation chain of its own.  With ``M =
+        diag(lam_k^-1/2) U_k^T`` from ``np.linalg.eigh(gram())`` these are the principal rows of ``J`` (orthonormal: their
+        ``gram()`` is the identity), a truncated-SVD basis or a compressed store."""
+        return self.rows.project(M)
+
+    def _column_sums(self, weights, cm, damping, what):
+        """``q[j] = (X^T A^-1 X)[j, j]`` over the columns of a store, ``A = gram(cm) + damping W^-1``: with ``A = K K^T`` and ``T =
+        K^-1 R`` on the device, ``X = R`` and ``q = sum_k T[k, j]^2`` on a plain store, ``X = R L^T`` and ``q = sum_k (L t_k)[j]^2``
+        on a ``with_covariance`` store.  The temporary store ``T`` is closed before this returns."""
+        w = self._stacked(weights, 'weights')
+        A = self.gram(cm) + damping * np.diag(1 / w)
+        try:
+            K = np.linalg.cholesky(A)
+        except np.linalg.LinAlgError as exc:
+            raise ValueError(f"RowStore.{what}: J C_m J^T + damping W^-1 is not positive definite with `damping` = {damping!r} "
+                             "(dependent rows need a positive `damping`).") from exc
+        P = np.linalg.solve(K, np.eye(self.n_rows))
+        with self.project(P) as T:
+            if self.cov is not None:
+                planes = 3 if self.components else 1
+                T.smooth(self._vnM, planes, self.cov.factors, self.cov.passes, scale=self.cov.scale(planes), after=True)
+            return T.colsumsq()
+
+    def resolution_diagonal(self, weights, cm=None, damping=0.0):
+        """The diagonal of the model resolution matrix ``R_m = C_m J^T (J C_m J^T + damping W^-1)^-1 J`` as cells: how much of a
+        unit change of a cell the data-space ``step`` with the same ``weights`` (stacked, or a data array), ``cm`` (cells, the
+        diagonal of ``C_m``; default one) and ``damping`` gives back.  ``A = gram(cm) + damping * np.diag(1 / w)``, ``K =
+        np.linalg.cholesky(A)``, ``T = project(K^-1)``, result ``cm * T.colsumsq()``; the temporary store (a second block of the
+        store's size) is closed before the method returns.  Defined on a plain store only: under a smoothing covariance ``C = L
+        L^T`` the matrix is ``L X L^-1`` with ``X = B^T A^-1 B``, and ``diag(L X L^-1)`` is not a column sum of anything the store
+        holds -- a ``with_covariance`` store raises ``ValueError``; ``posterior_variance`` is defined there.  ``ValueError`` also
+        where ``A`` is not positive definite (it names ``damping``)."""
+        if self.cov is not None:
+            raise ValueError("RowStore.resolution_diagonal: this store holds B = J L of a SmoothingCovariance (with_covariance); its "
+                             "resolution matrix is L X L^-1, and diag(L X L^-1) is not a column sum of the rows -- use "
+                             "posterior_variance, which is defined on this store, or the store it was made from.")
+        c = None if cm is None else self._columns(cm, 'cm')
+        q = self._column_sums(weights, cm, damping, 'resolution_diagonal')
+        return self._cells(q if c is None else c * q)
+
+    def posterior_variance(self, weights, cm=None, damping=0.0):
+        """The diagonal of ``C - C J^T (J C J^T + damping W^-1)^-1 J C`` as cells: the posterior variance of every cell for the
+        prior covariance ``C`` and the data covariance ``damping W^-1`` (``weights``: stacked, or a data array).  On a plain
+        store ``C = diag(cm)`` (cells; default one) and the result is ``cm - cm^2 * q`` with ``q`` the column sums of
+        ``resolution_diagonal``.  On a ``with_covariance`` store ``C`` is its covariance (``cm`` is refused): row ``k`` of ``T =
+        K^-1 B`` becomes ``L t_k`` on the device (``DeviceRows.smooth(after=True)``) and the result is ``cov.diagonal() -
+        T.colsumsq()``.  Returned as computed, a difference of two positive numbers: no clipping -- where the data fix a cell
+        almost completely the value is small against the prior variance and carries its rounding error, and may be a few
+        ``cond(A) eps`` of the prior variance below zero.  The temporary store is closed before the method returns."""
+        self._refuse_cm(cm, 'posterior_variance')
+        q = self._column_sums(weights, cm, damping, 'posterior_variance')
+        if self.cov is not None:
+            prior = self.cov.diagonal()
+            prior = np.concatenate([p.ravel(order='F') for p in (prior if isinstance(prior, tuple) else (prior,) * (3 if self.components else 1))])
+            return self._cells(prior - q)
+        if cm is None:
+            return self._cells(1.0 - q)
+        c = self._columns(cm, 'cm')
+        return self._cells(c - c * c * q)
+
     def with_covariance(self, cov, inplace=False):
         """A ``RowStore`` whose rows are ``B = J L`` for the smoothing covariance ``cov = L L^T`` (``maps.SmoothingCovariance``):
         row ``d`` of ``B`` is ``L^T j_d``, every row smoothed in place on the device (``DeviceRows.smooth``, ``k_rows_smooth_*``: per

@@ -872,7 +872,7 @@ class DeviceMG:
 class DeviceRows:
     """A row store on the device (``emg3d_rows_*``): ``n_rows`` x ``n_cols`` doubles, row-major, in ONE block of HBM of its own, and
     the dense products a data-space method takes from rows that stay there -- ``gram`` (``R diag(cm) R^T`` on the f64 matrix cores),
-    ``matvec`` (``R v``) and ``rmatvec`` (``cm (.) R^T y``).  It belongs to no ``DeviceMG``: the handles of a survey park into one
+    ``matvec`` (``R v``) and ``rmatvec`` (``cm (.) R^T y``), and ``project`` (``M R`` into a second store) with ``colsumsq``.  It belongs to no ``DeviceMG``: the handles of a survey park into one
     store (``DeviceMG.sens_rows_park``); ``set_row`` fills it from the host.  Creating it checks its bytes against the device's free
     memory first: a store that cannot fit raises ``HipLibraryError`` with the bytes needed and free, and nothing was allocated.
     Every product is deterministic (no atomics; the column slabs follow from ``n_cols`` alone): see ``gram``.  A context manager;
@@ -1001,21 +1001,80 @@ class DeviceRows:
         new._h = h
         return new
 
-    def smooth(self, shape, planes, factors, passes, scale=None):
+    def smooth(self, shape, planes, factors, passes, scale=None, after=False):
         """Every row <- ``L^T`` row of ``maps.SmoothingCovariance``, in place (``emg3d_rows_smooth``, ``k_rows_smooth_*``): a row is
         ``planes`` arrays of ``shape`` = ``(nx, ny, nz)``, x fastest, each smoothed on its own; ``factors``: per axis ``(lo, cp,
         inv)`` or ``None`` (skipped); ``scale``: ``n_cols`` doubles multiplied in first, or ``None``.  Bit for bit the numpy loop of
-        ``SmoothingCovariance.sqrt_t(host=True)`` on every row."""
+        ``SmoothingCovariance.sqrt_t(host=True)`` on every row.  ``after=True``: ``L`` row instead (``emg3d_rows_smooth_l``) -- the
+        same sweeps, ``scale`` multiplied in last; bit for bit ``SmoothingCovariance.sqrt(host=True)``."""
         shape = tuple(int(n) for n in shape)
         if len(shape) != 3:
             raise ValueError(f"DeviceRows.smooth: `shape` must be (nx, ny, nz); provided: {shape}.")
         ptrs, keep = _lib.factor_ptrs(factors, shape)
         w = None if scale is None else self._vector(scale, self.n_cols, "smooth: `scale`")
-        st = self._lib.emg3d_rows_smooth(self._open(), *shape, int(planes), None if w is None else _lib.ptr(w), *ptrs, int(passes))
+        name = "emg3d_rows_smooth_l" if after else "emg3d_rows_smooth"
+        st = getattr(self._lib, name)(self._open(), *shape, int(planes), None if w is None else _lib.ptr(w), *ptrs, int(passes))
         if st == -2:
             raise ValueError(f"DeviceRows.smooth: {planes} planes of shape {shape} are not the {self.n_cols} columns of a row, or "
-                             f"`passes` = {passes!r} is less than 1 (emg3d_rows_smooth: -2).")
-        _lib.check(st, "emg3d_rows_smooth")
+                             f"`passes` = {passes!r} is less than 1 ({name}: -2).")
+        _lib.check(st, name)
+
+    def project(self, M, out=None):
+        """``Y = M R`` as a ``DeviceRows`` of ``m`` rows, ``M``: ``(m, n_rows)`` real -- the product that contracts over the ROWS of
+        the store (``emg3d_rows_project``, ``k_rows_project`` on ``v_mfma_f64_16x16x4_f64``); this store is not modified.  By
+        default the result is a new store (the memory check of a new store: one that cannot fit raises ``HipLibraryError`` and
+        nothing was allocated), which the caller owns; ``out=`` is a store of ``m`` rows and ``n_cols`` columns on the same device,
+        not this one, that is overwritten and returned.  The same bits at every call.  ``Y[i, j]`` depends on row ``i`` of ``M``
+        and column ``j`` of the store alone: one accumulation chain over the rows in groups of four, whatever ``m`` and ``n_cols``
+        are -- rows of ``M`` permuted give the rows of ``Y`` permuted bit for bit.  The order inside a group of four is the
+        hardware's: not bit for bit a numpy loop, but within ``gamma(n_rows + 2) |M| |R|`` of the exact product."""
+        M = np.asarray(M)
+        if np.iscomplexobj(M):
+            raise TypeError("DeviceRows.project: `M` must be real.")
+        if M.ndim != 2 or M.shape[0] < 1 or M.shape[1] != self.n_rows:
+            raise ValueError(f"DeviceRows.project: `M` must have shape (m, {self.n_rows}), m >= 1; provided: {M.shape}.")
+        M = np.ascontiguousarray(M, dtype=np.float64)
+        m = M.shape[0]
+        h = self._open()
+        if out is None:
+            dst = object.__new__(DeviceRows)
+            dst._lib, dst._h = self._lib, None
+            dst.n_rows, dst.n_cols, dst.device = m, self.n_cols, self.device
+            hd = ctypes.c_void_p()
+            st = self._lib.emg3d_rows_create(self.device, m, self.n_cols, ctypes.byref(hd))
+            if st == 2:
+                mi = _lib.mem_info(self.device)
+                raise _lib.HipLibraryError(
+                    f"DeviceRows.project: the result, a second block of {m} rows of {self.n_cols} columns, needs "
+                    f"{m * self.n_cols * 8} bytes of device memory, {mi['free'] + mi['pooled_on_device']} bytes are free; project "
+                    "onto fewer rows at a time.")
+            _lib.check(st, "emg3d_rows_create")
+            dst._h = hd
+        else:
+            dst = out
+            if not isinstance(dst, DeviceRows) or dst is self or dst.n_rows != m or dst.n_cols != self.n_cols or dst.device != self.device:
+                raise ValueError(f"DeviceRows.project: `out` must be another DeviceRows of {m} rows and {self.n_cols} columns on device "
+                                 f"{self.device}.")
+            dst._open()
+        try:
+            st = self._lib.emg3d_rows_project(h, _lib.ptr(M), m, dst._h)
+            if st == -2:
+                raise ValueError("DeviceRows.project: the stores do not fit each other (emg3d_rows_project: -2).")
+            _lib.check(st, "emg3d_rows_project")
+        except BaseException:
+            if out is None:
+                dst.close()
+            raise
+        return dst
+
+    def colsumsq(self, s=None):
+        """``sum_i s[i] R[i, j]^2``, ``n_cols`` doubles; ``s``: ``n_rows`` doubles, default all one.  One thread per column: ``acc =
+        acc + s[i] * (R[i, j] * R[i, j])`` over the rows ascending (no ``s``: ``acc + R[i, j] * R[i, j]``), every operation
+        rounded once -- bit for bit that loop in numpy."""
+        s = None if s is None else self._vector(s, self.n_rows, "colsumsq: `s`")
+        out = np.empty(self.n_cols)
+        _lib.check(self._lib.emg3d_rows_colsumsq(self._open(), None if s is None else _lib.ptr(s), _lib.ptr(out)), "emg3d_rows_colsumsq")
+        return out
 
 
 class FrequencyHandles:

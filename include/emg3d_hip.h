@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 117
+#define EMG3D_HIP_ABI_VERSION 118
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -375,6 +375,36 @@ int emg3d_rows_rmatvec(emg3d_rows_t* rows, const double* y, const double* cm, do
 int emg3d_rows_gram_plan(int64_t n_rows, int64_t n_cols, int64_t* out);
 int emg3d_rows_gram_job(int64_t n_rows, int64_t job, int64_t* out);
 
+/* ---- a small dense matrix times the store (solver.DeviceRows.project / colsumsq; optimize.RowStore.project,
+ *      resolution_diagonal, posterior_variance) -----------------------------------------------------------------------
+ * rows_gram contracts over the columns; rows_project contracts over the ROWS: Y[m x n_cols] = M[m x n_rows] R, every column on its
+ * own, no split over k, no partials, no second pass; the result is a store.
+ *   rows_project     : dst <- M src.  M: m x src.n_rows doubles of the host, row-major; dst: another store on the same device with
+ *                      n_rows == m and n_cols == src.n_cols -- anything else (dst == src included: there is no in-place mode)
+ *                      answers -2.  M goes through src's workspace; runs on src's stream, synchronised before it returns; src is
+ *                      not modified.  k_rows_project: v_mfma_f64_16x16x4_f64, one workgroup per panel of columns and block of
+ *                      output rows (rows_project_plan), which walks ALL rows of src in ascending steps with its accumulators in
+ *                      registers and writes every element once; each block of output rows is one pass over src.  The contract:
+ *                        deterministic -- the same bits at every call (no atomics);
+ *                        local -- Y[i][j] depends on row i of M and column j of src and on nothing else: it is one accumulation
+ *                          chain over k = 0 .. n_rows - 1 in groups of four (one MFMA each), padded with zeros, whatever m and
+ *                          n_cols are and wherever the row sits in M and the column in the store.  Rows of M permuted give the
+ *                          rows of Y permuted, a store of some of the columns gives those columns of Y, a NaN in one column of src
+ *                          stays in that column of Y;
+ *                        the order of the four products inside one instruction is the hardware's, so Y is NOT bit for bit a loop
+ *                          on the host; against exact arithmetic |Y - M R| <= gamma_(n_rows + 2) |M| |R| per element.
+ *   rows_colsumsq    : out (host, n_cols) <- sum_i s[i] R[i][j]^2; s: n_rows doubles (host) or NULL (= 1).  One thread per column:
+ *                      acc = acc + s[i] * (R[i][j] * R[i][j]) over the rows ascending (s NULL: acc + R[i][j] * R[i][j]), every
+ *                      operation rounded once -- bit for bit that loop on the host.
+ *   rows_project_plan: host arithmetic, needs no GPU; the launch calls the same function.  out[8] <- output rows per block, columns
+ *                      per workgroup, source rows (k) per step, passes over the source = ceil(m / rows per block), workgroups
+ *                      (passes * panels), LDS bytes of the largest workgroup, panels = ceil(n_cols / columns per workgroup), the
+ *                      rows the last block's kernel covers (32, 64, 128 or a whole block: a block with fewer live rows stages and
+ *                      multiplies fewer).  The panels are a function of n_cols alone.  -2: a size < 1, out NULL.           */
+int emg3d_rows_project_plan(int64_t n_rows, int64_t m, int64_t n_cols, int64_t* out);
+int emg3d_rows_project(emg3d_rows_t* src, const double* M, int64_t m, emg3d_rows_t* dst);
+int emg3d_rows_colsumsq(emg3d_rows_t* rows, const double* s, double* out);
+
 /* ---- smoothing model covariance (maps.SmoothingCovariance, optimize.RowStore.with_covariance) ----------------------
  * C = L L^T with L = diag(w) S^p, S = S_z S_y S_x, S_axis = T^-1 one implicit diffusion step along an axis: T the symmetric
  * tridiagonal matrix I + ell^2 H^-1/2 D^T diag(1/d) D H^-1/2 of the axis' cell widths h, centre distances d and correlation
@@ -396,6 +426,9 @@ int emg3d_rows_gram_job(int64_t n_rows, int64_t job, int64_t* out);
  *   rows_smooth     : L^T on every row of a store in place; a row is `planes` arrays of nx x ny x nz, each smoothed on its own;
  *                     scale: n_cols doubles (host) or NULL.  Factors and scale go through the store's workspace; runs on the
  *                     store's stream, synchronised before it returns.  -2: nx * ny * nz * planes != n_cols, passes < 1, ...
+ *   rows_smooth_l   : the same arguments and answers; L instead of L^T on every row: the same sweeps, then the scale multiplied in
+ *                     on the way out of the last active axis (k_rows_smooth_*'s w_post; the scale kernel where no axis is active).
+ *                     Bit for bit SmoothingCovariance.sqrt(row, host=True).
  *   rows_clone      : *out <- a second store of the same size on the same device with the same rows (device to device; the chain
  *                     factors are not copied).  The memory check and the answers of rows_create.                             */
 int emg3d_rows_smooth_plan(int64_t nx, int64_t ny, int64_t nz, int axis, int64_t* out);
@@ -405,6 +438,9 @@ int emg3d_smooth3d(int device, int64_t n_arrays, int64_t nx, int64_t ny, int64_t
 int emg3d_rows_smooth(emg3d_rows_t* rows, int64_t nx, int64_t ny, int64_t nz, int planes, const double* scale, const double* lo_x,
                       const double* cp_x, const double* inv_x, const double* lo_y, const double* cp_y, const double* inv_y,
                       const double* lo_z, const double* cp_z, const double* inv_z, int passes);
+int emg3d_rows_smooth_l(emg3d_rows_t* rows, int64_t nx, int64_t ny, int64_t nz, int planes, const double* scale, const double* lo_x,
+                        const double* cp_x, const double* inv_x, const double* lo_y, const double* cp_y, const double* inv_y,
+                        const double* lo_z, const double* cp_z, const double* inv_z, int passes);
 int emg3d_rows_clone(emg3d_rows_t* rows, emg3d_rows_t** out);
 
 /* ---- sensitivity products (optimize.Jacobian) --------------------------------------------------------------------
