@@ -22,7 +22,7 @@ c_double = ctypes.c_double
 c_dp = ctypes.POINTER(ctypes.c_double)
 
 # include/emg3d_hip.h: EMG3D_HIP_ABI_VERSION -- a library built from another header version is refused at load
-ABI_VERSION = 118
+ABI_VERSION = 119
 
 # name -> (restype, argtypes); mirrors include/emg3d_hip.h one to one.
 SIGNATURES = {
@@ -102,6 +102,7 @@ SIGNATURES = {
     "emg3d_rows_rmatvec": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "emg3d_rows_gram_plan": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64)]),
     "emg3d_rows_gram_job": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64)]),
+    "emg3d_rows_gram_batch": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64)]),
     "emg3d_rows_smooth_plan": (c_int, [c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_i64)]),
     "emg3d_smooth3d": (c_int, [c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
                                c_vp]),
@@ -320,11 +321,16 @@ def rows_gram_plan(n_rows, n_cols):
     """The geometry of the Gram launch of a row store of ``n_rows`` x ``n_cols`` (``emg3d_rows_gram_plan``): host arithmetic, runs
     without a GPU.  ``slab``, the columns of a K-slab, follows from ``n_cols`` alone; a workgroup owns one slab and one job, a pair
     of row blocks ``ba >= bb`` of ``block`` rows; ``jobs`` lists their rows ``(a0, a1, b0, b1)``, half open (``a0 == b0``: a diagonal
-    job, which computes the 16 x 16 tile pairs ``ta >= tb`` of its block only)."""
+    job, which computes the 16 x 16 tile pairs ``ta >= tb`` of its block only).  The jobs run in their order in ``launches`` launches
+    of ``jobs_per_launch`` (``emg3d_rows_gram_batch``, what ``emg3d_rows_gram`` itself runs): as many as fit ``scratch_bytes`` of
+    slab partials, ``job_bytes`` each, and at least one."""
     info = (c_i64 * 8)()
     check(load().emg3d_rows_gram_plan(int(n_rows), int(n_cols), info), "emg3d_rows_gram_plan")
+    batch = (c_i64 * 4)()
+    check(load().emg3d_rows_gram_batch(int(n_rows), int(n_cols), batch), "emg3d_rows_gram_batch")
     out = {"block": info[0], "kstep": info[1], "slab": info[2], "nslab": info[3], "nblocks": info[4], "njobs": info[5],
-           "grid": info[6], "lds_bytes": info[7], "tile": 16, "jobs": []}
+           "grid": info[6], "lds_bytes": info[7], "tile": 16, "jobs_per_launch": batch[0], "launches": batch[1],
+           "job_bytes": batch[2], "scratch_bytes": batch[3], "jobs": []}
     rect = (c_i64 * 4)()
     for job in range(info[5]):
         check(load().emg3d_rows_gram_job(int(n_rows), job, rect), "emg3d_rows_gram_job")

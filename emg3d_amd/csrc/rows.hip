@@ -37,7 +37,6 @@ struct emg3d_rows {
 namespace {
 
 constexpr int PARK_PAIRS_MAX = 64 * 64;         // pairs of one emg3d_mg_sens_rows call
-constexpr size_t GRAM_SCRATCH = (size_t)256 << 20;      // slab partials held at a time (jobs run in batches of this many bytes)
 
 size_t aligned(size_t nb) { return (nb + 255) & ~(size_t)255; }
 
@@ -419,6 +418,13 @@ int emg3d_rows_gram_job(int64_t n_rows, int64_t job, int64_t* out) {
     return 0;
 }
 
+int emg3d_rows_gram_batch(int64_t n_rows, int64_t n_cols, int64_t* out) {
+    if (n_rows < 1 || n_cols < 1 || !out) return -2;
+    const RowsGramBatch b = rows_gram_batch(n_rows, n_cols);
+    out[0] = b.batch; out[1] = b.launches; out[2] = b.per_job; out[3] = ROWS_GRAM_SCRATCH;
+    return 0;
+}
+
 int emg3d_rows_create(int device, int64_t n_rows, int64_t n_cols, emg3d_rows_t** out) {
     if (!out || n_rows < 1 || n_cols < 1) return -2;
     *out = nullptr;
@@ -516,8 +522,9 @@ int emg3d_rows_gram(emg3d_rows_t* r, const double* cm, double* G) {
     if (!r || !G) return -2;
     ROWS_TRY(hipSetDevice(r->device));
     const RowsGramPlan p = rows_gram_plan(r->n_rows, r->n_cols);
-    const size_t per_job = (size_t)64 * (size_t)p.nslab * 256 * sizeof(double);
-    const i64 batch = std::min<i64>(p.njobs, std::max<i64>(1, (i64)(GRAM_SCRATCH / per_job)));
+    const RowsGramBatch gb = rows_gram_batch(r->n_rows, r->n_cols);
+    const size_t per_job = (size_t)gb.per_job;
+    const i64 batch = gb.batch;
     double* w[3];       // slab partials, G, cm
     if (!carve(r, {per_job / sizeof(double) * (size_t)batch, (size_t)r->n_rows * (size_t)r->n_rows, cm ? (size_t)r->n_cols : 1}, w))
         return (int)hipErrorOutOfMemory;

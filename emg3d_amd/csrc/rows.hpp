@@ -1,6 +1,6 @@
 // Device-resident row store (csrc/rows.hip): rows of J parked in HBM, and the dense products a data-space method takes from them.
 // This header is what the two translation units share: the geometry of the Gram launch (host arithmetic, also exported as
-// emg3d_rows_gram_plan / emg3d_rows_gram_job) and the one entry the multigrid handle calls (emg3d_mg_sens_rows_park).
+// emg3d_rows_gram_plan / emg3d_rows_gram_job / emg3d_rows_gram_batch) and the one entry the multigrid handle calls (emg3d_mg_sens_rows_park).
 #pragma once
 #include "common.hpp"
 
@@ -39,6 +39,23 @@ inline RowsGramPlan rows_gram_plan(i64 n_rows, i64 n_cols) {
     p.njobs = p.nblk * (p.nblk + 1) / 2;
     p.lds_bytes = 2 * (i64)ROWS_KSTEP * ROWS_LD * (i64)sizeof(double);
     return p;
+}
+// The jobs run in LAUNCHES of as many as fit ROWS_GRAM_SCRATCH bytes of slab partials (at least one): launch l holds the jobs
+// l * batch .. min(njobs, (l + 1) * batch) - 1, one k_rows_gram and one k_rows_gram_reduce each.  A job's partials are its 64 tile
+// pairs of 256 doubles per slab, so that `batch` depends on n_rows through njobs only.  What emg3d_rows_gram runs and what
+// emg3d_rows_gram_batch reports.
+constexpr i64 ROWS_GRAM_SCRATCH = (i64)256 << 20;       // bytes of slab partials held at a time
+struct RowsGramBatch {
+    i64 per_job = 0, batch = 0, launches = 0;           // bytes of one job's partials, jobs per launch, launches
+};
+inline RowsGramBatch rows_gram_batch(i64 n_rows, i64 n_cols) {
+    const RowsGramPlan p = rows_gram_plan(n_rows, n_cols);
+    RowsGramBatch b;
+    b.per_job = 64 * p.nslab * 256 * (i64)sizeof(double);
+    const i64 fit = ROWS_GRAM_SCRATCH / b.per_job > 1 ? ROWS_GRAM_SCRATCH / b.per_job : 1;
+    b.batch = p.njobs < fit ? p.njobs : fit;
+    b.launches = (p.njobs + b.batch - 1) / b.batch;
+    return b;
 }
 // job -> its pair of row blocks
 HD void rows_job_blocks(i64 job, i64& ba, i64& bb) {

@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 118
+#define EMG3D_HIP_ABI_VERSION 119
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -359,7 +359,11 @@ int emg3d_mg_sens_rows(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0
  *   rows_gram_plan: host arithmetic, needs no GPU.  out[8] <- rows per block, columns staged per step, columns per K-slab, slabs,
  *                   row blocks, jobs (pairs of row blocks ba >= bb), workgroups (jobs * slabs), LDS bytes per workgroup.  The slab
  *                   length is a function of n_cols alone.  rows_gram_job: out[4] <- the rows [a0, a1) x [b0, b1) of job `job`; a
- *                   diagonal job (a0 == b0) computes the 16 x 16 tile pairs ta >= tb of its block only.  -2: bad arguments.   */
+ *                   diagonal job (a0 == b0) computes the 16 x 16 tile pairs ta >= tb of its block only.  -2: bad arguments.
+ *   rows_gram_batch: host arithmetic, needs no GPU; what rows_gram itself runs.  out[4] <- jobs per launch, launches, bytes of one
+ *                   job's slab partials (64 tile pairs x slabs x 256 doubles), bytes of partials held at a time.  The jobs run in
+ *                   their order, as many per launch as fit the partials' bytes and at least one; jobs per launch depends on
+ *                   n_rows through the number of jobs only.  -2: bad arguments.   */
 typedef struct emg3d_rows emg3d_rows_t;
 int emg3d_rows_create(int device, int64_t n_rows, int64_t n_cols, emg3d_rows_t** out);
 void emg3d_rows_destroy(emg3d_rows_t* rows);
@@ -374,6 +378,7 @@ int emg3d_rows_matvec(emg3d_rows_t* rows, const double* v, double* out);
 int emg3d_rows_rmatvec(emg3d_rows_t* rows, const double* y, const double* cm, double* out);
 int emg3d_rows_gram_plan(int64_t n_rows, int64_t n_cols, int64_t* out);
 int emg3d_rows_gram_job(int64_t n_rows, int64_t job, int64_t* out);
+int emg3d_rows_gram_batch(int64_t n_rows, int64_t n_cols, int64_t* out);
 
 /* ---- a small dense matrix times the store (solver.DeviceRows.project / colsumsq; optimize.RowStore.project,
  *      resolution_diagonal, posterior_variance) -----------------------------------------------------------------------

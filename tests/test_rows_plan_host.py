@@ -4,7 +4,8 @@ no GPU needed.
 * the K-slabs tile [0, n_cols) exactly once, and the jobs' tile pairs cover every (a, b) with a >= b exactly once;
 * the slab partition at a given n_cols is the same for every n_rows (the summation order of G must not depend on it), also past the
   size at which the slab length starts to grow;
-* a workgroup's LDS stays within the 160 KB of a gfx950 compute unit."""
+* a workgroup's LDS stays within the 160 KB of a gfx950 compute unit;
+* the launches the jobs run in (emg3d_rows_gram_batch) hold every job, fit the scratch size, and follow from n_cols and njobs."""
 import numpy as np
 import pytest
 
@@ -67,10 +68,37 @@ def test_jobs_cover_the_lower_triangle_once(lib, n_rows):
     assert np.all(seen[a // tile, b // tile] == 1)
 
 
+def test_jobs_per_launch(lib):
+    """emg3d_rows_gram_batch, the arithmetic emg3d_rows_gram runs its launches by: the launches hold all jobs, each holds at least one,
+    the partials of one launch fit the scratch size (unless a single job does not), and jobs_per_launch depends on n_rows through
+    njobs only: it is min(njobs, a function of n_cols)."""
+    S, cols = _n_cols(lib)
+    for n_cols in cols + [15 * S + 9, 256 * S, 256 * S + 1, 128 ** 3, 6_291_456, 2 ** 31 + 5]:
+        fit = None
+        for n_rows in N_ROWS + [1024, 1925, 5000]:
+            plan = lib.rows_gram_plan(n_rows, n_cols)
+            jpl, launches = plan["jobs_per_launch"], plan["launches"]
+            assert jpl >= 1 and launches == -(-plan["njobs"] // jpl)
+            assert plan["job_bytes"] == 64 * plan["nslab"] * 256 * 8 and plan["scratch_bytes"] > 0
+            assert jpl * plan["job_bytes"] <= plan["scratch_bytes"] or jpl == 1
+            # the most that fit, and that number is the same for every n_rows
+            cap = max(1, plan["scratch_bytes"] // plan["job_bytes"])
+            assert jpl == min(plan["njobs"], cap)
+            fit = fit or cap
+            assert cap == fit
+    # today's constants: 256 slabs make a job 32 MiB, 8 of them a launch; 16 slabs 2 MiB and 128
+    assert lib.rows_gram_plan(385, 128 ** 3)["jobs_per_launch"] == 8 and lib.rows_gram_plan(385, 128 ** 3)["launches"] == 2
+    assert lib.rows_gram_plan(384, 128 ** 3)["launches"] == 1
+    p = lib.rows_gram_plan(1925, 15 * S + 9)
+    assert (p["njobs"], p["jobs_per_launch"], p["launches"]) == (136, 128, 2)
+
+
 def test_bad_arguments(lib):
     import ctypes
     out = (ctypes.c_int64 * 8)()
     h = lib.load()
+    assert h.emg3d_rows_gram_batch(0, 5, out) == -2 and h.emg3d_rows_gram_batch(5, 0, out) == -2
+    assert h.emg3d_rows_gram_batch(5, 5, None) == -2 and h.emg3d_rows_gram_batch(5, 5, out) == 0
     assert h.emg3d_rows_gram_plan(0, 5, out) == -2 and h.emg3d_rows_gram_plan(5, 0, out) == -2
     assert h.emg3d_rows_gram_plan(5, 5, None) == -2
     assert h.emg3d_rows_gram_job(5, 1, out) == -2 and h.emg3d_rows_gram_job(5, -1, out) == -2 and h.emg3d_rows_gram_job(5, 0, out) == 0
