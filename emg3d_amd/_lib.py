@@ -22,7 +22,7 @@ c_double = ctypes.c_double
 c_dp = ctypes.POINTER(ctypes.c_double)
 
 # include/emg3d_hip.h: EMG3D_HIP_ABI_VERSION -- a library built from another header version is refused at load
-ABI_VERSION = 119
+ABI_VERSION = 120
 
 # name -> (restype, argtypes); mirrors include/emg3d_hip.h one to one.
 SIGNATURES = {
@@ -97,6 +97,7 @@ SIGNATURES = {
     "emg3d_rows_get": (c_int, [c_vp, c_i64, c_vp]),
     "emg3d_rows_set_chain": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "emg3d_mg_sens_rows_park": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int]),
+    "emg3d_mg_sens_rows_fill": (c_int, [c_vp, c_int, c_double, c_double, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int]),
     "emg3d_rows_gram": (c_int, [c_vp, c_vp, c_vp]),
     "emg3d_rows_matvec": (c_int, [c_vp, c_vp, c_vp]),
     "emg3d_rows_rmatvec": (c_int, [c_vp, c_vp, c_vp, c_vp]),

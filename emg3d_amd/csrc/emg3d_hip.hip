@@ -1310,6 +1310,19 @@ int emg3d_mg_sens_rows_park(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double
     });
 }
 
+int emg3d_mg_sens_rows_fill(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use_fwd, const int32_t* use_adj,
+                            int split, int on_model_grid, emg3d_rows_t* rows, const int32_t* dest_re, const int32_t* dest_im, int chain,
+                            int sum3) {
+    if (!mg || !use_fwd || !use_adj || !rows || !dest_re) return -2;
+    DISPATCH(mg, {
+        HIP_TRY(hipSetDevice(m->device));
+        const int st = m->sens_rows_fill(fwd_bvec, smu0_re, smu0_im, use_fwd, use_adj, split != 0, on_model_grid != 0, rows, dest_re,
+                                         dest_im, chain != 0, sum3 != 0);
+        const int fin = finish(m);          // (always: the store's later operations are ordered after this handle's stream)
+        return st ? st : fin;
+    });
+}
+
 int emg3d_mg_jvec_source_b(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const double* vx, const double* vy,
                            const double* vz, const int32_t* use) {
     if (!mg || !use) return -2;

@@ -6,8 +6,10 @@
 //   k_gradient_acc = the same for all systems of a batch in one launch, added into a per-cell accumulator in system order;
 //   k_sens_acc    = the survey sensitivity diagonal: W |row|^2 for all pairs of an adjoint and a forward system, into the same
 //                   accumulators (no counterpart in the reference);
-//   k_sens_rows   = the rows themselves, one per pair, into a planar row buffer (MG::sens_rows).
-// The last four are the per-cell kernels: one thread per cell behind the same cell_frame, SPLIT = the sum of the three directions
+//   k_sens_rows   = the rows themselves, one per pair, into a planar row buffer (MG::sens_rows);
+//   k_sens_rows_fill = the same rows, real and imaginary parts written straight into their rows of a row store (MG::sens_rows_fill;
+//                   instantiated in csrc/rows.hip, the store's translation unit).
+// The last five are the per-cell kernels: one thread per cell behind the same cell_frame, SPLIT = the sum of the three directions
 // or the directions apart, launched through MG_CELL_LAUNCH (mg.hpp), the accumulators those of MG::cell_acc.
 // Gather form: one thread per CELL sums the contributions of its 12 edges in the order in which the reference's
 // loops (iz, iy, ix ascending, four statements per edge) add them -- deterministic and equal to the reference's
@@ -299,6 +301,98 @@ __global__ void __launch_bounds__(256) k_sens_rows(i64 n0, i64 n1, i64 n2, Field
                 row_store(dst, plane, (cc[0] + cc[1]) + cc[2]);
             }
             dst += NDIR * NPART * plane;
+        }
+    }
+}
+
+// ---- the rows of J, both parts, straight into a row store (optimize.SurveyJacobian.park_rows(solves=1)) ----------------------
+// Where the fused kernel writes: the block of a row store (csrc/rows.hip: n_cols doubles per row, columns [dir][cell]), the two
+// destination tables of the call (device, one entry per pair in LOOP ORDER; a negative entry: that part of the pair is not kept;
+// dest_im == nullptr: no imaginary part is kept) and what k_rows_park applies on the way: the store's chain factors (c[0] ==
+// nullptr: none) and the sum of the three directions.
+struct RowsFillArgs {
+    double* R;
+    i64 n_cols;
+    const int32_t* dest_re;
+    const int32_t* dest_im;
+    const double* c[3];
+    int sum3;
+};
+
+__device__ __forceinline__ double sens_part(double c, int) { return c; }
+__device__ __forceinline__ double sens_part(c128 c, int part) { return part ? c.im : c.re; }
+
+// One real part of one pair at one cell into its store row: the operations of k_rows_park in their order -- chain factor times
+// value per direction, then (p0 + p1) + p2 --, without contraction, so that a filled row is the parked row bit for bit.  The pragma
+// covers this body alone: the products of sens_cell keep the flags they have inside k_sens_rows, and none of them can fuse with an
+// operation here, which carries no licence to contract.
+template <bool SPLIT>
+__device__ __forceinline__ void row_fill_part(double* out, i64 plane, double v0, double v1, double v2, bool chain, double ch0, double ch1,
+                                              double ch2, int sum3) {
+#pragma clang fp contract(off)
+    if (chain) {
+        v0 = ch0 * v0;
+        if (SPLIT) { v1 = ch1 * v1; v2 = ch2 * v2; }
+    }
+    if (!SPLIT) { out[0] = v0; return; }
+    if (sum3) out[0] = (v0 + v1) + v2;
+    else { out[0] = v0; out[plane] = v1; out[2 * plane] = v2; }
+}
+
+// k_sens_rows with its stores replaced by the work of k_rows_park: the real part of pair p goes to store row dest_re[p], the
+// imaginary part (c128) to row dest_im[p], columns [dir][cell] with cells x fastest -- consecutive lanes write consecutive doubles
+// of one row.  The same frame, offsets, loads, sens_cell, mask clipping and LOOP ORDER as k_sens_rows (p = the rank of the pair),
+// the twelve lambda values of a receiver in registers across the inner loop; a pair with both entries negative is skipped before its
+// forward load (wave-uniform: the tables are indexed by the loop counter and come through the scalar cache).  !SPLIT: one column
+// block, ((c_x + c_y) + c_z) formed as k_sens_rows forms it, times chain factor 0 if given; SPLIT: three blocks, or with sum3 the
+// one block (p0 + p1) + p2 of the (scaled) directions.  One thread per cell, every element of a named row written exactly once, rows
+// named in neither table not touched, no atomics, all offsets 64-bit.  Per launch the reads of k_sens_rows (a skipped pair's forward
+// field apart) plus three chain factors per cell, and 8 bytes written per element kept: no row buffer, no second pass.  The host
+// checks the tables (csrc/rows.hip: rows_fill_check): every entry < n_rows, no row named twice.
+template <class T, bool SPLIT>
+__global__ void __launch_bounds__(256) k_sens_rows_fill(i64 n0, i64 n1, i64 n2, FieldLayout fl, const T* fwd, const T* adj, i64 nE, int nsys,
+                                                        unsigned long long use_fwd, unsigned long long use_adj, double sr, double si,
+                                                        const double* h0, const double* h1, const double* h2, RowsFillArgs f) {
+    const i64 nC[3] = {n0, n1, n2};
+    i64 idx, j[3];
+    double vol;
+    if (!cell_frame(n0, n1, n2, h0, h1, h2, idx, j, vol)) return;
+    if (nsys < 64) {                    // (never a shift by 64: nsys = 64 with bit 63 set is a valid batch)
+        use_fwd &= (1ull << nsys) - 1ull;
+        use_adj &= (1ull << nsys) - 1ull;
+    }
+    constexpr bool CPLX = sizeof(T) > sizeof(double);
+    const i64 plane = n0 * n1 * n2;
+    CellEdges<i64> o;
+    cell_edge_offsets(j, fl, o);
+    const bool chain = f.c[0] != nullptr;
+    double ch0 = 0.0, ch1 = 0.0, ch2 = 0.0;
+    if (chain) {
+        ch0 = f.c[0][idx];
+        if (SPLIT) { ch1 = f.c[1][idx]; ch2 = f.c[2][idx]; }
+    }
+    double* const out = f.R + idx;      // this cell in the first column block of row 0
+    i64 p = 0;
+    for (unsigned long long ra = use_adj; ra; ra &= ra - 1ull) {          // (wave-uniform: the masks are kernel arguments)
+        const int br = __builtin_ctzll(ra);
+        CellEdges<T> lam;
+        cell_edge_load(adj + (i64)br * nE, o, lam);
+        for (unsigned long long rf = use_fwd; rf; rf &= rf - 1ull, ++p) {
+            const i64 dre = f.dest_re[p];
+            const i64 dim = (CPLX && f.dest_im) ? (i64)f.dest_im[p] : (i64)-1;
+            if (dre < 0 && dim < 0) continue;
+            const int bs = __builtin_ctzll(rf);
+            CellEdges<T> ev;
+            cell_edge_load(fwd + (i64)bs * nE, o, ev);
+            T cc[3];
+            sens_cell<T>(j, nC, vol, lam, ev, sr, si, cc);
+            if (!SPLIT) cc[0] = (cc[0] + cc[1]) + cc[2];
+            if (dre >= 0)
+                row_fill_part<SPLIT>(out + dre * f.n_cols, plane, sens_part(cc[0], 0), sens_part(cc[1], 0), sens_part(cc[2], 0), chain,
+                                     ch0, ch1, ch2, f.sum3);
+            if (CPLX && dim >= 0)
+                row_fill_part<SPLIT>(out + dim * f.n_cols, plane, sens_part(cc[0], 1), sens_part(cc[1], 1), sens_part(cc[2], 1), chain,
+                                     ch0, ch1, ch2, f.sum3);
         }
     }
 }

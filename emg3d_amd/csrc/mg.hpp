@@ -1145,6 +1145,39 @@ struct MG : emg3d_mg {
         if (rc) return rc;
         return rows_park(rows, stream, device, d.planes, d.pairs, (int)d.ndir, (int)d.npart, d.ncells, dest, chain, sum3);
     }
+    // Both parts of the same rows into a row store (emg3d_mg_sens_rows_fill): the real part of pair p into store row dest_re[p], the
+    // imaginary part into dest_im[p] (nullptr: none; a real handle has none).  On the computational grid ONE launch of
+    // k_sens_rows_fill (csrc/rows.hpp: rows_fill) from the fields into the store: no row buffer is allocated or grown, `bytes` stays.
+    // On the model grid the planes of both parts lie in row_buf[1] after sens_rows_device, and rows_park runs once per part -- part
+    // 1 is the same planes offset by ncells.  The checks of sens_rows_park, and those of rows_fill_check before anything is launched.
+    int sens_rows_fill(int fwd_bvec, double sr, double si, const int32_t* use_fwd, const int32_t* use_adj, int split, int on_model,
+                       emg3d_rows* rows, const int32_t* dest_re, const int32_t* dest_im, int chain, int sum3) {
+        const T* fwd = saved_bvec(fwd_bvec);
+        const unsigned long long uf = use_bits(use_fwd), ua = use_bits(use_adj);
+        if (!fwd || !uf || !ua) return -2;
+        if (on_model && (!mgl.set || !mgl.factors)) return -7;
+        Level<T>& L = *lv0;
+        const int ndir = split ? 3 : 1, npart = (int)(sizeof(T) / sizeof(double));
+        {
+            const int rc = rows_fill_check(rows, device, bit_count(uf) * bit_count(ua), ndir, npart, on_model ? mgl.nM : L.nCells, dest_re,
+                                           dest_im, chain, sum3);
+            if (rc) return rc;
+        }
+        if (on_model) {
+            SensRowsOnDevice d;
+            int rc = sens_rows_device(fwd_bvec, sr, si, use_fwd, use_adj, split, on_model, d);
+            if (rc) return rc;
+            rc = rows_park(rows, stream, device, d.planes, d.pairs, (int)d.ndir, (int)d.npart, d.ncells, dest_re, chain, sum3);
+            if (rc || !dest_im) return rc;
+            return rows_park(rows, stream, device, d.planes + d.ncells, d.pairs, (int)d.ndir, (int)d.npart, d.ncells, dest_im, chain, sum3);
+        }
+        e_to_ref(L);
+        if (broken) return err ? err : (int)hipErrorOutOfMemory;
+        RowsFillFields<T> f;
+        for (int a = 0; a < 3; ++a) { f.nC[a] = L.nC[a]; f.h[a] = (const double*)L.h[a]; }
+        f.fl = L.fl; f.fwd = fwd; f.adj = (const T*)L.e; f.nE = L.nE; f.nsys = nsys; f.use_fwd = uf; f.use_adj = ua; f.sr = sr; f.si = si;
+        return rows_fill<T>(rows, stream, device, f, split, dest_re, dest_im, chain, sum3);
+    }
     // what both share: the checks, the launches, and where the planes [p][dir][part][ncells] lie afterwards
     struct SensRowsOnDevice { const double* planes = nullptr; i64 pairs = 0, ndir = 0, npart = 0, ncells = 0; };
     int sens_rows_device(int fwd_bvec, double sr, double si, const int32_t* use_fwd, const int32_t* use_adj, int split, int on_model,

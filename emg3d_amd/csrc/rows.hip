@@ -2,6 +2,8 @@
 // emg3d_rows_* of include/emg3d_hip.h.  gfx950 only.
 //
 //   k_rows_park           one chunk of rows from a handle's row buffer into their store rows (emg3d_mg_sens_rows_park)
+//   k_sens_rows_fill      (csrc/gradient.hpp) both parts of a chunk's rows from the fields into their store rows, no row buffer
+//                         (emg3d_mg_sens_rows_fill)
 //   k_rows_gram           G = R diag(cm) R^T: per (K-slab, pair of row blocks) one workgroup on v_mfma_f64_16x16x4_f64, slab partials
 //   k_rows_gram_reduce    the slab partials summed in ascending slab order, the lower triangle mirrored
 //   k_rows_matvec(_reduce) R v: per (row, slab) a fixed tree, the slab partials summed in ascending order
@@ -16,7 +18,9 @@
 
 #include <algorithm>
 #include <new>
+#include <vector>
 
+#include "gradient.hpp"
 #include "rows.hpp"
 #include "rows_cov.hpp"
 
@@ -26,7 +30,7 @@ struct emg3d_rows {
     double* R = nullptr;            // the block
     size_t nbytes = 0;              // its size (256-byte aligned)
     hipStream_t stream = nullptr;   // the store's own products run here; every entry point ends with a synchronise
-    int32_t* d_dest = nullptr;      // park: destination rows of a chunk's pairs
+    int32_t* d_dest = nullptr;      // park: destination rows of a chunk's pairs; fill: two tables (real parts, then imaginary parts)
     double* chain[3] = {nullptr, nullptr, nullptr};     // chain factors of emg3d_rows_set_chain (one block)
     i64 chain_n = 0;
     size_t chain_bytes = 0;
@@ -439,7 +443,7 @@ int emg3d_rows_create(int device, int64_t n_rows, int64_t n_cols, emg3d_rows_t**
     if (!r) return -3;
     r->device = device; r->n_rows = n_rows; r->n_cols = n_cols;
     r->R = (double*)quiet_alloc(nb);
-    r->d_dest = r->R ? (int32_t*)quiet_alloc(aligned(PARK_PAIRS_MAX * sizeof(int32_t))) : nullptr;
+    r->d_dest = r->R ? (int32_t*)quiet_alloc(aligned(2 * PARK_PAIRS_MAX * sizeof(int32_t))) : nullptr;
     if (!r->d_dest || hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) {
         (void)hipGetLastError();
         emg3d_rows_destroy(r);
@@ -517,6 +521,55 @@ int rows_park(emg3d_rows* r, hipStream_t stream, int device, const double* src, 
                        ndir, npart, ncells, (const int32_t*)r->d_dest, c[0], c[1], c[2], sum3);
     return launched();
 }
+
+int rows_fill_check(const emg3d_rows* r, int device, i64 pairs, int ndir, int npart, i64 ncells, const int32_t* dest_re,
+                    const int32_t* dest_im, int chain, int sum3) {
+    if (!r || !dest_re || pairs < 1 || pairs > PARK_PAIRS_MAX || (ndir != 1 && ndir != 3) || npart < 1 || npart > 2 || ncells < 1)
+        return -2;
+    if (dest_im && npart != 2) return -2;
+    if (device != r->device || (sum3 && ndir != 3) || r->n_cols != (sum3 ? 1 : ndir) * ncells) return -2;
+    if (chain && r->chain_n != ncells) return -2;
+    std::vector<int32_t> named;
+    named.reserve((size_t)(2 * pairs));
+    for (const int32_t* dest : {dest_re, dest_im})
+        for (i64 p = 0; dest && p < pairs; ++p) {
+            if (dest[p] >= r->n_rows) return -2;
+            if (dest[p] >= 0) named.push_back(dest[p]);
+        }
+    if (named.empty()) return -2;
+    std::sort(named.begin(), named.end());
+    return std::adjacent_find(named.begin(), named.end()) == named.end() ? 0 : -2;
+}
+
+template <class T>
+int rows_fill(emg3d_rows* r, hipStream_t stream, int device, const RowsFillFields<T>& f, int split, const int32_t* dest_re,
+              const int32_t* dest_im, int chain, int sum3) {
+    if (!f.fwd || !f.adj || f.nsys < 1 || f.nsys > 64) return -2;
+    const unsigned long long clip = f.nsys < 64 ? (1ull << f.nsys) - 1ull : ~0ull;
+    const i64 pairs = (i64)__builtin_popcountll(f.use_fwd & clip) * (i64)__builtin_popcountll(f.use_adj & clip);
+    const i64 ncells = f.nC[0] * f.nC[1] * f.nC[2];
+    const int st = rows_fill_check(r, device, pairs, split ? 3 : 1, (int)(sizeof(T) / sizeof(double)), ncells, dest_re, dest_im, chain, sum3);
+    if (st) return st;
+    ROWS_TRY(hipStreamSynchronize(r->stream));          // (the store's own products are done with the rows about to change)
+    ROWS_TRY(hipMemcpyAsync(r->d_dest, dest_re, (size_t)pairs * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    if (dest_im)
+        ROWS_TRY(hipMemcpyAsync(r->d_dest + PARK_PAIRS_MAX, dest_im, (size_t)pairs * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    RowsFillArgs a;
+    a.R = r->R; a.n_cols = r->n_cols;
+    a.dest_re = r->d_dest; a.dest_im = dest_im ? r->d_dest + PARK_PAIRS_MAX : nullptr;
+    for (int q = 0; q < 3; ++q) a.c[q] = chain ? r->chain[q] : nullptr;
+    a.sum3 = sum3;
+    const dim3 grid((unsigned)((ncells + 255) / 256));
+    if (split)
+        hipLaunchKernelGGL((k_sens_rows_fill<T, true>), grid, dim3(256), 0, stream, f.nC[0], f.nC[1], f.nC[2], f.fl, f.fwd, f.adj, f.nE,
+                           f.nsys, f.use_fwd, f.use_adj, f.sr, f.si, f.h[0], f.h[1], f.h[2], a);
+    else
+        hipLaunchKernelGGL((k_sens_rows_fill<T, false>), grid, dim3(256), 0, stream, f.nC[0], f.nC[1], f.nC[2], f.fl, f.fwd, f.adj, f.nE,
+                           f.nsys, f.use_fwd, f.use_adj, f.sr, f.si, f.h[0], f.h[1], f.h[2], a);
+    return launched();
+}
+template int rows_fill<double>(emg3d_rows*, hipStream_t, int, const RowsFillFields<double>&, int, const int32_t*, const int32_t*, int, int);
+template int rows_fill<c128>(emg3d_rows*, hipStream_t, int, const RowsFillFields<c128>&, int, const int32_t*, const int32_t*, int, int);
 
 int emg3d_rows_gram(emg3d_rows_t* r, const double* cm, double* G) {
     if (!r || !G) return -2;

@@ -1,6 +1,7 @@
 // Device-resident row store (csrc/rows.hip): rows of J parked in HBM, and the dense products a data-space method takes from them.
 // This header is what the two translation units share: the geometry of the Gram launch (host arithmetic, also exported as
-// emg3d_rows_gram_plan / emg3d_rows_gram_job / emg3d_rows_gram_batch) and the one entry the multigrid handle calls (emg3d_mg_sens_rows_park).
+// emg3d_rows_gram_plan / emg3d_rows_gram_job / emg3d_rows_gram_batch) and the entries the multigrid handle calls (emg3d_mg_sens_rows_park:
+// rows_park; emg3d_mg_sens_rows_fill: rows_fill_check, rows_fill).
 #pragma once
 #include "common.hpp"
 
@@ -112,3 +113,30 @@ inline RowsProjectPlan rows_project_plan(i64 n_rows, i64 m, i64 n_cols) {
 // entries, another device.  The caller synchronises `stream` before it returns (dest is read asynchronously).
 int rows_park(emg3d_rows* rows, hipStream_t stream, int device, const double* src, i64 pairs, int ndir, int npart, i64 ncells,
               const int32_t* dest, int chain, int sum3);
+
+// ---- both parts of the rows of a chunk, filled by the sensitivity kernel itself (emg3d_mg_sens_rows_fill) ---------------------------
+// What a fill of `pairs` pairs of ndir directions, npart parts and ncells cells may ask of the store: the checks of rows_park for
+// both tables, and -2 too for a dest_im with one part (a real handle), a row named twice (in one table or across the two) and a
+// call in which every entry is negative.  0: the fill may run.  No device call.
+int rows_fill_check(const emg3d_rows* rows, int device, i64 pairs, int ndir, int npart, i64 ncells, const int32_t* dest_re,
+                    const int32_t* dest_im, int chain, int sum3);
+// The cells and fields of a level-0 launch of the per-cell kernels (csrc/gradient.hpp), as MG_CELL_LAUNCH passes them.
+template <class T>
+struct RowsFillFields {
+    i64 nC[3];
+    FieldLayout fl;
+    const T* fwd;           // batched vector of forward fields, [system][nE]
+    const T* adj;           // level-0 field array, [system][nE]
+    i64 nE;
+    int nsys;
+    unsigned long long use_fwd, use_adj;
+    double sr, si;
+    const double* h[3];
+};
+// ONE launch of k_sens_rows_fill<T, split> on `stream` into the store: the real part of pair p into row dest_re[p], the imaginary
+// part into row dest_im[p] (nullptr: none), with the store's chain factors and sum3 as rows_park applies them.  The kernel lives in
+// this unit so that the store's pointer, row length, chain factors and destination tables never leave it.  Runs rows_fill_check
+// first (its -2, nothing launched); the caller synchronises `stream` before it returns.  T = double, c128.
+template <class T>
+int rows_fill(emg3d_rows* rows, hipStream_t stream, int device, const RowsFillFields<T>& f, int split, const int32_t* dest_re,
+              const int32_t* dest_im, int chain, int sum3);

@@ -1106,6 +1106,14 @@ class SurveyJacobian(_JacobianBase):
         return out if components else out[0]
 
     # ---- the rows of J ------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _solves(solves):
+        """``solves`` of ``sensitivity_rows`` / ``park_rows`` after its check (no device call): 1 or 2."""
+        if isinstance(solves, (bool, np.bool_)) or not isinstance(solves, (int, np.integer)) or solves not in (1, 2):
+            raise ValueError(f"`solves` must be 2 (the imaginary parts from a second solve, for i e_d: the definition bit for bit) or 1 "
+                             f"(both parts from the solve for e_d); provided: {solves!r}.")
+        return int(solves)
+
     def _row_selection(self, i_freq, receivers):
         """``(i_freq, receiver indices)`` of ``sensitivity_rows`` after their checks (no device call)."""
         if isinstance(i_freq, (bool, np.bool_)) or not isinstance(i_freq, (int, np.integer)) or not 0 <= i_freq < self.n_freq:
@@ -1118,7 +1126,7 @@ class SurveyJacobian(_JacobianBase):
                              f"{receivers!r}.")
         return int(i_freq), [int(r) for r in recs]
 
-    def sensitivity_rows(self, i_freq, receivers=None, components=False, mapped=False):
+    def sensitivity_rows(self, i_freq, receivers=None, components=False, mapped=False, solves=2):
         """The rows of ``J`` themselves, for all sources and the receivers ``receivers`` (a list of indices into ``rec``, any order,
         kept; default: all) at ``freqs[i_freq]``: an array ``rows[i_src, k] + cells``, ``k`` the position in ``receivers``, cells of
         shape ``grid.vnC`` (F-ordered) -- ``model_grid.vnC`` with ``model_grid`` --, ``complex128`` for a frequency and ``float64``
@@ -1146,12 +1154,20 @@ class SurveyJacobian(_JacobianBase):
         is the solver's info dict of receiver ``receivers[k]``'s solve for ``e_d``, ``rows_info_imag[k]`` of that for ``i e_d``
         (``None`` in the Laplace domain).
 
+        ``solves=1`` takes both parts from the solve for ``e_d``: one ``_adjoint_sources`` and one solve per chunk, and the real
+        AND the imaginary planes of its ``DeviceMG.sens_rows``, each through the chain and sum operations as a real array of its
+        own -- half the solves of a frequency.  The real parts are those of ``solves=2`` bit for bit; the imaginary parts equal
+        ``jtvec(i e_d)`` to the rounding of the solves only (far below the ``tol`` to which either solve is accurate).
+        ``rows_info_imag`` is ``None``.  A Laplace-domain entry is one solve and one part in both forms.  Any other ``solves``
+        raises ``ValueError`` before any device call.
+
         The result is allocated before the first solve (``n_src * len(receivers)`` rows: 16 bytes per cell and row); the device
         keeps one chunk's rows
         (``min(batch, n_src)^2`` of them at most) in a buffer of the handle's own that grows to the largest call so far.  If that
         buffer does not fit, ``HipLibraryError`` names the bytes needed and free: use a smaller ``batch``, or fewer ``receivers`` per
         call.  Works after ``set_model``; deterministic."""
         mapped = self._mapped_or_refuse(mapped)
+        solves = self._solves(solves)
         j, recs = self._row_selection(i_freq, receivers)
         handles = self._require_open()
         ns, nb, nk = self.n_src, self._nb, len(recs)
@@ -1163,32 +1179,37 @@ class SurveyJacobian(_JacobianBase):
         chain = self._chain_factors() if mapped and not on_model else None
         dev, smu0 = handles.target(spec), spec.smu0
         real = dev.dtype.kind != 'c'
+        both = not real and solves == 1         # both parts from the solve for e_d
         infos = [[None] * nk for _ in range(1 if real else 2)]
         for k0 in range(0, nk, nb):
             n = min(nb, nk - k0)
-            for part, unit in enumerate((1.0,) if real else (1.0, 1j)):        # e_d, then i e_d: jtvec's solves, jtvec's products
+            for part, unit in enumerate((1.0,) if real or both else (1.0, 1j)):     # e_d, then i e_d: jtvec's solves, jtvec's products
                 w = np.zeros((n, self.n_rec), dtype=dev.dtype)
                 for b in range(n):
                     w[b, recs[k0 + b]] = unit
                 self._adjoint_sources(dev, smu0, np.conj(w), n)
                 infos[part][k0:k0 + n] = self._solve(dev, self.freqs[j], n)[:n]
-                dest = out if real else [(o.real, o.imag)[part] for o in out]       # views into the rows
+                # (plane of the product, views into the rows it fills)
+                dests = [('real', out if real else [(o.real, o.imag)[part] for o in out])]
+                if both:
+                    dests.append(('imag', [o.imag for o in out]))
                 for c, (i0, nsrc) in enumerate(self._chunks):
                     got = dev.sens_rows(self._slot[j] + c, smu0, _first(nsrc, nb), _first(n, nb), components=three,
                                         model_grid=on_model)
                     for b in range(n):
                         for s in range(nsrc):
-                            parts = [g.real for g in got[b * nsrc + s]]         # pair p = b * nsrc + s: adjoint systems outer
-                            if chain is not None:
-                                parts = [d * g for d, g in zip(chain, parts)]
-                            if three and not components:
-                                parts = [(parts[0] + parts[1]) + parts[2]]
-                            for q, g in enumerate(parts):
-                                dest[q][i0 + s, k0 + b] = g
-        self.rows_info, self.rows_info_imag = infos[0], None if real else infos[1]
+                            for plane, dest in dests:
+                                parts = [getattr(g, plane) for g in got[b * nsrc + s]]      # pair p = b * nsrc + s: adjoint systems outer
+                                if chain is not None:
+                                    parts = [d * g for d, g in zip(chain, parts)]
+                                if three and not components:
+                                    parts = [(parts[0] + parts[1]) + parts[2]]
+                                for q, g in enumerate(parts):
+                                    dest[q][i0 + s, k0 + b] = g
+        self.rows_info, self.rows_info_imag = infos[0], None if real or both else infos[1]
         return tuple(out) if components else out[0]
 
-    def park_rows(self, data=None, components=False, mapped=False):
+    def park_rows(self, data=None, components=False, mapped=False, solves=2):
         """The rows of ``sensitivity_rows`` for the selected data of the WHOLE survey, parked in HBM instead of returned: a
         ``RowStore`` whose ``gram``, ``matvec``, ``rmatvec`` and ``step`` run on the device, so that no row crosses PCIe.
 
@@ -1206,12 +1227,20 @@ class SurveyJacobian(_JacobianBase):
         uploaded once per call.  ``store.info[j][r]`` holds the solver info dicts ``(of e_d, of i e_d)`` of receiver ``r`` at
         ``freqs[j]`` (the second ``None`` in the Laplace domain), ``None`` for a receiver that was not solved for.
 
+        ``solves=1`` is the one-solve form of ``sensitivity_rows(solves=1)``: at a frequency one solve per chunk of receivers, for
+        ``e_d``, then ONE ``DeviceMG.sens_rows_fill`` per chunk of sources, which writes the real part of every pair into its
+        ``part`` 0 row and the imaginary part into its ``part`` 1 row -- on the computational grid straight from the fields, with
+        no row buffer on the handle and no parking launch.  ``store.row(i)`` equals the matching part of
+        ``sensitivity_rows(..., solves=1)`` bit for bit, the ``part`` 0 rows those of ``solves=2`` too; ``store.info[j][r]`` is
+        ``(info, None)``, and ``store.solves`` records the form.  Laplace-domain entries are parked as with ``solves=2``.
+
         The store is ONE block of ``n_rows * n_cols * 8`` bytes (``n_cols``: the cells of a row, times three with ``components``),
         checked against the free device memory before anything is solved: ``HipLibraryError`` names the bytes needed and free.
         It is a SNAPSHOT of the model at the time of the call: ``set_model`` leaves it valid as such -- it keeps returning the rows
         of the model it was parked for -- and a new ``park_rows`` gives those of the new model.  ``store.close()`` frees it; the
         ``SurveyJacobian`` closes its stores when it closes."""
         mapped = self._mapped_or_refuse(mapped)
+        solves = self._solves(solves)
         handles = self._require_open()
         shape = (self.n_src, self.n_freq, self.n_rec)
         if data is None:
@@ -1235,7 +1264,7 @@ class SurveyJacobian(_JacobianBase):
         row_of = {tuple(int(x) for x in key): i for i, key in enumerate(index)}
         ncell = int(np.prod(self._vnM))
         store = RowStore(solver.DeviceRows(index.shape[0], (3 if components else 1) * ncell, device=self.device), index, shape,
-                         self._vnM, bool(components), real)
+                         self._vnM, bool(components), real, solves=solves)
         try:
             chain = mapped and not on_model
             if chain:
@@ -1246,9 +1275,10 @@ class SurveyJacobian(_JacobianBase):
                     continue
                 dev, smu0 = handles.target(spec), spec.smu0
                 got = {r: [None, None] for r in recs}
+                both = not real[j] and solves == 1      # both parts from the solve for e_d, filled by the sensitivity kernel
                 for k0 in range(0, len(recs), nb):
                     n = min(nb, len(recs) - k0)
-                    for part, unit in enumerate((1.0,) if real[j] else (1.0, 1j)):     # e_d, then i e_d: sensitivity_rows' solves
+                    for part, unit in enumerate((1.0,) if real[j] or both else (1.0, 1j)):     # e_d, then i e_d: sensitivity_rows' solves
                         w = np.zeros((n, self.n_rec), dtype=dev.dtype)
                         for b in range(n):
                             w[b, recs[k0 + b]] = unit
@@ -1257,6 +1287,14 @@ class SurveyJacobian(_JacobianBase):
                         for b in range(n):
                             got[recs[k0 + b]][part] = infos[b]
                         for c, (i0, nsrc) in enumerate(self._chunks):
+                            if both:
+                                dre, dim = (np.array([row_of.get((j, i0 + s, recs[k0 + b], q), -1) for b in range(n)
+                                                      for s in range(nsrc)], dtype=np.int32) for q in (0, 1))
+                                if (dre >= 0).any():        # (a datum has both parts or neither)
+                                    dev.sens_rows_fill(self._slot[j] + c, smu0, _first(nsrc, nb), _first(n, nb), store.rows, dre, dim,
+                                                       components=three, model_grid=on_model, chain=chain,
+                                                       sum3=three and not components)
+                                continue
                             dest = np.array([row_of.get((j, i0 + s, recs[k0 + b], part), -1) for b in range(n) for s in range(nsrc)],
                                             dtype=np.int32)         # pair p = b * nsrc + s: adjoint systems outer
                             if (dest >= 0).any():
@@ -1278,11 +1316,13 @@ class RowStore:
     the imaginary part of the datum's row; ``n_rows`` of them.  ``info[j][r]``: the solver info dicts of receiver ``r`` at
     frequency ``j`` (``None``: not solved for).  A "stacked" vector has one real entry per row (``stack`` / ``data`` convert from
     and to complex data arrays); cells are arrays of the shape ``sensitivity_rows`` gives its rows, a tuple of three for a store
-    parked with ``components=True``.  A snapshot of the model it was parked for; a context manager, ``close()`` frees the device
-    block."""
+    parked with ``components=True``.  ``solves`` is the form it was parked in (``park_rows(solves=)``: 2 = the imaginary parts from
+    solves of their own, 1 = both parts from the solve for ``e_d``); ``with_covariance`` and ``project`` carry it over.  A snapshot
+    of the model it was parked for; a context manager, ``close()`` frees the device block."""
 
-    def __init__(self, rows, index, shape, vnM, components, real):
+    def __init__(self, rows, index, shape, vnM, components, real, solves=2):
         self.rows, self.index, self.components = rows, index, components
+        self.solves = solves        # park_rows(solves=): 2 = the imaginary parts from solves of their own, 1 = from the solve for e_d
         self.n_rows = index.shape[0]
         self._shape, self._vnM, self._real = shape, tuple(vnM), list(real)
         self._ncell = int(np.prod(vnM))
@@ -1404,8 +1444,10 @@ class RowStore:
         n_rows)`` real, ``R`` the stacked rows of this store, of any kind.  ``DeviceRows.project``: the product over the rows of
         the store on the f64 matrix cores, deterministic, every element one accumulation chain of its own.  With ``M =
         diag(lam_k^-1/2) U_k^T`` from ``np.linalg.eigh(gram())`` these are the principal rows of ``J`` (orthonormal: their
-        ``gram()`` is the identity), a truncated-SVD basis or a compressed store."""
-        return self.rows.project(M)
+        ``gram()`` is the identity), a truncated-SVD basis or a compressed store.  The result carries this store's ``solves``."""
+        out = self.rows.project(M)
+        out.solves = self.solves        # (the form of the rows it combines)
+        return out
 
     def _column_sums(self, weights, cm, damping, what):
         """``q[j] = (X^T A^-1 X)[j, j]`` over the columns of a store, ``A = gram(cm) + damping W^-1``: with ``A = K K^T`` and ``T =
@@ -1486,7 +1528,7 @@ class RowStore:
         if inplace:
             new = self
         else:
-            new = RowStore(self.rows.clone(), self.index, self._shape, self._vnM, self.components, self._real)
+            new = RowStore(self.rows.clone(), self.index, self._shape, self._vnM, self.components, self._real, solves=self.solves)
             new.info = self.info
         try:
             new.rows.smooth(self._vnM, planes, cov.factors, cov.passes, scale=scale)

@@ -425,6 +425,47 @@ class DeviceMG:
                          f"sens_rows_park: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy), or the "
                          "store does not fit the rows (its device, its columns, a destination row, its chain factors).")
 
+    def sens_rows_fill(self, fwd_bvec, smu0, use_fwd, use_adj, rows, dest_re, dest_im=None, components=False, model_grid=False,
+                       chain=False, sum3=False):
+        """BOTH parts of the rows of ``sens_rows`` into the ``DeviceRows`` ``rows`` (``emg3d_mg_sens_rows_fill``): the real part of
+        pair ``p`` into row ``dest_re[p]``, the imaginary part into row ``dest_im[p]`` (``None``: real parts only; a ``float64``
+        handle has no other).  A negative entry skips that part; a pair with both negative is not computed; no row may be named
+        twice and at least one must be named.  The arguments, the checks and the messages of ``sens_rows_park``, and its
+        operations in its order: part 0 is what ``sens_rows_park`` parks and part 1 the imaginary plane of the same ``sens_rows``,
+        bit for bit.  On the computational grid this is ONE launch from the fields into the store -- the handle's row buffer is
+        neither allocated nor grown, ``device_bytes`` stays --; with ``model_grid=True`` the launches of ``sens_rows``, then one
+        parking launch per part.  The handle's stream is synchronised before the call returns."""
+        a = complex(smu0)
+        uf, ua = self._use_flags(use_fwd, "sens_rows_fill"), self._use_flags(use_adj, "sens_rows_fill")
+        pairs = int(self._lib.emg3d_mg_sens_rows_count(_lib.ptr(uf), _lib.ptr(ua), self.nsys))
+        d = np.ascontiguousarray(dest_re, dtype=np.int32)
+        di = None if dest_im is None else np.ascontiguousarray(dest_im, dtype=np.int32)
+        if pairs < 1 or d.shape != (pairs,) or (di is not None and di.shape != (pairs,)):
+            raise ValueError(f"sens_rows_fill: `use_fwd` and `use_adj` name {pairs} pairs (at least one is needed), `dest_re` has shape "
+                             f"{d.shape}" + ("" if di is None else f", `dest_im` {di.shape}") + ".")
+        if model_grid and self._vnM is None:
+            raise RuntimeError("sens_rows_fill: the handle has no model grid or no regrid factors (set_model_grid, set_regrid_factors).")
+        if model_grid and not components and self._factors_shared is False:
+            raise ValueError("sens_rows_fill: model_grid=True without components needs regrid factors that the three directions share.")
+        before = self.device_bytes
+        st = self._lib.emg3d_mg_sens_rows_fill(self._h, int(fwd_bvec), a.real, a.imag, _lib.ptr(uf), _lib.ptr(ua), int(bool(components)),
+                                               int(bool(model_grid)), rows._h, _lib.ptr(d), None if di is None else _lib.ptr(di),
+                                               int(bool(chain)), int(bool(sum3)))
+        if st == 2:         # hipErrorOutOfMemory: a row buffer of the model-grid path did not fit; the handle is still usable
+            n = int(np.prod(self._vnM if model_grid else self._vnC))
+            need = pairs * (3 if components else 1) * (2 if self.dtype == np.complex128 else 1) * 8 * (self.nC + (n if model_grid else 0))
+            mi = _lib.mem_info(self.device)
+            raise _lib.HipLibraryError(
+                f"sens_rows_fill: the rows of {pairs} pairs need up to {need} bytes of device memory beside the {before} the handle "
+                f"holds, {mi['free'] + mi['pooled_on_device']} bytes are free; ask for fewer pairs per call (SurveyJacobian: a smaller "
+                "`batch`).")
+        if st == -7:
+            self._require_model_grid(st, "emg3d_mg_sens_rows_fill")
+        self._check_bvec(st, "emg3d_mg_sens_rows_fill",
+                         f"sens_rows_fill: batched vector {fwd_bvec} does not exist (the forward fields must be a saved copy), or the "
+                         "store does not fit the rows (its device, its columns, a destination row, its chain factors), or the "
+                         "destinations are refused (a row named twice, none named, imaginary parts of a real handle).")
+
     # ---- the accumulators on a model grid (optimize.SurveyJacobian(model_grid=)) ----
     def set_model_grid(self, model_grid):
         """Link the handle to the grid the model lives on (``emg3d_mg_set_model_grid``): the segment tables of volume averaging

@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 119
+#define EMG3D_HIP_ABI_VERSION 120
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -345,6 +345,16 @@ int emg3d_mg_sens_rows(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0
  *                   row equals the row that returns, bit for bit.  The handle's stream is synchronised before the call returns, so
  *                   every later operation of the store sees the rows.  -2 also: a store on another device or of another n_cols, a
  *                   dest[p] >= n_rows, chain without factors of `cells` entries.
+ *   sens_rows_fill: BOTH parts of the same rows into the store: the real part of pair p into row dest_re[p], the imaginary part into
+ *                   row dest_im[p] (dest_im NULL: real parts only), a negative entry skips that part, and a pair with both
+ *                   negative is not computed.  Columns, chain and sum3 as for sens_rows_park, the same operations in the same
+ *                   order: part 0 is what sens_rows_park parks bit for bit, part 1 the imaginary plane of emg3d_mg_sens_rows
+ *                   through the same real operations.  on_model_grid = 0: ONE launch (k_sens_rows_fill) from the fields into the
+ *                   store -- the handle's row buffer is neither allocated nor grown.  on_model_grid != 0: the launches of
+ *                   emg3d_mg_sens_rows, then k_rows_park once per part.  The handle's stream is synchronised before the call
+ *                   returns.  The codes of sens_rows_park (-2, -7; 2 on the model-grid path); -2 also: dest_re NULL, a dest_im
+ *                   on a float64 handle, a row named twice (in one table or across the two), every entry negative.  A
+ *                   refused call writes nothing.
  *   rows_gram     : G (host, n_rows^2 doubles) <- R diag(cm) R^T, G[a][b] = sum_j R[a][j] cm[j] R[b][j]; cm: n_cols doubles (host) or
  *                   NULL (= 1).  k_rows_gram: v_mfma_f64_16x16x4_f64, one workgroup per K-slab of columns and pair of row blocks
  *                   (rows_gram_plan), cm multiplied into one operand while staging; the slab partials are summed in ascending slab
@@ -373,6 +383,9 @@ int emg3d_rows_get(emg3d_rows_t* rows, int64_t i, double* host);
 int emg3d_rows_set_chain(emg3d_rows_t* rows, int64_t n, const double* cx, const double* cy, const double* cz);
 int emg3d_mg_sens_rows_park(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use_fwd, const int32_t* use_adj,
                             int split, int on_model_grid, emg3d_rows_t* rows, const int32_t* dest, int chain, int sum3);
+int emg3d_mg_sens_rows_fill(emg3d_mg_t* mg, int fwd_bvec, double smu0_re, double smu0_im, const int32_t* use_fwd, const int32_t* use_adj,
+                            int split, int on_model_grid, emg3d_rows_t* rows, const int32_t* dest_re, const int32_t* dest_im, int chain,
+                            int sum3);
 int emg3d_rows_gram(emg3d_rows_t* rows, const double* cm, double* G);
 int emg3d_rows_matvec(emg3d_rows_t* rows, const double* v, double* out);
 int emg3d_rows_rmatvec(emg3d_rows_t* rows, const double* y, const double* cm, double* out);
