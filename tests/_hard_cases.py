@@ -1,4 +1,6 @@
-"""Inputs and references of the accuracy tests (tests/test_oracle_truth.py on the CPU, tests/test_gpu_accuracy.py on the GPU).
+"""Inputs and references of the accuracy tests (tests/test_oracle_truth.py on the CPU, tests/test_gpu_accuracy.py on the GPU) and of
+the family-level tests of the batched contract (tests/test_gpu_batch_families.py: every sweep kernel family, the point smoother and
+the residual kernels with three systems in one handle, one of them frozen, and with 64).
 
 Two generators, each a function of (shape, direction, dtype, seed) that returns float64 / complex128 arrays:
 
@@ -13,7 +15,12 @@ Two generators, each a function of (shape, direction, dtype, seed) that returns 
 
 The truth is the oracle's smoother (oracle/emg3d_oracle.cpp) compiled with every scalar a long double (x87 extended precision, 64-bit
 significand) on the same float64 inputs, converted exactly; `reference` is the float64 oracle.  Both are computed once per case and
-shared read-only."""
+shared read-only.
+
+Batched runs: system 0 of a case is the case's own `e0`, `s`; `system_fields` draws the start field and source of system b >= 1 on the
+same grid and model from a generator of its own (the draws above are not touched), `references_b` holds their oracle sweep and truth.
+`wide_runs` gives every case its line length on 36 x 36 lines (324 per colour), so that a batched launch has more line blocks than
+XCDs and the line map of `EMG_SWEEP_WG` (csrc/common.hpp) places blocks inside an XCD's share."""
 import numpy as np
 
 MU_0 = 4e-7 * np.pi
@@ -86,6 +93,7 @@ def hard(shape, direction, dtype, seed=0):
 
 
 GENERATORS = {"benign": benign, "hard": hard}
+GENERATOR_IDS = {"benign": 1, "hard": 2}
 # Seeds of the hard cases the tests use: 0, but for the draws below, where seed 0 puts one pathological line into the case (a line
 # through air cells only is close to singular: the float64 reference itself is then 1e-7 off, and the max-norm speaks of that line
 # alone).  The smallest seed whose float64 reference is 2e-13 ... 5e-10 from the truth; test_oracle_truth.py holds every case to
@@ -155,6 +163,72 @@ def err(x, truth):
     truth = np.asarray(truth)
     d = np.abs(np.asarray(x).astype(truth.dtype) - truth).max()
     return float(d / np.abs(truth).max())
+
+
+# ---- further systems of a case (batched handles) ------------------------------------------------------------------------------------
+SYSTEM_SALT = 3                     # (`_rng` uses 1 for the benign and 2 for the hard generator)
+SOURCE_SCALE = {"benign": 1.0, "hard": 1e-6}
+# (systems 1 and 2 of every hard run: float64 reference 3.6e-13 ... 5.2e-11 from the truth, the sweep changes the field by >= 0.9;
+# tests/test_oracle_truth.py holds them to the window of system 0, [1e-13, 1e-9])
+
+
+def system_fields(kind, shape, direction, dtype, b):
+    """(e0_b, s_b) of system `b` of a batched run on the case `problem(kind, shape, direction, dtype)`: system 0 is the case's own
+    pair; b >= 1 is drawn with `_fields` (same boundary treatment, same source scale) from a generator salted by SYSTEM_SALT and b."""
+    if b == 0:
+        p = problem(kind, shape, direction, dtype)
+        return p['e0'], p['s']
+    char = np.dtype(dtype).char
+    key = ("fields", kind, tuple(shape), direction, char, b)
+    if key not in _cache:
+        rng = np.random.default_rng([SYSTEM_SALT, b, GENERATOR_IDS[kind], *shape, direction, np.dtype(dtype).itemsize,
+                                     seed_of(kind, shape, direction, dtype), 0])
+        e0, s = _fields(rng, tuple(shape), np.dtype(dtype) == np.complex128, SOURCE_SCALE[kind])
+        _cache[key] = (_frozen(e0), _frozen(s))
+    return _cache[key]
+
+
+def system_problem(kind, shape, direction, dtype, b):
+    """The case's problem with the fields of system `b` (grid and model shared, not copied)."""
+    e0, s = system_fields(kind, shape, direction, dtype, b)
+    return dict(problem(kind, shape, direction, dtype), e0=e0, s=s)
+
+
+def references_b(oracle, kind, shape, direction, dtype, b, order, nu=2):
+    """(float64 reference, extended truth) of `nu` sweeps of system `b`: computed once per case and system."""
+    if b == 0:
+        return references(oracle, kind, shape, direction, dtype, order=order, nu=nu)[1:]
+    key = ("sweep_b", kind, tuple(shape), direction, np.dtype(dtype).char, b, order, nu)
+    if key not in _cache:
+        p = system_problem(kind, shape, direction, dtype, b)
+        _cache[key] = (_frozen(sweep(oracle, p, direction, nu, order)), _frozen(sweep(oracle, p, direction, nu, order, ext=True)))
+    return _cache[key]
+
+
+def reference_b(oracle, kind, shape, direction, dtype, b, order, nu=2):
+    """The float64 reference of system `b` alone (no truth: what the 64-system runs compare with)."""
+    key = ("sweep_b", kind, tuple(shape), direction, np.dtype(dtype).char, b, order, nu)
+    if key in _cache or b == 0:
+        return references_b(oracle, kind, shape, direction, dtype, b, order, nu)[0]
+    key = ("sweep_b64", *key[1:])
+    if key not in _cache:
+        _cache[key] = _frozen(sweep(oracle, system_problem(kind, shape, direction, dtype, b), direction, nu, order))
+    return _cache[key]
+
+
+def first_difference(a, b, shape):
+    """(component, i, j, k) of the first edge, in storage order, at which two fields differ; None where they are equal."""
+    d = np.flatnonzero(np.asarray(a) != np.asarray(b))
+    if d.size == 0:
+        return None
+    nx, ny, nz = shape
+    dims = ((nx, ny + 1, nz + 1), (nx + 1, ny, nz + 1), (nx + 1, ny + 1, nz))
+    k = int(d[0])
+    for c, dim in enumerate(dims):
+        n = dim[0] * dim[1] * dim[2]
+        if k < n:
+            return (c, *(int(v) for v in np.unravel_index(k, dim, order='F')))
+        k -= n
 
 
 FLOOR = 16 * 2.0 ** -53          # a few final roundings where the reference itself is at 10 to 20 ulp
@@ -237,3 +311,22 @@ def sweep_runs():
     runs = {(shape, d, 1 if c["ordering"] == "colour" else 0) for c in SWEEP_CASES for shape, d in c["runs"]}
     runs |= {(shape, 0, 1 if o == "colour" else 0) for shape, o in POINT_CASES}
     return sorted(runs)
+
+
+# ---- wide runs: the same lines, many of them -----------------------------------------------------------------------------------------
+WIDE = 36                  # transverse cells of a wide run: 18 x 18 = 324 lines per colour -- 11 ... 324 line blocks per system in every
+#                            family's launch (the thread-per-line kernel: 6), more than the 8 XCDs, several counts no multiple of 8
+WIDE_FUSED_SCAN = 20       # `fused_scan` stops fusing above this; 100 lines per colour
+# (at 68 transverse cells the fused cases no longer fuse and qpl22 moves to k_line_sweep_tha: no wider than this)
+
+
+def wide_of(case):
+    return WIDE_FUSED_SCAN if case["name"] == "fused_scan" else WIDE
+
+
+def wide_runs(case):
+    """One run per (shape, direction) of a case: the line length and direction kept, both transverse axes `wide_of(case)` cells.
+    Benign generator only: on the wide hard model the float64 oracle itself is 1e-8 ... 2e-5 from the truth (lines through the
+    strongly stretched corner cells), and a bound relative to that says nothing."""
+    w = wide_of(case)
+    return [(tuple(n if a == d - 1 else w for a, n in enumerate(shape)), d) for shape, d in case["runs"]]

@@ -49,6 +49,35 @@ def test_case_selects_its_kernel(lib, monkeypatch, case):
         lib.use(prev)
 
 
+@pytest.mark.parametrize("case", hc.SWEEP_CASES, ids=[c["name"] for c in hc.SWEEP_CASES])
+def test_case_selects_its_kernel_with_three_systems(lib, monkeypatch, case):
+    """What tests/test_gpu_batch_families.py runs: the narrow runs and the wide ones (same lines, 36 x 36 of them) in a batch of three
+    stay with the case's kernel and its way of issuing the passes, and the wide runs keep their 324 lines per colour (fused_scan: 100)
+    -- more line blocks than XCDs in every family's launch, which is what they are for."""
+    for k, v in case["env"].items():
+        monkeypatch.setenv(k, v)
+    prev = lib.use(lib.LAB_PATH if case["library"] == "lab" else None)
+    wide = hc.wide_runs(case)
+    assert [d for _, d in wide] == [d for _, d in case["runs"]]
+    try:
+        for dtype in hc.DTYPES:
+            want = case["kernel"].format(t=hc.tname(dtype))
+            for is_wide, runs in ((False, case["runs"]), (True, wide)):
+                for (shape, direction), (narrow, _) in zip(runs, case["runs"]):
+                    p = lib.sweep_plan(shape, direction, dtype=dtype, ordering=case["ordering"], nsys=3, cu_count=CUS)
+                    assert p["kernel"].startswith(want), (case["name"], shape, direction, p["kernel"], want)
+                    assert not p["split"]
+                    f = lib.sweep_fuse_plan(shape, direction, NPASS, dtype=dtype, ordering=case["ordering"], nsys=3, cu_count=CUS)
+                    if case["fused"] is not None:
+                        assert f["fused"] == case["fused"], (case["name"], shape, direction, f)
+                    if is_wide:
+                        assert shape[direction - 1] == narrow[direction - 1]
+                        lines = 100 if case["name"] == "fused_scan" else 324
+                        assert p["lines_per_colour"] == lines, (case["name"], shape, direction, p)
+    finally:
+        lib.use(prev)
+
+
 def test_cases_cover_the_families_and_the_directions():
     fams = {c["kernel"].split("<")[0] for c in hc.SWEEP_CASES}
     assert fams == {"k_line_sweep", "k_line_sweep_rp", "k_line_sweep_qc", "k_line_sweep_qc_big", "k_line_sweep_thm", "k_line_sweep_tha",

@@ -2,7 +2,9 @@
 frequency through the SAME launches of the cycle.  The reference has no such mode (it solves one source-frequency
 pair per solver.solve call, simulations.py:916-1015); the contract checked here is that batching is invisible:
 every system of a batch gets bit for bit the field, the residual norms and the termination of a solve of its own.
-The single-system path itself is pinned against the oracle and the reference's goldens by the other GPU tests."""
+The single-system path itself is pinned against the oracle and the reference's goldens by the other GPU tests.
+The cycles here reach whichever kernels their levels select; the contract per sweep kernel family, by name, with a
+frozen system and launches of more line blocks than XCDs, is tests/test_gpu_batch_families.py."""
 import numpy as np
 import pytest
 

@@ -163,6 +163,40 @@ def test_hard_cases_of_the_gpu_tests_are_in_the_window(orc, shape, direction, or
 
 @pytest.mark.parametrize("dtype", hc.DTYPES)
 @pytest.mark.parametrize("shape,direction,order", hc.sweep_runs())
+def test_further_systems_of_the_hard_cases_are_in_the_window(orc, shape, direction, order, dtype):
+    """Systems 1 and 2 of the batched runs (tests/test_gpu_batch_families.py, hc.system_fields): the band system 0 is held to."""
+    for b in (1, 2):
+        e0, s = hc.system_fields("hard", shape, direction, dtype, b)
+        p = hc.problem("hard", shape, direction, dtype)
+        assert not np.array_equal(e0, p['e0']) and not np.array_equal(s, p['s'])
+        ref, truth = hc.references_b(orc, "hard", shape, direction, dtype, b, order)
+        e, change = hc.err(ref, truth), hc.err(e0, truth)
+        print(f"[system] {shape} dir {direction} order {order} {hc.tname(dtype)} system {b} err(ref) {e:.2e} change {change:.2e}")
+        assert 1e-13 <= e <= 1e-9, (b, e)
+        assert change > 1e-3, (b, change)
+
+
+def test_system_fields_are_cached_frozen_and_leave_the_case_alone():
+    shape, dtype = (6, 5, 12), np.complex128
+    p = hc.problem("hard", shape, 3, dtype)
+    assert hc.system_fields("hard", shape, 3, dtype, 0)[0] is p['e0']
+    e1, s1 = hc.system_fields("hard", shape, 3, dtype, 1)
+    e2, s2 = hc.system_fields("hard", shape, 3, dtype, 2)
+    assert hc.system_fields("hard", shape, 3, dtype, 1)[0] is e1 and not e1.flags.writeable and not s1.flags.writeable
+    assert not np.array_equal(e1, e2) and not np.array_equal(s1, s2)
+    assert 0.1 < np.abs(s1).max() / np.abs(p['s']).max() < 10 and np.abs(s1).max() < 1e-4            # (the hard source scale)
+    assert np.abs(hc.system_fields("benign", shape, 3, dtype, 1)[1]).max() > 1
+    for f in (e1, s1):
+        fx, fy, fz = hc.field_views(f, shape)
+        assert not fx[:, [0, -1], :].any() and not fy[:, :, [0, -1]].any() and not fz[[0, -1], :, :].any()
+    assert hc.first_difference(e1, e1, shape) is None
+    other = np.array(e1)
+    other[6 * 6 * 13 + 3] += 1          # the fourth edge of the y-component
+    assert hc.first_difference(e1, other, shape) == (1, 3, 0, 0)
+
+
+@pytest.mark.parametrize("dtype", hc.DTYPES)
+@pytest.mark.parametrize("shape,direction,order", hc.sweep_runs())
 def test_benign_cases_of_the_gpu_tests_are_near_the_floor(orc, shape, direction, order, dtype):
     """On the benign generator the reference is a few ulp from the truth: the bound of the GPU tests there is the floor's."""
     p, ref, truth = hc.references(orc, "benign", shape, direction, dtype, order=order)
