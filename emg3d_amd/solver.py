@@ -1467,17 +1467,10 @@ def _krylov_sources(dev, vars_, active):
         dev.bvec_copy(dst, dev.EFIELD)
         return failed
 
-    def callback(var):
-        def cb(l2):
-            _count_krylov_step(var)
-            var.l2 = l2
-            _log_krylov_step(var)
-        return cb
-
     drive = {'bicgstab': _bicgstab_device_batched, 'cgs': _cgs_device_batched}[name]
     failed = []
     codes = drive(dev, n, rtol=v0.tol, maxiter=v0.ssl_maxit, atol=1e-30, psolve=psolve if v0.cycle else None,
-                  callbacks=[callback(var) for var in vars_], active=active, failed=failed)
+                  callbacks=[lambda l2, var=var: _krylov_step(var, l2) for var in vars_], active=active, failed=failed)
     for b, var in enumerate(vars_):
         if active[b]:
             _krylov_exit_message(var, codes[b], b in failed)
@@ -1703,159 +1696,121 @@ DEVICE_KRYLOV = True
 PREPARE_AHEAD = True
 
 
-def _bicgstab_device(dev, b, x0, rtol, maxiter, atol, psolve, callback):
-    X, R, RT, P, V, S, T, PH, SH, B, TMP, RES = range(12)
-    dev.vec_alloc(12)
-    dev.vec_set(B, b)
-    dev.vec_set(X, x0)
-    bnrm2 = dev.vec_norm(B)
-    atol = max(float(atol), float(rtol) * float(bnrm2))
-    if bnrm2 == 0:
-        return np.array(b), 0
-    rhotol = np.finfo(dev.dtype.char).eps ** 2
-    omegatol = rhotol
+class _Systems:
+    """What the two backends of the Krylov bodies (``_bicgstab``, ``_cgs``) share: which systems still iterate and their
+    return codes.  A backend adds the vector primitives the bodies are written on -- ``load``, ``start``, ``copy``,
+    ``axpy``, ``scale``, ``dot``, ``norm`` (lists, one entry per system), ``amatvec``, ``psolve``, ``sync``."""
 
-    def residual_into(dst):          # dst = b - A x
-        dev.vec_amatvec(TMP, X)
-        dev.vec_copy(dst, B)
-        dev.vec_axpy(dst, -1.0, TMP)
-
-    if np.any(x0):
-        residual_into(R)
-    else:
-        dev.vec_copy(R, B)
-    dev.vec_copy(RT, R)
-    rho_prev = omega = alpha = None
-
-    def apply_psolve(src, dst):
-        if psolve is None:
-            dev.vec_copy(dst, src)
-        else:
-            psolve(src, dst)
-
-    for iteration in range(maxiter):
-        if dev.vec_norm(R) < atol:
-            return dev.vec_get(X), 0
-        rho = dev.vec_dot(RT, R)
-        if abs(rho) < rhotol:
-            return dev.vec_get(X), -10
-        if iteration > 0:
-            if abs(omega) < omegatol:
-                return dev.vec_get(X), -11
-            beta = (rho / rho_prev) * (alpha / omega)
-            dev.vec_axpy(P, -omega, V)       # p -= omega*v
-            dev.vec_scale(P, beta)           # p *= beta
-            dev.vec_axpy(P, 1.0, R)          # p += r
-        else:
-            dev.vec_copy(P, R)
-        apply_psolve(P, PH)
-        dev.vec_amatvec(V, PH)
-        rv = dev.vec_dot(RT, V)
-        if rv == 0:
-            return dev.vec_get(X), -11
-        alpha = rho / rv
-        dev.vec_axpy(R, -alpha, V)           # r -= alpha*v
-        dev.vec_copy(S, R)                   # s = r
-        if dev.vec_norm(S) < atol:
-            dev.vec_axpy(X, alpha, PH)
-            return dev.vec_get(X), 0
-        apply_psolve(S, SH)
-        dev.vec_amatvec(T, SH)
-        omega = dev.vec_dot(T, S) / dev.vec_dot(T, T)
-        dev.vec_axpy(X, alpha, PH)
-        dev.vec_axpy(X, omega, SH)
-        dev.vec_axpy(R, -omega, T)
-        rho_prev = rho
-        if callback:
-            residual_into(RES)               # the reference's callback: || sfield - A x ||
-            callback(dev.vec_norm(RES))
-    return dev.vec_get(X), maxiter
-
-
-def _cgs_device(dev, b, x0, rtol, maxiter, atol, psolve, callback):
-    """SciPy's ``cgs`` (the reference's call site emg3d/solver.py:717-719; SciPy >= 1.12 ``_isolve/iterative.py``)
-    restated operation by operation on ``emg3d_mg_vec_*``: every Krylov vector stays in HBM, the host sees two dot
-    products and one norm per iteration.  Same breakdown tests and exit codes."""
-    X, R, RT, P, U, Q, PH, VH, UQ, UH, B, TMP = range(12)
-    dev.vec_alloc(12)
-    dev.vec_set(B, b)
-    dev.vec_set(X, x0)
-    bnrm2 = dev.vec_norm(B)
-    atol = max(float(atol), float(rtol) * float(bnrm2))
-    if bnrm2 == 0:
-        return np.array(b), 0
-    rhotol = np.finfo(dev.dtype.char).eps ** 2
-
-    def residual_into(dst):          # dst = b - A x
-        dev.vec_amatvec(TMP, X)
-        dev.vec_copy(dst, B)
-        dev.vec_axpy(dst, -1.0, TMP)
-
-    def apply_psolve(src, dst):
-        if psolve is None:
-            dev.vec_copy(dst, src)
-        else:
-            psolve(src, dst)
-
-    if np.any(x0):
-        residual_into(R)
-    else:
-        dev.vec_copy(R, B)
-    dev.vec_copy(RT, R)
-    rho_prev = None
-    for iteration in range(maxiter):
-        if dev.vec_norm(R) < atol:
-            return dev.vec_get(X), 0
-        rho = dev.vec_dot(RT, R)
-        if abs(rho) < rhotol:
-            return dev.vec_get(X), -10
-        if iteration > 0:
-            beta = rho / rho_prev
-            dev.vec_copy(U, R)               # u = r + beta q
-            dev.vec_axpy(U, beta, Q)
-            dev.vec_scale(P, beta)           # p = u + beta (q + beta p)
-            dev.vec_axpy(P, 1.0, Q)
-            dev.vec_scale(P, beta)
-            dev.vec_axpy(P, 1.0, U)
-        else:
-            dev.vec_copy(P, R)
-            dev.vec_copy(U, R)
-        apply_psolve(P, PH)
-        dev.vec_amatvec(VH, PH)
-        rv = dev.vec_dot(RT, VH)
-        if rv == 0:
-            return dev.vec_get(X), -11
-        alpha = rho / rv
-        dev.vec_copy(Q, U)                   # q = u - alpha vhat
-        dev.vec_axpy(Q, -alpha, VH)
-        dev.vec_copy(UQ, U)                  # uhat = M (u + q)
-        dev.vec_axpy(UQ, 1.0, Q)
-        apply_psolve(UQ, UH)
-        dev.vec_axpy(X, alpha, UH)
-        residual_into(R)                     # the true residual, as SciPy computes it
-        rho_prev = rho
-        if callback:
-            callback(dev.vec_norm(R))        # the reference's callback: || sfield - A x ||
-    return dev.vec_get(X), maxiter
-
-
-class _Lockstep:
-    """Bookkeeping of the batched Krylov drivers: which systems of the handle still iterate, their return codes, and the
-    per-system views of the batched reductions.  All active systems execute iteration k together; a system that returns
-    is frozen (``set_mask``) and its vectors stay as they are from then on."""
-
-    def __init__(self, dev, n, active=None):
-        self.dev = dev
-        self.nsys = dev.nsys
-        self.active = np.zeros(self.nsys, dtype=np.int32)
+    def __init__(self, dev, psolve, nsys, n, active=None):
+        self.dev, self._psolve, self.nsys = dev, psolve, nsys
+        self.active = np.zeros(nsys, dtype=np.int32)
         self.active[:n] = 1 if active is None else np.asarray(active)[:n]
         self.codes = [0] * n
-        self.failed = []            # systems whose preconditioner failed (code -1, as krylov() sets it)
-        self.cplx = np.dtype(dev.dtype).kind == 'c'
-        self._on_device = None
 
     def live(self):
         return [b for b in range(len(self.codes)) if self.active[b]]
+
+    def finish(self, b, code):
+        self.active[b] = 0
+        self.codes[b] = code
+
+    def finish_where(self, code, hit):
+        for b in self.live():
+            if hit(b):
+                self.finish(b, code)
+
+    def all_finished(self):
+        """Freeze on the device what has finished since the last time; has every system?"""
+        self.sync()
+        return not self.live()
+
+    def each(self, value):
+        """[value(b)] for the systems that still iterate, None for the others."""
+        return [value(b) if b < len(self.codes) and self.active[b] else None for b in range(self.nsys)]
+
+    def coef(self, values, sign=1):
+        """Per-system coefficients for axpy / scale (0 for frozen systems, which the kernels skip); sign -1: -v."""
+        return [0.0 if (v is None or not self.active[k]) else (-v if sign < 0 else v) for k, v in enumerate(values)]
+
+
+class _OneSystem(_Systems):
+    """Backend of a single solve: the system the handle has selected, on ``vec_*`` one to one.  No mask, no ``bvec_*``;
+    ``b`` and ``x0`` are host arrays, and a ``_ConvergenceError`` of ``psolve(src, dst)`` goes up to ``krylov()``."""
+    lockstep = False
+
+    def __init__(self, dev, psolve, b=None, x0=None):
+        super().__init__(dev, psolve, 1, 1)
+        self.copy, self.amatvec = dev.vec_copy, dev.vec_amatvec
+        self.b, self.x0 = b, x0
+
+    def load(self, nvec, X, B):
+        self.dev.vec_alloc(nvec)
+        self.dev.vec_set(B, self.b)
+        self.dev.vec_set(X, self.x0)
+        self.X = X
+
+    def start(self, R, RT, B, TMP):
+        """r = rt = b - A x0.  (A zero right-hand side has finished: nothing more is issued.)"""
+        self.zero_rhs = not self.live()
+        if self.zero_rhs:
+            return
+        if np.any(self.x0):
+            _residual_into(self, R, self.X, B, TMP)
+        else:
+            self.copy(R, B)
+        self.copy(RT, R)
+
+    def sync(self, mask=None):
+        pass
+
+    def axpy(self, y, coefs, x):
+        self.dev.vec_axpy(y, coefs[0] if isinstance(coefs, list) else coefs, x)
+
+    def scale(self, y, coefs):
+        self.dev.vec_scale(y, coefs[0])
+
+    def dot(self, a, b):
+        return [self.dev.vec_dot(a, b)]
+
+    def norm(self, a):
+        return [self.dev.vec_norm(a)]
+
+    def psolve(self, src, dst):
+        if self._psolve is None:
+            self.copy(dst, src)
+        else:
+            self._psolve(src, dst)
+
+    def solve(self, body, rtol, maxiter, atol, callback):
+        code, = body(self, rtol, maxiter, atol, [callback] if callback else None)
+        return (np.array(self.b) if self.zero_rhs else self.dev.vec_get(self.X)), code
+
+
+class _Lockstep(_Systems):
+    """Backend of a batched solve: the first ``n`` systems of a batched handle on ``bvec_*``.  All active systems execute
+    iteration k together; a system that returns is frozen (``set_mask``) and its vectors stay as they are from then on.
+    The right-hand sides are the level-0 sources in the handle, the start vector is zero."""
+    lockstep = True
+
+    def __init__(self, dev, n, active=None, psolve=None, failed=None):
+        super().__init__(dev, psolve, dev.nsys, n, active)
+        self.copy, self.amatvec, self.axpy, self.scale = dev.bvec_copy, dev.bvec_amatvec, dev.bvec_axpy, dev.bvec_scale
+        self.failed = [] if failed is None else failed      # systems whose preconditioner failed (code -1, as krylov() sets it)
+        self.cplx = np.dtype(dev.dtype).kind == 'c'
+        self._on_device = None
+
+    def load(self, nvec, X, B):
+        self.dev.bvec_alloc(nvec)
+        self.sync(self.only(range(len(self.codes))))
+        self.dev.bvec_zero(X)
+        self.sync()
+        self.copy(B, self.dev.SFIELD)
+        self.X = X
+
+    def start(self, R, RT, B, TMP):
+        self.sync()
+        self.copy(R, B)
+        self.copy(RT, R)
 
     def sync(self, mask=None):
         """The device's mask <- ``mask`` (default: the active systems), if it is another one."""
@@ -1869,12 +1824,8 @@ class _Lockstep:
         mask[list(systems)] = 1
         return mask
 
-    def finish(self, b, code):
-        self.active[b] = 0
-        self.codes[b] = code
-
     def dot(self, a, b):
-        """[vec_dot(a_b, b_b)] as Python scalars (the arithmetic of the single-system driver), None for frozen systems."""
+        """[vec_dot(a_b, b_b)] as Python scalars (what ``vec_dot`` gives a single solve), None for frozen systems."""
         d = self.dev.bvec_dot(a, b)
         return [(complex(d[k]) if self.cplx else float(d[k])) if k < len(self.codes) and self.active[k] else None
                 for k in range(self.nsys)]
@@ -1882,230 +1833,186 @@ class _Lockstep:
     def norm(self, a):
         return [None if v is None else float(np.sqrt(abs(v))) for v in self.dot(a, a)]
 
-    def coef(self, values, sign=1):
-        """Per-system coefficients for bvec_axpy / bvec_scale (0 for frozen systems, which the kernels skip); sign -1: -v."""
-        return [0.0 if (v is None or not self.active[k]) else (-v if sign < 0 else v) for k, v in enumerate(values)]
+    def psolve(self, src, dst):
+        """``psolve(src, dst, mask)`` applies the preconditioner to the systems of ``mask`` (the device's mask on entry, and
+        again on return) and returns those for which it failed."""
+        if self._psolve is None:
+            self.copy(dst, src)
+            return
+        for b in self._psolve(src, dst, self.active.copy()):
+            self.sync(self.only([b]))       # as a single solve ends there: the returned field is zero
+            self.dev.bvec_zero(self.X)
+            self.finish(b, -1)
+            self.failed.append(b)
+        self.sync()
+
+
+def _residual_into(ops, dst, X, B, TMP):
+    """dst = b - A x"""
+    ops.amatvec(TMP, X)
+    ops.copy(dst, B)
+    ops.axpy(dst, -1.0, TMP)
+
+
+def _krylov_start(ops, nvec, rtol, atol, X, R, RT, B, TMP):
+    """x = x0, r = rt = b - A x0; a system with a zero right-hand side finishes with code 0.  Returns the absolute
+    tolerance of every system, max(atol, rtol ||b||), and rhotol."""
+    ops.load(nvec, X, B)
+    bnrm2 = ops.norm(B)
+    tol = [None if v is None else max(float(atol), float(rtol) * float(v)) for v in bnrm2]
+    ops.finish_where(0, lambda b: bnrm2[b] == 0)
+    ops.start(R, RT, B, TMP)
+    return tol, np.finfo(np.dtype(ops.dev.dtype).char).eps ** 2
+
+
+def _bicgstab(ops, rtol, maxiter, atol, callbacks):
+    """The BiCGSTAB iteration (see above) of every system of the backend ``ops`` (``_OneSystem``, ``_Lockstep``).  Every
+    system keeps its own rho, alpha, omega and atol and goes through exactly the operations of an iteration of its own;
+    it ends with ``ops.finish(b, code)``: 0, maxiter, -10, -11 (-1: its preconditioner failed, the iterate is zero).
+    ``callbacks[b]`` gets || s_b - A x_b || after every iteration of system b.  Returns the list of exit codes; the
+    iterates are left in vector 0."""
+    X, R, RT, P, V, S, T, PH, SH, B, TMP, RES = range(12)
+    tol, rhotol = _krylov_start(ops, 12, rtol, atol, X, R, RT, B, TMP)
+    omegatol = rhotol
+    for iteration in range(maxiter):
+        if not ops.live():
+            break
+        nr = ops.norm(R)
+        ops.finish_where(0, lambda b: nr[b] < tol[b])
+        if ops.all_finished():
+            break
+        rho = ops.dot(RT, R)
+        ops.finish_where(-10, lambda b: abs(rho[b]) < rhotol)
+        if iteration > 0:
+            ops.finish_where(-11, lambda b: abs(omega[b]) < omegatol)
+            if ops.all_finished():
+                break
+            beta = ops.each(lambda b: (rho[b] / rho_prev[b]) * (alpha[b] / omega[b]))
+            ops.axpy(P, ops.coef(omega, -1), V)         # p -= omega*v
+            ops.scale(P, ops.coef(beta))                # p *= beta
+            ops.axpy(P, 1.0, R)                         # p += r
+        else:
+            if ops.all_finished():
+                break
+            ops.copy(P, R)
+        ops.psolve(P, PH)
+        if not ops.live():
+            break
+        ops.amatvec(V, PH)
+        rv = ops.dot(RT, V)
+        ops.finish_where(-11, lambda b: rv[b] == 0)
+        if ops.all_finished():
+            break
+        alpha = ops.each(lambda b: rho[b] / rv[b])
+        ops.axpy(R, ops.coef(alpha, -1), V)             # r -= alpha*v
+        ops.copy(S, R)                                  # s = r
+        ns = ops.norm(S)
+        done = [b for b in ops.live() if ns[b] < tol[b]]
+        # x += alpha*phat: the update of a system that converges here and the first of the two updates of the others
+        # (nothing reads x in between: the same two operations on x in the same order either way).  In lockstep it is
+        # issued once for all systems, before they part; a single solve that goes on issues it after omega, as SciPy.
+        if ops.lockstep or done:
+            ops.axpy(X, ops.coef(alpha), PH)
+        for b in done:
+            ops.finish(b, 0)
+        if ops.all_finished():
+            break
+        ops.psolve(S, SH)
+        if not ops.live():
+            break
+        ops.amatvec(T, SH)
+        ts, tt = ops.dot(T, S), ops.dot(T, T)
+        omega, rho_prev = ops.each(lambda b: ts[b] / tt[b]), rho
+        if not ops.lockstep:
+            ops.axpy(X, ops.coef(alpha), PH)
+        ops.axpy(X, ops.coef(omega), SH)
+        ops.axpy(R, ops.coef(omega, -1), T)
+        if callbacks:
+            _residual_into(ops, RES, X, B, TMP)         # the reference's callback: || sfield - A x ||
+            res = ops.norm(RES)
+            for b in ops.live():
+                callbacks[b](res[b])
+    for b in ops.live():
+        ops.finish(b, maxiter)
+    return ops.codes
+
+
+def _cgs(ops, rtol, maxiter, atol, callbacks):
+    """SciPy's ``cgs`` (the reference's call site emg3d/solver.py:717-719; SciPy >= 1.12 ``_isolve/iterative.py``)
+    restated operation by operation on the primitives of the backend ``ops``, as ``_bicgstab`` is: every Krylov vector
+    stays in HBM, the host sees two dot products and one norm per iteration.  Same breakdown tests and exit codes."""
+    X, R, RT, P, U, Q, PH, VH, UQ, UH, B, TMP = range(12)
+    tol, rhotol = _krylov_start(ops, 12, rtol, atol, X, R, RT, B, TMP)
+    for iteration in range(maxiter):
+        if not ops.live():
+            break
+        nr = ops.norm(R)
+        ops.finish_where(0, lambda b: nr[b] < tol[b])
+        if ops.all_finished():
+            break
+        rho = ops.dot(RT, R)
+        ops.finish_where(-10, lambda b: abs(rho[b]) < rhotol)
+        if ops.all_finished():
+            break
+        if iteration > 0:
+            beta = ops.each(lambda b: rho[b] / rho_prev[b])
+            ops.copy(U, R)                              # u = r + beta q
+            ops.axpy(U, ops.coef(beta), Q)
+            ops.scale(P, ops.coef(beta))                # p = u + beta (q + beta p)
+            ops.axpy(P, 1.0, Q)
+            ops.scale(P, ops.coef(beta))
+            ops.axpy(P, 1.0, U)
+        else:
+            ops.copy(P, R)
+            ops.copy(U, R)
+        ops.psolve(P, PH)
+        if not ops.live():
+            break
+        ops.amatvec(VH, PH)
+        rv = ops.dot(RT, VH)
+        ops.finish_where(-11, lambda b: rv[b] == 0)
+        if ops.all_finished():
+            break
+        alpha, rho_prev = ops.each(lambda b: rho[b] / rv[b]), rho
+        ops.copy(Q, U)                                  # q = u - alpha vhat
+        ops.axpy(Q, ops.coef(alpha, -1), VH)
+        ops.copy(UQ, U)                                 # uhat = M (u + q)
+        ops.axpy(UQ, 1.0, Q)
+        ops.psolve(UQ, UH)
+        if not ops.live():
+            break
+        ops.axpy(X, ops.coef(alpha), UH)
+        _residual_into(ops, R, X, B, TMP)               # the true residual, as SciPy computes it
+        if callbacks:
+            res = ops.norm(R)                           # the reference's callback: || sfield - A x ||
+            for b in ops.live():
+                callbacks[b](res[b])
+    for b in ops.live():
+        ops.finish(b, maxiter)
+    return ops.codes
+
+
+def _bicgstab_device(dev, b, x0, rtol, maxiter, atol, psolve, callback):
+    """``_bicgstab`` for the system the handle has selected, from the host arrays ``b`` and ``x0``: (x, exit code)."""
+    return _OneSystem(dev, psolve, b, x0).solve(_bicgstab, rtol, maxiter, atol, callback)
+
+
+def _cgs_device(dev, b, x0, rtol, maxiter, atol, psolve, callback):
+    return _OneSystem(dev, psolve, b, x0).solve(_cgs, rtol, maxiter, atol, callback)
 
 
 def _bicgstab_device_batched(dev, n, rtol, maxiter, atol, psolve, callbacks, active=None, failed=None):
-    """``_bicgstab_device`` for the first ``n`` systems of a batched handle in lockstep, restated on ``bvec_*``: same order
-    of operations, same breakdown tests and, per system, the same exit codes (0, maxiter, -10, -11; -1: the
-    preconditioner failed for that system and its iterate is zero).  Every system keeps its own rho, alpha, omega and
-    atol and goes through exactly the operations of an iteration of its own.  The right-hand sides are the level-0
-    sources in the handle, the start vector is zero; the iterates are left in batched vector 0.  ``psolve(src, dst,
-    mask)`` applies the preconditioner to the systems of ``mask`` (the device's mask on entry, and again on return) and
-    returns those for which it failed; ``callbacks[b]`` gets || s_b - A x_b || after every iteration of system b;
-    ``active``: flags, 0 leaves a system out from the start.  Returns the list of exit codes; the systems whose
-    preconditioner failed are appended to ``failed`` (a code of -1 alone may also be ``maxiter``)."""
-    X, R, RT, P, V, S, T, PH, SH, B, TMP, RES = range(12)
-    ls = _Lockstep(dev, n, active)
-    dev.bvec_alloc(12)
-    ls.sync(ls.only(range(n)))
-    dev.bvec_zero(X)
-    ls.sync()
-    dev.bvec_copy(B, dev.SFIELD)
-    bnrm2 = ls.norm(B)
-    tol = [None if v is None else max(float(atol), float(rtol) * float(v)) for v in bnrm2]
-    for b in ls.live():
-        if bnrm2[b] == 0:
-            ls.finish(b, 0)
-    rhotol = np.finfo(np.dtype(dev.dtype).char).eps ** 2
-    omegatol = rhotol
-    rho_prev, omega, alpha = [None] * ls.nsys, [None] * ls.nsys, [None] * ls.nsys
-
-    def apply_psolve(src, dst):
-        if psolve is None:
-            dev.bvec_copy(dst, src)
-            return
-        failed = psolve(src, dst, ls.active.copy())      # (the device's mask on return: the one it got)
-        for b in failed:             # as a single solve ends there: the returned field is zero
-            ls.sync(ls.only([b]))
-            dev.bvec_zero(X)
-            ls.finish(b, -1)
-            ls.failed.append(b)
-        ls.sync()
-
-    ls.sync()
-    dev.bvec_copy(R, B)
-    dev.bvec_copy(RT, R)
-    for iteration in range(maxiter):
-        if not ls.live():
-            break
-        nr = ls.norm(R)
-        for b in ls.live():
-            if nr[b] < tol[b]:
-                ls.finish(b, 0)
-        ls.sync()
-        if not ls.live():
-            break
-        rho = ls.dot(RT, R)
-        for b in ls.live():
-            if abs(rho[b]) < rhotol:
-                ls.finish(b, -10)
-        if iteration > 0:
-            for b in ls.live():
-                if abs(omega[b]) < omegatol:
-                    ls.finish(b, -11)
-            ls.sync()
-            if not ls.live():
-                break
-            beta = [None] * ls.nsys
-            for b in ls.live():
-                beta[b] = (rho[b] / rho_prev[b]) * (alpha[b] / omega[b])
-            dev.bvec_axpy(P, ls.coef(omega, -1), V)     # p -= omega*v
-            dev.bvec_scale(P, ls.coef(beta))            # p *= beta
-            dev.bvec_axpy(P, 1.0, R)                    # p += r
-        else:
-            ls.sync()
-            if not ls.live():
-                break
-            dev.bvec_copy(P, R)
-        apply_psolve(P, PH)
-        if not ls.live():
-            break
-        dev.bvec_amatvec(V, PH)
-        rv = ls.dot(RT, V)
-        for b in ls.live():
-            if rv[b] == 0:
-                ls.finish(b, -11)
-        ls.sync()
-        if not ls.live():
-            break
-        for b in ls.live():
-            alpha[b] = rho[b] / rv[b]
-        dev.bvec_axpy(R, ls.coef(alpha, -1), V)         # r -= alpha*v
-        dev.bvec_copy(S, R)                             # s = r
-        ns = ls.norm(S)
-        # x += alpha*phat: the update of a system that converges here and the first of the two updates of the others
-        # (nothing reads x in between: the same two operations on x in the same order either way)
-        dev.bvec_axpy(X, ls.coef(alpha), PH)
-        for b in ls.live():
-            if ns[b] < tol[b]:
-                ls.finish(b, 0)
-        ls.sync()
-        if not ls.live():
-            break
-        apply_psolve(S, SH)
-        if not ls.live():
-            break
-        dev.bvec_amatvec(T, SH)
-        ts, tt = ls.dot(T, S), ls.dot(T, T)
-        for b in ls.live():
-            omega[b] = ts[b] / tt[b]
-            rho_prev[b] = rho[b]
-        dev.bvec_axpy(X, ls.coef(omega), SH)
-        dev.bvec_axpy(R, ls.coef(omega, -1), T)
-        if callbacks:
-            dev.bvec_amatvec(TMP, X)                    # the reference's callback: || sfield - A x ||
-            dev.bvec_copy(RES, B)
-            dev.bvec_axpy(RES, -1.0, TMP)
-            res = ls.norm(RES)
-            for b in ls.live():
-                callbacks[b](res[b])
-    for b in ls.live():
-        ls.finish(b, maxiter)
-    if failed is not None:
-        failed.extend(ls.failed)
-    return ls.codes
+    """``_bicgstab`` for the first ``n`` systems of a batched handle in lockstep: per system what ``_bicgstab_device``
+    gives it alone.  The right-hand sides are the level-0 sources in the handle, the start vector is zero; the iterates
+    are left in batched vector 0.  ``psolve(src, dst, mask)``: see ``_Lockstep.psolve``; ``active``: flags, 0 leaves a
+    system out from the start.  Returns the list of exit codes; the systems whose preconditioner failed are appended to
+    ``failed`` (a code of -1 alone may also be ``maxiter``)."""
+    return _bicgstab(_Lockstep(dev, n, active, psolve, failed), rtol, maxiter, atol, callbacks)
 
 
 def _cgs_device_batched(dev, n, rtol, maxiter, atol, psolve, callbacks, active=None, failed=None):
-    """``_cgs_device`` for the first ``n`` systems of a batched handle in lockstep (see ``_bicgstab_device_batched``)."""
-    X, R, RT, P, U, Q, PH, VH, UQ, UH, B, TMP = range(12)
-    ls = _Lockstep(dev, n, active)
-    dev.bvec_alloc(12)
-    ls.sync(ls.only(range(n)))
-    dev.bvec_zero(X)
-    ls.sync()
-    dev.bvec_copy(B, dev.SFIELD)
-    bnrm2 = ls.norm(B)
-    tol = [None if v is None else max(float(atol), float(rtol) * float(v)) for v in bnrm2]
-    for b in ls.live():
-        if bnrm2[b] == 0:
-            ls.finish(b, 0)
-    rhotol = np.finfo(np.dtype(dev.dtype).char).eps ** 2
-    rho_prev = [None] * ls.nsys
-
-    def apply_psolve(src, dst):
-        if psolve is None:
-            dev.bvec_copy(dst, src)
-            return
-        failed = psolve(src, dst, ls.active.copy())      # (the device's mask on return: the one it got)
-        for b in failed:             # as a single solve ends there: the returned field is zero
-            ls.sync(ls.only([b]))
-            dev.bvec_zero(X)
-            ls.finish(b, -1)
-            ls.failed.append(b)
-        ls.sync()
-
-    ls.sync()
-    dev.bvec_copy(R, B)
-    dev.bvec_copy(RT, R)
-    for iteration in range(maxiter):
-        if not ls.live():
-            break
-        nr = ls.norm(R)
-        for b in ls.live():
-            if nr[b] < tol[b]:
-                ls.finish(b, 0)
-        ls.sync()
-        if not ls.live():
-            break
-        rho = ls.dot(RT, R)
-        for b in ls.live():
-            if abs(rho[b]) < rhotol:
-                ls.finish(b, -10)
-        ls.sync()
-        if not ls.live():
-            break
-        if iteration > 0:
-            beta = [None] * ls.nsys
-            for b in ls.live():
-                beta[b] = rho[b] / rho_prev[b]
-            dev.bvec_copy(U, R)                         # u = r + beta q
-            dev.bvec_axpy(U, ls.coef(beta), Q)
-            dev.bvec_scale(P, ls.coef(beta))            # p = u + beta (q + beta p)
-            dev.bvec_axpy(P, 1.0, Q)
-            dev.bvec_scale(P, ls.coef(beta))
-            dev.bvec_axpy(P, 1.0, U)
-        else:
-            dev.bvec_copy(P, R)
-            dev.bvec_copy(U, R)
-        apply_psolve(P, PH)
-        if not ls.live():
-            break
-        dev.bvec_amatvec(VH, PH)
-        rv = ls.dot(RT, VH)
-        for b in ls.live():
-            if rv[b] == 0:
-                ls.finish(b, -11)
-        ls.sync()
-        if not ls.live():
-            break
-        alpha = [None] * ls.nsys
-        for b in ls.live():
-            alpha[b] = rho[b] / rv[b]
-            rho_prev[b] = rho[b]
-        dev.bvec_copy(Q, U)                             # q = u - alpha vhat
-        dev.bvec_axpy(Q, ls.coef(alpha, -1), VH)
-        dev.bvec_copy(UQ, U)                            # uhat = M (u + q)
-        dev.bvec_axpy(UQ, 1.0, Q)
-        apply_psolve(UQ, UH)
-        if not ls.live():
-            break
-        dev.bvec_axpy(X, ls.coef(alpha), UH)
-        dev.bvec_amatvec(TMP, X)                        # r = b - A x: the true residual, as SciPy computes it
-        dev.bvec_copy(R, B)
-        dev.bvec_axpy(R, -1.0, TMP)
-        if callbacks:
-            res = ls.norm(R)                            # the reference's callback: || sfield - A x ||
-            for b in ls.live():
-                callbacks[b](res[b])
-    for b in ls.live():
-        ls.finish(b, maxiter)
-    if failed is not None:
-        failed.extend(ls.failed)
-    return ls.codes
+    """``_cgs`` for the first ``n`` systems of a batched handle in lockstep (see ``_bicgstab_device_batched``)."""
+    return _cgs(_Lockstep(dev, n, active, psolve, failed), rtol, maxiter, atol, callbacks)
 
 
 def _krylov_fits_device(dev, name, m=20, nsys=1):
@@ -2152,14 +2059,9 @@ def _gcrotmk_device(dev, b, x0, rtol, maxiter, atol, psolve, callback, m=20, k=N
     X, R, B, TMP, RT = new_vec(), new_vec(), new_vec(), new_vec(), new_vec()
     dev.vec_set(B, b)
     dev.vec_set(X, x0)
-
-    def residual_into(dst):          # dst = b - A x
-        dev.vec_amatvec(TMP, X)
-        dev.vec_copy(dst, B)
-        dev.vec_axpy(dst, -1.0, TMP)
-
+    ops = _OneSystem(dev, psolve)         # (its b - A x and its identity-or-preconditioner application)
     if np.any(x0):
-        residual_into(R)
+        _residual_into(ops, R, X, B, TMP)
     else:
         dev.vec_copy(R, B)
     b_norm = dev.vec_norm(B)
@@ -2179,10 +2081,7 @@ def _gcrotmk_device(dev, b, x0, rtol, maxiter, atol, psolve, callback, m=20, k=N
         j = 0
         for j in range(ml):
             z = new_vec()
-            if psolve is None:
-                dev.vec_copy(z, vs[-1])
-            else:
-                psolve(vs[-1], z)
+            ops.psolve(vs[-1], z)
             w = new_vec()
             dev.vec_amatvec(w, z)
             w_norm = dev.vec_norm(w)
@@ -2221,12 +2120,12 @@ def _gcrotmk_device(dev, b, x0, rtol, maxiter, atol, psolve, callback, m=20, k=N
     j_outer = -1
     for j_outer in range(maxiter):
         if callback is not None:
-            residual_into(RT)
+            _residual_into(ops, RT, X, B, TMP)
             callback(dev.vec_norm(RT))              # the reference's callback: || sfield - A x ||
         beta = dev.vec_norm(R)
         beta_tol = max(atol, rtol * b_norm)
         if beta <= beta_tol and (j_outer > 0 or CU):
-            residual_into(R)                        # recompute the residual to avoid rounding error
+            _residual_into(ops, R, X, B, TMP)       # recompute the residual to avoid rounding error
             beta = dev.vec_norm(R)
         if beta <= beta_tol:
             j_outer = -1
@@ -2282,13 +2181,12 @@ def _gcrotmk_device(dev, b, x0, rtol, maxiter, atol, psolve, callback, m=20, k=N
     return dev.vec_get(X), j_outer + 1
 
 
-def _count_krylov_step(var):
+def _krylov_step(var, l2):
+    """End of a Krylov iteration: bookkeeping and log line (solver.py:685-708).  ``l2``: || sfield - A x ||, or a function
+    that computes it (after the time of the step is taken, as the reference does)."""
     var._ssl_it += 1
     var.runtime_at_cycle = np.r_[var.runtime_at_cycle, var.time.elapsed]
-
-
-def _log_krylov_step(var):
-    """End of a Krylov iteration, ``var.l2`` = || sfield - A x ||: bookkeeping and log line (solver.py:685-708)."""
+    var.l2 = l2() if callable(l2) else l2
     var.error_at_cycle = np.r_[var.error_at_cycle, var.l2]
     if var.verb > 3:
         log = f"   [{var.time.now}]   {var.l2/var.l2_refe:.3e} "
@@ -2354,13 +2252,10 @@ def krylov(grid, model, sfield, efield, var, dev=None):
         M = ssl.LinearOperator(shape=(grid.nE, grid.nE), dtype=sfield.dtype, matvec=mg_matvec)
 
     def callback(x):
-        _count_krylov_step(var)
         if isinstance(x, float):        # device path: the norm of s - A x, computed on the device
-            var.l2 = x
+            _krylov_step(var, x)
         else:
-            r = np.asarray(sfield) - dev.amatvec(np.asarray(x))
-            var.l2 = float(np.linalg.norm(r))
-        _log_krylov_step(var)
+            _krylov_step(var, lambda: float(np.linalg.norm(np.asarray(sfield) - dev.amatvec(np.asarray(x)))))
 
     def mg_on_device(src, dst):
         """dst = M src with both vectors on the device (same cycles as mg_matvec)."""

@@ -160,7 +160,34 @@ class DenseHandle:
         return self._bv(i)[b].copy()
 
 
+class RecordingHandle(DenseHandle):
+    """``DenseHandle`` that logs every primitive call as (method name, integer arguments...): the vector ids, and for
+    ``set_mask`` the flags.  (``vec_norm`` is followed by the ``vec_dot`` it is made of.)"""
+
+    def __init__(self, A, rhs):
+        super().__init__(A, rhs)
+        self.trace = []
+
+
+def _recorded(name):
+    inner = getattr(DenseHandle, name)
+
+    def call(self, *args):
+        ints = args[0] if name == 'set_mask' else [a for a in args if isinstance(a, (int, np.integer))]
+        self.trace.append((name,) + tuple(int(a) for a in ints))
+        return inner(self, *args)
+    return call
+
+
+for _name in dir(DenseHandle):
+    if _name.startswith(('vec_', 'bvec_')) or _name == 'set_mask':
+        setattr(RecordingHandle, _name, _recorded(_name))
+
 N = 40
+
+
+def _x_start(warm):
+    return np.linspace(1.0, 2.0, N) * (1 - 0.5j) if warm else np.zeros(N, dtype=complex)
 
 
 @pytest.fixture(scope="module")
@@ -288,6 +315,101 @@ def test_negative_maxiter_is_not_a_failed_preconditioner(problem, name):
     var.exit_message = "DIVERGED"
     solver._krylov_exit_message(var, -1, True)
     assert var.exit_message == "DIVERGED (returned field is zero)"
+
+
+# --------------------------------------------------------------------------- the primitive calls of either path
+# Recorded from the drivers as they stood before the iteration was written once (``_bicgstab_device`` / ``_cgs_device`` on
+# ``vec_*``, their batched restatements on ``bvec_*``), on ``RecordingHandle`` with the arguments of the tests below:
+# the shared bodies must issue exactly these calls through either backend.  x0 = 0 / x0 != 0 differ in how r is formed.
+def _calls(prefix, text):
+    """'copy 1 9; set_mask 1 0 1' -> [(prefix + 'copy', 1, 9), ('set_mask', 1, 0, 1)]"""
+    return [(w[0] if w[0] == 'set_mask' else prefix + w[0],) + tuple(int(i) for i in w[1:])
+            for w in (c.split() for c in text.split(';'))]
+
+
+BICGSTAB_ITERATIONS = (     # (norm: followed by the dot it is made of)
+    "norm 1; dot 1 1; dot 2 1; copy 3 1; copy 7 3; amatvec 4 7; dot 2 4; axpy 1 4; copy 5 1; norm 5; dot 5 5; copy 8 5;"
+    "amatvec 6 8; dot 6 5; dot 6 6; axpy 0 7; axpy 0 8; axpy 1 6; amatvec 10 0; copy 11 9; axpy 11 10; norm 11; dot 11 11;"
+    "norm 1; dot 1 1; dot 2 1; axpy 3 4; scale 3; axpy 3 1; copy 7 3; amatvec 4 7; dot 2 4; axpy 1 4; copy 5 1; norm 5; dot 5 5;"
+    "copy 8 5; amatvec 6 8; dot 6 5; dot 6 6; axpy 0 7; axpy 0 8; axpy 1 6; amatvec 10 0; copy 11 9; axpy 11 10; norm 11;"
+    "dot 11 11; get 0")
+CGS_ITERATIONS = (
+    "norm 1; dot 1 1; dot 2 1; copy 3 1; copy 4 1; copy 6 3; amatvec 7 6; dot 2 7; copy 5 4; axpy 5 7; copy 8 4; axpy 8 5;"
+    "copy 9 8; axpy 0 9; amatvec 11 0; copy 1 10; axpy 1 11; norm 1; dot 1 1;"
+    "norm 1; dot 1 1; dot 2 1; copy 4 1; axpy 4 5; scale 3; axpy 3 5; scale 3; axpy 3 4; copy 6 3; amatvec 7 6; dot 2 7;"
+    "copy 5 4; axpy 5 7; copy 8 4; axpy 8 5; copy 9 8; axpy 0 9; amatvec 11 0; copy 1 10; axpy 1 11; norm 1; dot 1 1; get 0")
+SINGLE_TRACES = {           # (method, x0 != 0)
+    ('bicgstab', False): "alloc 12; set 9; set 0; norm 9; dot 9 9; copy 1 9; copy 2 1;" + BICGSTAB_ITERATIONS,
+    ('bicgstab', True): "alloc 12; set 9; set 0; norm 9; dot 9 9; amatvec 10 0; copy 1 9; axpy 1 10; copy 2 1;"
+                        + BICGSTAB_ITERATIONS,
+    ('cgs', False): "alloc 12; set 10; set 0; norm 10; dot 10 10; copy 1 10; copy 2 1;" + CGS_ITERATIONS,
+    ('cgs', True): "alloc 12; set 10; set 0; norm 10; dot 10 10; amatvec 11 0; copy 1 10; axpy 1 11; copy 2 1;" + CGS_ITERATIONS}
+BATCHED_TRACES = {
+    'bicgstab':
+        "alloc 12; set_mask 1 1 1; zero 0; set_mask 1 0 1; copy 9 -1; dot 9 9; copy 1 9; copy 2 1;"
+        "dot 1 1; dot 2 1; copy 3 1; copy 7 3; amatvec 4 7; dot 2 4; axpy 1 4; copy 5 1; dot 5 5; axpy 0 7; copy 8 5;"
+        "amatvec 6 8; dot 6 5; dot 6 6; axpy 0 8; axpy 1 6; amatvec 10 0; copy 11 9; axpy 11 10; dot 11 11;"
+        "dot 1 1; dot 2 1; axpy 3 4; scale 3; axpy 3 1; copy 7 3; amatvec 4 7; dot 2 4; axpy 1 4; copy 5 1; dot 5 5; axpy 0 7;"
+        "copy 8 5; amatvec 6 8; dot 6 5; dot 6 6; axpy 0 8; axpy 1 6; amatvec 10 0; copy 11 9; axpy 11 10; dot 11 11",
+    'cgs':
+        "alloc 12; set_mask 1 1 1; zero 0; set_mask 1 0 1; copy 10 -1; dot 10 10; copy 1 10; copy 2 1;"
+        "dot 1 1; dot 2 1; copy 3 1; copy 4 1; copy 6 3; amatvec 7 6; dot 2 7; copy 5 4; axpy 5 7; copy 8 4; axpy 8 5; copy 9 8;"
+        "axpy 0 9; amatvec 11 0; copy 1 10; axpy 1 11; dot 1 1;"
+        "dot 1 1; dot 2 1; copy 4 1; axpy 4 5; scale 3; axpy 3 5; scale 3; axpy 3 4; copy 6 3; amatvec 7 6; dot 2 7; copy 5 4;"
+        "axpy 5 7; copy 8 4; axpy 8 5; copy 9 8; axpy 0 9; amatvec 11 0; copy 1 10; axpy 1 11; dot 1 1"}
+BATCHED_MASK_CALLS = 2
+
+
+@pytest.mark.parametrize("warm", [False, True])
+@pytest.mark.parametrize("identity", [False, True])
+@pytest.mark.parametrize("name", ['bicgstab', 'cgs'])
+def test_single_path_call_trace(problem, name, identity, warm):
+    """A single solve issues the ``vec_*`` calls it always has, in their order, and nothing of the batched machinery."""
+    A, rhs = problem
+    dev = RecordingHandle(A, rhs[0][None, :])
+    its = []
+    _, code = DRIVERS[name][0](dev, rhs[0], _x_start(warm), rtol=RTOL, maxiter=2, atol=1e-30,
+                               psolve=(lambda s, d: dev.vec_copy(d, s)) if identity else None, callback=its.append)
+    assert code == 2 and len(its) == 2
+    assert dev.trace == _calls('vec_', SINGLE_TRACES[name, warm])
+    assert not [c for c in dev.trace if c[0].startswith('bvec_') or c[0] == 'set_mask'] and dev.mask_calls == 0
+
+
+@pytest.mark.parametrize("identity", [False, True])
+@pytest.mark.parametrize("name", ['bicgstab', 'cgs'])
+def test_batched_path_call_trace(problem, name, identity):
+    """A batched solve issues the ``bvec_*`` calls and writes the masks it always has, and no ``vec_*``."""
+    A, rhs = problem
+    dev = RecordingHandle(A, rhs[:3])
+
+    def psolve(src, dst, mask):
+        dev.bvec_copy(dst, src)
+        return []
+    res = [[] for _ in range(3)]
+    codes = DRIVERS[name][1](dev, 3, rtol=RTOL, maxiter=2, atol=1e-30, psolve=psolve if identity else None,
+                             callbacks=[r.append for r in res], active=[1, 0, 1])
+    assert codes == [2, 0, 2] and [len(r) for r in res] == [2, 0, 2]
+    assert dev.trace == _calls('bvec_', BATCHED_TRACES[name])
+    assert not [c for c in dev.trace if c[0].startswith('vec_')]
+    assert dev.mask_calls <= BATCHED_MASK_CALLS
+
+
+@pytest.mark.parametrize("name", ['bicgstab', 'cgs'])
+def test_single_driver_warm_start(problem, name):
+    """x0 != 0 (r = b - A x0): started from the iterate of a 3-iteration run, the driver reaches the solution of the cold
+    run in fewer iterations."""
+    A, rhs = problem
+    single = DRIVERS[name][0]
+    cold, code, its_cold = _alone(single, A, rhs[0])
+    assert code == 0
+    dev = DenseHandle(A, rhs[0][None, :])
+    x3, code = single(dev, rhs[0], np.zeros(N, dtype=complex), rtol=RTOL, maxiter=3, atol=1e-30, psolve=None, callback=None)
+    assert code == 3 and np.any(x3)
+    its = []
+    x, code = single(DenseHandle(A, rhs[0][None, :]), rhs[0], x3, rtol=RTOL, maxiter=100, atol=1e-30, psolve=None,
+                     callback=its.append)
+    assert code == 0 and len(its) < len(its_cold)
+    np.testing.assert_allclose(x, cold, rtol=0, atol=1e-10 * np.abs(cold).max())
 
 
 # --------------------------------------------------------------------------- workspace estimate
