@@ -56,6 +56,44 @@ class TensorMesh:
 _TensorMesh = TensorMesh
 
 
+def same_grid(a, b):
+    """Whether two meshes are the same grid: the same object, or three width arrays and an origin that are equal element for
+    element (a width that differs in its last bit makes another grid: results are compared bit for bit)."""
+    if a is b:
+        return True
+    return all(np.array_equal(ha, hb) for ha, hb in zip(a.h, b.h)) and np.array_equal(a.origin, b.origin)
+
+
+def distinct_grids(grids):
+    """``(distinct, index)`` of a sequence of meshes: the distinct grids (``same_grid``) in order of first appearance -- the
+    first object that stands for each --, and per entry the position of its grid among them."""
+    distinct, index = [], []
+    for g in grids:
+        hit = [k for k, d in enumerate(distinct) if same_grid(d, g)]
+        if not hit:
+            distinct.append(g)
+        index.append(hit[0] if hit else len(distinct) - 1)
+    return distinct, index
+
+
+def frequency_grids(grid, n_freq, model_grid, who):
+    """The computational grid of every entry of a survey's ``freqs`` from the ``grid`` argument of ``who``: a mesh stands for all
+    of them; a list or tuple holds one mesh per entry (repeats allowed) and needs ``model_grid``, the grid the model lives on --
+    the cells of different computational grids have nothing else in common.  ``ValueError`` otherwise; no device call."""
+    if not isinstance(grid, (list, tuple)):
+        return [grid] * int(n_freq)
+    bad = [type(g).__name__ for g in grid if not all(hasattr(g, a) for a in ('h', 'origin', 'vnC'))]
+    if bad:
+        raise ValueError(f"{who}: a sequence for `grid` must hold one TensorMesh per entry of `freqs`; it holds a {bad[0]}.")
+    if len(grid) != int(n_freq):
+        raise ValueError(f"{who}: a sequence for `grid` must hold one TensorMesh per entry of `freqs` ({int(n_freq)}); it holds "
+                         f"{len(grid)}.")
+    if model_grid is None:
+        raise ValueError(f"{who}: a computational grid per frequency needs `model_grid`, the grid `model` lives on (the products of "
+                         "different frequencies have no cells in common otherwise).")
+    return list(grid)
+
+
 def stretched_widths(ncore, npad, width, factor):
     """Widths [w f^npad .. w f, w x ncore, w f .. w f^npad] used by the synthetic
     benchmark grids."""

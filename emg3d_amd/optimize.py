@@ -27,14 +27,15 @@ gives the products in the model's own parameter.
 What the four entry points share is written once: the argument checks (``_check_arguments``), the receivers (``_receivers``), the
 residual / adjoint source of one system (``_adjoint_source``, the reference's rule included), the flags of a short chunk
 (``_first``) and, for the two Jacobians, ``_JacobianBase``; the per-dtype handles of the survey-level entry points, re-targeted
-from frequency to frequency, are a ``solver.FrequencyHandles`` (``DeviceMG.retarget``).
+from frequency to frequency, are a ``solver.FrequencyHandles`` (``DeviceMG.retarget``) -- for ``SurveyJacobian`` one per distinct
+computational grid, a ``solver.GridHandles``.
 """
 import contextlib
 import time
 
 import numpy as np
 
-from . import _lib, fields, maps, models, solver
+from . import _lib, fields, maps, meshes, models, solver
 
 
 def misfit(synthetic, observed, weights):
@@ -408,6 +409,26 @@ def _perturbations(v, vnC):
     return out, single
 
 
+def _parked_slots(grid_index, dtypes, n_chunks):
+    """Where ``SurveyJacobian`` parks its forward fields.  A handle is a (distinct grid, dtype) pair, ``(grid_index[j],
+    dtypes[j].str)`` for frequency ``j``; every frequency owns ``n_chunks`` consecutive batched vectors of its handle.  Returns
+    ``(slot, nslots, first)``: ``slot[j]`` the first vector of frequency ``j``, numbered per handle in the order of the
+    frequencies; ``nslots[handle]`` the vectors the handle needs; ``first[handle]`` the first frequency on it."""
+    slot, nslots, first = {}, {}, {}
+    for j, (k, dtype) in enumerate(zip(grid_index, dtypes)):
+        key = (int(k), np.dtype(dtype).str)
+        first.setdefault(key, j)
+        slot[j] = nslots.get(key, 0)
+        nslots[key] = slot[j] + int(n_chunks)
+    return slot, nslots, first
+
+
+def _parked_bytes(nslots, nb, nE):
+    """The bytes of the parked forward fields: the sum over the handles of ``nslots`` (``_parked_slots``) of ``slots * nb *
+    nE[k] * itemsize`` -- ``nb`` systems per batched vector, ``nE[k]`` the edges of distinct grid ``k``."""
+    return sum(int(n) * int(nb) * int(nE[k]) * np.dtype(dtype).itemsize for (k, dtype), n in nslots.items())
+
+
 class _JacobianBase:
     """What ``Jacobian`` and ``SurveyJacobian`` share: the ``with`` protocol, the test for the open state (``self._held``: the
     handle resp. the handles, None when closed) and the two steps every product is made of."""
@@ -434,7 +455,7 @@ class _JacobianBase:
 
     def _chain_factors(self):
         if self._chain is None:
-            dev = next(iter(self._held)) if isinstance(self._held, solver.FrequencyHandles) else self._held
+            dev = next(iter(self._held)) if isinstance(self._held, solver.GridHandles) else self._held
             fmap = self.model.map
             dx = fmap.chain_factor(dev.get_sigma(0))
             dy = fmap.chain_factor(dev.get_sigma(1)) if self.model.case in (1, 3) else dx
@@ -454,9 +475,11 @@ class _JacobianBase:
         out = tuple(dc * g for dc, g in zip(d, g3))
         return out if components else (out[0] + out[1]) + out[2]
 
-    def _solve(self, dev, freq, n):
-        """Solve the systems 0 .. n-1 of the handle (at ``freq``) for the sources they hold; the fields stay in HBM."""
-        _, infos = solver.solve_sources(self.grid, None, None, freq, handle=dev, resident=n, download=False, **self._opts)
+    def _solve(self, dev, freq, n, grid=None):
+        """Solve the systems 0 .. n-1 of the handle (at ``freq``) for the sources they hold; the fields stay in HBM.  ``grid``: the
+        handle's own (default: ``self.grid``)."""
+        _, infos = solver.solve_sources(self.grid if grid is None else grid, None, None, freq, handle=dev, resident=n,
+                                        download=False, **self._opts)
         return infos
 
     def _data(self, dev, smu0):
@@ -710,7 +733,19 @@ class SurveyJacobian(_JacobianBase):
     ``jtvec(w, mapped=True) = Q (.) A^T (F (.) J^T w)`` of that shape (``maps.regrid_factors``; ``A^T`` applied to the accumulators
     on the device, ``DeviceMG.grad_acc_get_model``: one ``nM``-sized array per frequency and direction comes back), ``partial`` the
     per-frequency results on the model grid in the ``G_f`` sign convention.  The two are an adjoint pair as without a model grid.
-    ``mapped=False`` (the default) raises ``ValueError`` there: the conductivity on the model grid is not what the solves see."""
+    ``mapped=False`` (the default) raises ``ValueError`` there: the conductivity on the model grid is not what the solves see.
+
+    A COMPUTATIONAL GRID PER FREQUENCY (the reference's ``gridding='dict'`` with the caller's grids, emg3d/simulations.py:92-117):
+    with ``model_grid``, ``grid`` may be a list or tuple with one ``TensorMesh`` per entry of ``freqs``, repeats allowed
+    (``ValueError`` without ``model_grid``, for another length or for an entry that is no mesh, before any device call).  Entries
+    that are the same object or equal in every width and the origin are one grid (``meshes.same_grid``): ``grids`` holds the mesh
+    of every entry, ``grid_index`` its position among the distinct grids in order of first appearance, ``grid`` what the caller
+    passed.  There is one handle per distinct (grid, dtype), re-targeted among the entries it serves (``solver.GridHandles``);
+    the model is regridded, the factors ``F`` are read back and a ``jvec`` right-hand side is formed once per distinct grid; the
+    parked vectors are numbered per handle.  Every product of entry ``j`` is bit for bit that of ``SurveyJacobian(grids[j],
+    model, sources, [freqs[j]], rec, model_grid=model_grid, ...)``, the sums over the frequencies are formed on the host in the
+    order of ``freqs`` as always, and rows from any grid are model-grid sized: one ``RowStore`` holds them all.  A sequence that
+    repeats one grid is the single-mesh call."""
 
     def __init__(self, grid, model, sources, freqs, rec, batch=8, receiver_interpolation='cubic', adjoint='exact', electric=True,
                  strength=0, device=0, model_grid=None, **solver_opts):
@@ -724,13 +759,15 @@ class SurveyJacobian(_JacobianBase):
             raise ValueError("SurveyJacobian: no sources or no frequencies.")
         self.grid, self.model = grid, model
         self.n_src, self.n_freq = len(self.sources), len(self.freqs)
+        self.grids = meshes.frequency_grids(grid, self.n_freq, model_grid, 'SurveyJacobian')
+        self.grid_index = meshes.distinct_grids(self.grids)[1]
         self.n_rec, self.rec = _receivers(rec)
         self.receiver_interpolation = receiver_interpolation
         self.adjoint, self.electric = adjoint, bool(electric)
         self.batch, self.strength, self.device = int(batch), strength, device
         self._opts = {k: v for k, v in solver_opts.items() if k not in ('return_info', 'sslsolver')}
         self._specs = [fields.FrequencySpec(f) for f in self.freqs]
-        self._vnC = tuple(int(n) for n in grid.vnC)
+        self._vnC = tuple(int(n) for n in self.grids[0].vnC)    # (the cells of the one grid there is without `model_grid`)
         self._vnM = self._vnC if model_grid is None else tuple(int(n) for n in model_grid.vnC)     # the cells of `v` and `J^T w`
         self._nb = min(self.batch, self.n_src)
         self._chunks = [(i0, min(self._nb, self.n_src - i0)) for i0 in range(0, self.n_src, self._nb)]
@@ -756,22 +793,26 @@ class SurveyJacobian(_JacobianBase):
             raise ValueError(f"SurveyJacobian: `model` must live on `model_grid` {tuple(self.model_grid.vnC)}; it has "
                              f"{tuple(model.vnC)} cells.")
 
-    def _on_grid(self, model):
-        """``model`` on the computational grid."""
-        return model if self.model_grid is None else model.interpolate2grid(self.model_grid, self.grid)
+    # With a computational grid per frequency (``grid`` a sequence) all of this holds per DISTINCT grid: the model is regridded to
+    # each (``GridHandles.on_grids``), F comes from a handle of that grid, Q from the model alone, and ``jvec`` forms one right-hand
+    # side per distinct grid and product.  What comes back is model-grid sized whatever grid a frequency was solved on.
 
     def _refresh_factors(self, handles):
-        dev = next(iter(handles))
+        """``_regrid_FQ[k]``: the factors of distinct grid ``k``, F from the conductivity one of its handles holds."""
         case = self.model.case
-        sx = dev.get_sigma(0)
-        sigma = (sx, dev.get_sigma(1) if case in (1, 3) else sx, dev.get_sigma(2) if case in (2, 3) else sx)
-        self._regrid_FQ = maps.regrid_factors(self.model, sigma)
-        handles.set_regrid_factors(*self._regrid_FQ)
+        self._regrid_FQ = []
+        for k, member in enumerate(handles.members):
+            dev = next(iter(member))
+            sx = dev.get_sigma(0)
+            sigma = (sx, dev.get_sigma(1) if case in (1, 3) else sx, dev.get_sigma(2) if case in (2, 3) else sx)
+            self._regrid_FQ.append(maps.regrid_factors(self.model, sigma))
+            handles.set_regrid_factors(k, *self._regrid_FQ[k])
 
-    def _to_grid(self, vec):
-        """(v_x, v_y, v_z), F-raveled perturbations of p on the model grid (entries may be None) -> of sigma on ``grid``; entries
-        that are the same array with the same factors stay one array."""
-        F, Q = self._regrid_FQ
+    def _to_grid(self, vec, k):
+        """(v_x, v_y, v_z), F-raveled perturbations of p on the model grid (entries may be None) -> of sigma on distinct grid
+        ``k``; entries that are the same array with the same factors stay one array."""
+        F, Q = self._regrid_FQ[k]
+        grid = self._held.distinct[k]
         out, done = [], []
         for c, v in enumerate(vec):
             hit = [r for v0, c0, r in done if v0 is v and F[c0] is F[c] and Q[c0] is Q[c]]
@@ -779,10 +820,20 @@ class SurveyJacobian(_JacobianBase):
                 out.append(None if v is None else hit[0])
                 continue
             vm = np.asfortranarray(Q[c] * v.reshape(self._vnM, order='F'))
-            r = np.ascontiguousarray((F[c] * maps.grid2grid(self.model_grid, vm, self.grid, 'volume')).ravel(order='F'))
+            r = np.ascontiguousarray((F[c] * maps.grid2grid(self.model_grid, vm, grid, 'volume')).ravel(order='F'))
             done.append((v, c, r))
             out.append(r)
         return tuple(out)
+
+    def _right_hand_sides(self, vec, mapped):
+        """The perturbation of a product as the solves of every distinct grid take it, formed once per distinct grid: ``vecs[k]``
+        for ``_sweep``."""
+        if not mapped:
+            return [vec]
+        handles = self._require_open()
+        if self.model_grid is None:
+            return [self._to_sigma(vec)]
+        return [self._to_grid(vec, k) for k in range(len(handles.distinct))]
 
     def _mapped_or_refuse(self, mapped):
         mapped = _mapped(mapped)
@@ -796,18 +847,12 @@ class SurveyJacobian(_JacobianBase):
         if self._held is not None:
             return self
         ns, nf, nb = self.n_src, self.n_freq, self._nb
-        parts = models.model_parts(self.grid, self._on_grid(self.model), raw=True)
-        handles = solver.FrequencyHandles(self.grid, parts, self.device, nsys=nb)
-        self._slot, first, nslots = {}, {}, {}
-        for j, spec in enumerate(self._specs):
-            key = spec.dtype.str
-            first.setdefault(key, spec)
-            self._slot[j] = nslots.get(key, 0)              # first batched vector of frequency j on its handle
-            nslots[key] = self._slot[j] + len(self._chunks)
+        handles = solver.GridHandles(self.grids, self.model, self.device, nsys=nb, model_grid=self.model_grid)
+        self._slot, nslots, first = _parked_slots(self.grid_index, [spec.dtype for spec in self._specs], len(self._chunks))
         try:
-            devs = {key: handles.target(spec) for key, spec in first.items()}
+            devs = {key: handles.target(j, self._specs[j]) for key, j in first.items()}
             # the parked forward fields: one batched vector per (frequency, chunk), sized and allocated before the first solve
-            need = sum(nslots[key] * nb * dev.nE * dev.dtype.itemsize for key, dev in devs.items())
+            need = _parked_bytes(nslots, nb, [g.nE for g in handles.distinct])
             mi = _lib.mem_info(self.device)
             free = mi['free'] + mi['pooled_on_device']
             if need >= 0.92 * free:
@@ -831,12 +876,12 @@ class SurveyJacobian(_JacobianBase):
         self.synthetic = np.full((ns, nf, self.n_rec), np.nan, dtype=self.dtype)
         self.forward_info = [[None] * nf for _ in range(ns)]
         for j, spec in enumerate(self._specs):
-            dev, smu0 = handles.target(spec), spec.smu0
+            dev, smu0 = handles.target(j, spec), spec.smu0
             for c, (i0, n) in enumerate(self._chunks):
                 for b in range(n):
                     dev.select(b)
                     dev.set_source(self.sources[i0 + b], smu0, strength=self.strength)
-                infos = self._solve(dev, self.freqs[j], n)
+                infos = self._solve(dev, self.freqs[j], n, self.grids[j])
                 for b in range(n):
                     self.forward_info[i0 + b][j] = infos[b]
                     dev.select(b)
@@ -851,7 +896,7 @@ class SurveyJacobian(_JacobianBase):
 
     def set_model(self, model):
         """Another model on the same grid, in the same anisotropy case (any property map), on the open handles -- what an
-        inversion does every iteration and every trial step: ``FrequencyHandles.set_model`` (the conductivities, eta, coarse
+        inversion does every iteration and every trial step: ``GridHandles.set_model`` (the conductivities, eta, coarse
         models and line factorisations of every handle recomputed in HBM), all pairs solved forward again into the SAME parked
         vectors, ``synthetic`` and ``forward_info`` anew.  Every product is then bit for bit that of a new ``SurveyJacobian`` on
         ``model``; no handle, hierarchy, launch graph or parked vector is created (``device_bytes`` stays).  With ``model_grid``
@@ -859,7 +904,7 @@ class SurveyJacobian(_JacobianBase):
         handles = self._require_open()
         _check_arguments('Jacobian', model, self.adjoint, self.electric, self.receiver_interpolation)
         self._check_model_grid(model)
-        handles.set_model(self._on_grid(model))
+        handles.set_model(model)
         self.model = model
         self._forward(handles)
         return self
@@ -923,28 +968,29 @@ class SurveyJacobian(_JacobianBase):
             if not _adjoint_source(dev, self.rec, smu0, cw[b], method='cubic', exact=False, electric=self.electric):
                 dev.vec_scale(dev.SFIELD, 0.0)
 
-    def _sweep(self, vec, w, weights, components):
+    def _sweep(self, vecs, w, weights, components):
         """Frequency by frequency and chunk by chunk: [J v: source, solve, data] then [J^T w: source, solve, accumulate], the rows
-        ``w`` given or ``weights * (J v)``."""
+        ``w`` given or ``weights * (J v)``.  ``vecs``: the perturbation per distinct grid (``_right_hand_sides``), or None."""
         handles = self._require_open()
         ns, nf, nb = self.n_src, self.n_freq, self._nb
         adj = w is not None or weights is not None
-        dd = np.full((ns, nf, self.n_rec), np.nan, dtype=self.dtype) if vec is not None else None
+        dd = np.full((ns, nf, self.n_rec), np.nan, dtype=self.dtype) if vecs is not None else None
         jinfo = [[None] * nf for _ in range(ns)]
         binfo = [[None] * nf for _ in range(ns)]
         nacc = 3 if components else 1
         on_model = self.model_grid is not None          # read back through A^T: G_f on the model grid, factors applied
         partial = np.zeros((nacc, nf) + self._vnM[::-1]).transpose(0, 1, 4, 3, 2) if adj else None     # every G_f F-ordered
         for j, spec in enumerate(self._specs):
-            dev, smu0 = handles.target(spec), spec.smu0
+            dev, smu0 = handles.target(j, spec), spec.smu0
             real = dev.dtype.kind != 'c'
+            vec = None if vecs is None else vecs[self.grid_index[j]]
             if adj:
                 dev.grad_acc_reset(components)
             for c, (i0, n) in enumerate(self._chunks):
                 slot = self._slot[j] + c
                 if vec is not None:
                     dev.jvec_source_b(slot, smu0, *vec, _first(n, nb))
-                    infos = self._solve(dev, self.freqs[j], n)
+                    infos = self._solve(dev, self.freqs[j], n, self.grids[j])
                     for b in range(n):
                         jinfo[i0 + b][j] = infos[b]
                         dev.select(b)
@@ -959,7 +1005,7 @@ class SurveyJacobian(_JacobianBase):
                 if not live.any():
                     continue
                 self._adjoint_sources(dev, smu0, cw, n)
-                infos = self._solve(dev, self.freqs[j], n)
+                infos = self._solve(dev, self.freqs[j], n, self.grids[j])
                 use = _first(0, nb)
                 use[:n] = live
                 for b in range(n):
@@ -996,10 +1042,7 @@ class SurveyJacobian(_JacobianBase):
         ``v`` perturbs the model's own property."""
         mapped = self._mapped_or_refuse(mapped)
         vec = self._perturbation(v)
-        if mapped:
-            self._require_open()
-            vec = self._to_sigma(vec) if self.model_grid is None else self._to_grid(vec)
-        dd, self.info, _, _ = self._sweep(vec, None, None, False)
+        dd, self.info, _, _ = self._sweep(self._right_hand_sides(vec, mapped), None, None, False)
         return dd
 
     def jtvec(self, w, components=False, mapped=False):
@@ -1019,11 +1062,8 @@ class SurveyJacobian(_JacobianBase):
         mapped = self._mapped_or_refuse(mapped)
         vec = self._perturbation(v)
         weights = self._weights(weights)
-        if mapped:
-            self._require_open()
-            vec = self._to_sigma(vec) if self.model_grid is None else self._to_grid(vec)
         three = components or (mapped and self.model.case != 0)
-        _, self.jvec_info, partial, self.info = self._sweep(vec, None, weights, three)
+        _, self.jvec_info, partial, self.info = self._sweep(self._right_hand_sides(vec, mapped), None, weights, three)
         return self._mapped_result(partial, components, mapped)
 
     # ---- diag(J^H W J) ------------------------------------------------------------------------------------------------
@@ -1073,7 +1113,7 @@ class SurveyJacobian(_JacobianBase):
         partial = np.zeros((nacc, nf) + self._vnC[::-1]).transpose(0, 1, 4, 3, 2)       # every P_f F-ordered
         sinfo = [[None] * nr for _ in range(nf)]
         for j, spec in enumerate(self._specs):
-            dev, smu0 = handles.target(spec), spec.smu0
+            dev, smu0 = handles.target(j, spec), spec.smu0
             dev.grad_acc_reset(components)
             wanted = np.any(weights[:, j, :] != 0, axis=0)          # receivers with a datum at this frequency
             for r0 in range(0, nr, nb):
@@ -1085,7 +1125,7 @@ class SurveyJacobian(_JacobianBase):
                 for b in np.flatnonzero(live):
                     cw[b, r0 + b] = 1
                 self._adjoint_sources(dev, smu0, cw, n)
-                infos = self._solve(dev, self.freqs[j], n)
+                infos = self._solve(dev, self.freqs[j], n, self.grids[j])
                 use_adj = _first(0, nb)
                 use_adj[:n] = live
                 for b in np.flatnonzero(live):
@@ -1177,7 +1217,7 @@ class SurveyJacobian(_JacobianBase):
         nout = 3 if components else 1
         out = [np.empty((ns, nk) + self._vnM[::-1], dtype=spec.dtype).transpose(0, 1, 4, 3, 2) for _ in range(nout)]    # rows F-ordered
         chain = self._chain_factors() if mapped and not on_model else None
-        dev, smu0 = handles.target(spec), spec.smu0
+        dev, smu0 = handles.target(j, spec), spec.smu0
         real = dev.dtype.kind != 'c'
         both = not real and solves == 1         # both parts from the solve for e_d
         infos = [[None] * nk for _ in range(1 if real else 2)]
@@ -1188,7 +1228,7 @@ class SurveyJacobian(_JacobianBase):
                 for b in range(n):
                     w[b, recs[k0 + b]] = unit
                 self._adjoint_sources(dev, smu0, np.conj(w), n)
-                infos[part][k0:k0 + n] = self._solve(dev, self.freqs[j], n)[:n]
+                infos[part][k0:k0 + n] = self._solve(dev, self.freqs[j], n, self.grids[j])[:n]
                 # (plane of the product, views into the rows it fills)
                 dests = [('real', out if real else [(o.real, o.imag)[part] for o in out])]
                 if both:
@@ -1273,7 +1313,7 @@ class SurveyJacobian(_JacobianBase):
                 recs = [r for r in range(self.n_rec) if sel[:, j, r].any()]
                 if not recs:
                     continue
-                dev, smu0 = handles.target(spec), spec.smu0
+                dev, smu0 = handles.target(j, spec), spec.smu0
                 got = {r: [None, None] for r in recs}
                 both = not real[j] and solves == 1      # both parts from the solve for e_d, filled by the sensitivity kernel
                 for k0 in range(0, len(recs), nb):
@@ -1283,7 +1323,7 @@ class SurveyJacobian(_JacobianBase):
                         for b in range(n):
                             w[b, recs[k0 + b]] = unit
                         self._adjoint_sources(dev, smu0, np.conj(w), n)
-                        infos = self._solve(dev, self.freqs[j], n)
+                        infos = self._solve(dev, self.freqs[j], n, self.grids[j])
                         for b in range(n):
                             got[recs[k0 + b]][part] = infos[b]
                         for c, (i0, nsrc) in enumerate(self._chunks):

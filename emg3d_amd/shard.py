@@ -82,10 +82,12 @@ def solve_frequencies(grid, model, src, freqs, device=0, strength=0, concurrent=
         return [one(f, handles) for f in freqs]
 
 
-def solve_survey(grid, model, sources, freqs, rec, device=0, strength=0, batch=8, return_fields=False, **solver_opts):
+def solve_survey(grid, model, sources, freqs, rec, device=0, strength=0, batch=8, return_fields=False, model_grid=None,
+                 **solver_opts):
     """A survey's forward modelling on ONE GPU: every source of ``sources`` at every frequency of ``freqs`` (the
-    (source, frequency) loop of ``Simulation.compute``, emg3d/simulations.py:821-878, with ``gridding='same'``) and
-    the responses at the receivers ``rec = (x, y, z, azimuth, dip)``.  Frequencies are independent handles
+    (source, frequency) loop of ``Simulation.compute``, emg3d/simulations.py:821-878, with ``gridding='same'``, or with
+    ``model_grid`` its ``'single'`` and, for the caller's grids, ``'dict'``) and the responses at the receivers
+    ``rec = (x, y, z, azimuth, dip)``.  Frequencies are independent handles
     (across GPUs: give every rank ``my_frequencies(freqs, rank, world)`` and gather the responses with
     ``gather_fields``); the sources of one frequency share its operator and go through the SAME launches, ``batch``
     at a time (``solver.solve_sources``: bit for bit the results of one solve per source).  Nothing nE-sized
@@ -93,25 +95,32 @@ def solve_survey(grid, model, sources, freqs, rec, device=0, strength=0, batch=8
 
     Returns ``(responses, infos)`` -- ``responses[i_src, i_freq, i_rec]`` complex (or float for Laplace-domain
     frequencies), ``infos[i_src][i_freq]`` the ``info_dict`` of that solve -- and the fields ``[i_src][i_freq]`` if
-    ``return_fields``."""
-    from emg3d_amd import solver
+    ``return_fields``.
+
+    ``model_grid`` (a ``TensorMesh``; default None: ``model`` lives on ``grid``): ``model`` lives on ``model_grid`` and reaches the
+    computational grid through ``model.interpolate2grid(model_grid, grid)``.  ``grid`` may then be a list or tuple with one
+    ``TensorMesh`` per entry of ``freqs``, repeats allowed (``ValueError`` without ``model_grid``, or for another length): the
+    model is regridded once per distinct grid (``meshes.same_grid``), there is one handle per distinct (grid, dtype, systems per
+    launch) (``solver.GridHandles``), and column ``j`` of every result is bit for bit that of ``solve_survey(grid[j],
+    model.interpolate2grid(model_grid, grid[j]), sources, [freqs[j]], rec)``; ``return_fields`` gives every field on its own
+    grid."""
+    from emg3d_amd import fields, meshes, solver
     freqs = [float(f) for f in freqs]
     ns, nf = len(sources), len(freqs)
+    grids = meshes.frequency_grids(grid, nf, model_grid, 'solve_survey')
     resp = None
     infos = [[None] * nf for _ in range(ns)]
     efs = [[None] * nf for _ in range(ns)] if return_fields else None
     # one handle per (dtype, systems per launch), re-targeted from frequency to frequency (DeviceMG.retarget: eta, coarse
     # models and line factorisations are recomputed in HBM, hierarchy / buffers / launch graphs stay); bit for bit the
     # results of solver.solve_sources with a handle of its own
-    from emg3d_amd import fields, models
-    parts = models.model_parts(grid, model, raw=True)
-    with solver.FrequencyHandles(grid, parts, device) as handles:
+    with solver.GridHandles(grids, model, device, model_grid=model_grid) as handles:
         for jf, f in enumerate(freqs):
             spec = fields.FrequencySpec(f)
             for i0 in range(0, ns, int(batch)):
                 chunk = list(sources[i0:i0 + int(batch)])
-                dev = handles.target(spec, key=(len(chunk),))
-                e, info, r = solver.solve_sources(grid, model, chunk, f, strength=strength, rec=rec, device=device,
+                dev = handles.target(jf, spec, key=(len(chunk),))
+                e, info, r = solver.solve_sources(grids[jf], None, chunk, f, strength=strength, rec=rec, device=device,
                                                   download=return_fields, handle=dev, **solver_opts)
                 if resp is None:
                     resp = np.zeros((ns, nf, r.shape[1]), dtype=np.result_type(r.dtype, np.float64))

@@ -30,7 +30,7 @@ import scipy.sparse.linalg as ssl
 from emg3d_amd import _lib, core, fields, meshes, models
 
 __all__ = ['solve', 'multigrid', 'krylov', 'smoothing', 'restriction', 'prolongation',
-           'residual', 'MGParameters', 'DeviceMG', 'FrequencyHandles']
+           'residual', 'MGParameters', 'DeviceMG', 'FrequencyHandles', 'GridHandles']
 
 ORDERINGS = {'lex': 0, 'colour': 1, 'color': 1}
 
@@ -1179,6 +1179,68 @@ class FrequencyHandles:
         for dev in self._handles.values():
             dev.close()
         self._handles = {}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class GridHandles:
+    """The handles of a loop over frequencies whose entries may each have a computational grid of their own: one
+    ``FrequencyHandles`` per DISTINCT grid of ``grids`` (``meshes.distinct_grids``; one mesh per entry of the loop), hence one
+    ``DeviceMG`` per distinct (grid, dtype) -- and optional extra ``key`` --, on which the entries of that grid are re-targeted
+    exactly as on a ``FrequencyHandles`` of their own.  ``members[k]`` are the handles of ``distinct[k]``, ``index[j]`` the ``k``
+    of entry ``j``.
+
+    ``model_grid=None``: ``model`` lives on the (then one) grid.  Otherwise it lives on ``model_grid`` and reaches every distinct
+    grid through ``model.interpolate2grid(model_grid, grid)``, once per distinct grid (``on_grids``)."""
+
+    def __init__(self, grids, model, device, nsys=1, bvecs=0, model_grid=None):
+        self.grids, self.device, self.model_grid = list(grids), device, model_grid
+        self.distinct, self.index = meshes.distinct_grids(self.grids)
+        self.members = [FrequencyHandles(g, models.model_parts(g, m, raw=True), device, nsys=nsys, bvecs=bvecs)
+                        for g, m in zip(self.distinct, self.on_grids(model))]
+
+    def on_grids(self, model):
+        """``model`` on every distinct grid."""
+        if self.model_grid is None:
+            return [model] * len(self.distinct)
+        return [model.interpolate2grid(self.model_grid, g) for g in self.distinct]
+
+    def target(self, j, spec, key=()):
+        """The handle of entry ``j`` for ``spec`` (``FrequencyHandles.target`` on the entry's grid), standing at its frequency."""
+        return self.members[self.index[j]].target(spec, key)
+
+    def set_model(self, model):
+        """Re-target every handle to ``model`` (regridded once per distinct grid; checked against ALL handles of all grids before
+        the first upload); handles created later are created from it."""
+        parts = [models.model_parts(g, m, raw=True) for g, m in zip(self.distinct, self.on_grids(model))]
+        for member, p in zip(self.members, parts):
+            for dev in member:
+                dev._model_arrays(member.grid, p)
+        for member, p in zip(self.members, parts):
+            for dev in member:
+                dev._set_parts(member.grid, p)
+            member.parts = p
+
+    def set_model_grid(self, model_grid):
+        """Link every open handle, and the handles created later, to the grid the model lives on."""
+        for member in self.members:
+            member.set_model_grid(model_grid)
+
+    def set_regrid_factors(self, k, F, Q):
+        """The factors of ``grad_acc(3)_get_model`` for the handles of ``distinct[k]``, open or created later (``F`` lives on that
+        grid)."""
+        self.members[k].set_regrid_factors(F, Q)
+
+    def __iter__(self):
+        return itertools.chain.from_iterable(self.members)
+
+    def close(self):
+        for member in self.members:
+            member.close()
 
     def __enter__(self):
         return self
