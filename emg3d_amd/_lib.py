@@ -22,7 +22,7 @@ c_double = ctypes.c_double
 c_dp = ctypes.POINTER(ctypes.c_double)
 
 # include/emg3d_hip.h: EMG3D_HIP_ABI_VERSION -- a library built from another header version is refused at load
-ABI_VERSION = 120
+ABI_VERSION = 121
 
 # name -> (restype, argtypes); mirrors include/emg3d_hip.h one to one.
 SIGNATURES = {
@@ -46,6 +46,7 @@ SIGNATURES = {
     "emg3d_prolongation": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int]),
     "emg3d_restrict_model": (c_int, [c_int, c_i64, c_i64, c_i64, c_vp, c_vp, c_int]),
     "emg3d_sweep_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, ctypes.c_char_p, ctypes.POINTER(c_i64)]),
+    "emg3d_sweep_scantab": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, ctypes.POINTER(c_i64)]),
     "emg3d_sweep_thm_zkeep": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, ctypes.POINTER(c_i64)]),
     "emg3d_sweep_fuse_plan": (c_int, [c_int, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, ctypes.POINTER(c_i64),
                                       ctypes.POINTER(c_i64), c_i64]),
@@ -278,11 +279,14 @@ def sweep_plan(vnC, direction, dtype=np.complex128, ordering='colour', nsys=1, c
     ``cu_count`` compute units (0: the current device) -- ``emg3d_sweep_plan``: shape logic only, runs without a GPU when
     ``cu_count`` > 0.  Returns the instantiation's name and the launch shape."""
     name = ctypes.create_string_buffer(64)
-    info = (c_i64 * 6)()
+    info, tab = (c_i64 * 6)(), (c_i64 * 4)()
+    check(load().emg3d_sweep_scantab(dtype_code(dtype), int(vnC[0]), int(vnC[1]), int(vnC[2]), int(direction),
+                                     1 if ordering == 'colour' else 0, int(nsys), int(cu_count), tab), "emg3d_sweep_scantab")
     check(load().emg3d_sweep_plan(dtype_code(dtype), int(vnC[0]), int(vnC[1]), int(vnC[2]), int(direction),
                                   1 if ordering == 'colour' else 0, int(nsys), int(cu_count), name, info), "emg3d_sweep_plan")
     return {"kernel": name.value.decode(), "lines_per_colour": info[0], "lines_per_wave": info[1], "rounds": info[2],
-            "factor_kind": info[3], "split": bool(info[4]), "big_offsets": bool(info[5])}
+            "factor_kind": info[3], "split": bool(info[4]), "big_offsets": bool(info[5]), "scan_table": bool(tab[0]),
+            "scan_table_bytes": tab[1]}
 
 
 def sweep_thm_zkeep(vnC, direction, dtype=np.complex128, ordering='colour', nsys=1, cu_count=0):

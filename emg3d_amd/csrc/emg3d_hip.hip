@@ -537,6 +537,18 @@ static int sweep_plan_impl(i64 nx, i64 ny, i64 nz, int dir, int order, int nsys,
     return 0;
 }
 
+// emg3d_sweep_scantab: the scan-table part of the same SweepPlan (sweep_scantab of sweep_plan.hpp) on a bare shape
+template <class T>
+static int scantab_impl(i64 nx, i64 ny, i64 nz, int dir, int order, int nsys, int cu_count, int64_t* info) {
+    SweepKnobs K;
+    if (cu_count > 0) K.simds = 4 * (i64)cu_count;
+    else sweep_device_knobs<T>(K, current_device());
+    K.order = order; K.nsys = nsys;
+    const SweepPlan p = plan_sweep(K, SweepShape{{nx, ny, nz}, (int)sizeof(T)}, dir - 1);
+    info[0] = p.scantab ? 1 : 0; info[1] = p.scantab_bytes; info[2] = p.seg; info[3] = K.scantab_max_threads();
+    return 0;
+}
+
 // emg3d_sweep_thm_zkeep: sweep_thm_zkeep of sweep_plan.hpp on a bare shape
 template <class T>
 static int thm_zkeep_impl(i64 nx, i64 ny, i64 nz, int dir, int order, int nsys, int cu_count, int64_t* info) {
@@ -955,6 +967,12 @@ int emg3d_sweep_plan(int dtype, int64_t nx, int64_t ny, int64_t nz, int dir, int
     if (nx < 2 || ny < 2 || nz < 2 || dir < 1 || dir > 3 || order < 0 || order > 1 || nsys < 1 || nsys > 64 || !name || !info) return -2;
     return dtype ? sweep_plan_impl<c128>(nx, ny, nz, dir, order, nsys, cu_count, name, info)
                  : sweep_plan_impl<double>(nx, ny, nz, dir, order, nsys, cu_count, name, info);
+}
+
+int emg3d_sweep_scantab(int dtype, int64_t nx, int64_t ny, int64_t nz, int dir, int order, int nsys, int cu_count, int64_t* info) {
+    if (nx < 2 || ny < 2 || nz < 2 || dir < 1 || dir > 3 || order < 0 || order > 1 || nsys < 1 || nsys > 64 || !info) return -2;
+    return dtype ? scantab_impl<c128>(nx, ny, nz, dir, order, nsys, cu_count, info)
+                 : scantab_impl<double>(nx, ny, nz, dir, order, nsys, cu_count, info);
 }
 
 int emg3d_sweep_thm_zkeep(int dtype, int64_t nx, int64_t ny, int64_t nz, int dir, int order, int nsys, int cu_count, int64_t* info) {

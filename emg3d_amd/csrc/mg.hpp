@@ -69,6 +69,10 @@ struct Level {
     // per-lane launch descriptors of the scan kernel's colour launches (LineArgs::qd; smooth_qpl.hpp DM): [direction][colour]
     void* qd[3][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
     unsigned qdn[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    // scan tables of the same launches (LineArgs::sm; smooth_qpl.hpp SM): [direction][colour]; they hold products of the factor, and
+    // are rewritten whenever it is recomputed
+    void* sm[3][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
+    unsigned smn[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
     // private slab copies of the fused smoothing calls (MG::ensure_fuse): [system][slab][nE], elements allocated
     T* fz[3] = {nullptr, nullptr, nullptr};
     i64 fz_n[3] = {0, 0, 0};
@@ -725,7 +729,7 @@ struct MG : emg3d_mg {
                 for (int c = 1; c < 3; ++c)
                     if (L.eta[c] != L.eta[0]) transpose_xy(L.etaT[c], (const T*)L.eta[c], L.nC[0], L.nC[1], L.nC[2], true, 0);
             }
-            for (int d = 0; d < 3; ++d) if (L.fac[d]) compute_factor(L, d);
+            for (int d = 0; d < 3; ++d) if (L.fac[d]) { compute_factor(L, d); fill_scantab(L, d); }
         };
         refresh(L0);
         for (auto& kv : hier) for (auto& l : kv.second.lv) if (l) refresh(*l);
@@ -1441,6 +1445,7 @@ struct MG : emg3d_mg {
             }
         }
         a.qd = nullptr; a.qdn = 0;
+        a.sm = nullptr; a.smn = 0;
         a.fe = nullptr; a.fnE = 0; a.fax = a.fnX = a.fown = a.fns = a.fnp = 0; a.fseq = 0;
         for (int c = 0; c < 4; ++c) { a.fqd[c] = nullptr; a.fqdn[c] = 0; }
         a.qpl = P.NW; a.qM = P.M; a.seg = P.seg; a.qlpw = 0;
@@ -1538,6 +1543,50 @@ struct MG : emg3d_mg {
         }
         check_launch();
     }
+    // Scan tables of the same colour launches (SweepPlan::scantab; smooth_qpl.hpp SM): the matrix part of every lane's row after
+    // every full step of the two scans is a function of the factor and the level's coefficients, not of e or s.  The kernel's own
+    // scans write it once (fill_scantab: the sweep as it runs without a table, storing the matrices instead of the field), every
+    // sweep launch thereafter loads it and scans the offsets alone.  Optional memory: a refusal keeps the computing path.
+    void ensure_scantab(Level<T>& L, int dir) {
+        const SweepPlan& P = plan(L, dir);
+        if (!P.scantab || L.sm[dir][0] || L.smn[dir][0] == ~0u) return;
+        L.smn[dir][0] = ~0u;                                    // (asked once)
+        if (!L.fac[dir]) return;
+        LineArgs<T> a;
+        line_args(L, dir, a, true);
+        const i64 lpg = 16 / a.seg;
+        const i64 rows = 2 * (i64)(__builtin_ctz((unsigned)a.seg) - 1) * 4;      // [pass][step][k]
+        void* tab[4] = {nullptr, nullptr, nullptr, nullptr};
+        unsigned nth[4] = {0, 0, 0, 0};
+        for (int c = 0; c < 4; ++c) {
+            const i64 n = a.nA[c & 1] * a.nB2[c >> 1];
+            if (n <= 0) continue;
+            nth[c] = xcd_grid((n + lpg - 1) / lpg) * 64u;
+            tab[c] = try_alloc<T>((i64)nth[c] * rows);
+            if (!tab[c]) return;                                // (all colours or none: the blocks taken stay with the handle)
+        }
+        for (int c = 0; c < 4; ++c) { L.sm[dir][c] = tab[c]; L.smn[dir][c] = nth[c]; }
+        fill_scantab(L, dir);
+    }
+    // (re)write the scan tables of (level, direction) from the factor as it stands: after ensure_factor and after every
+    // compute_factor of a factor that has tables (refresh_model, set_smu0)
+    void fill_scantab(Level<T>& L, int dir) {
+        if (!L.sm[dir][0] && !L.sm[dir][1] && !L.sm[dir][2] && !L.sm[dir][3]) return;
+        LineArgs<T> a;
+        line_args(L, dir, a, true);
+        const i64 lpg = 16 / a.seg;
+        a.bt = Batch();                                         // (the tables do not depend on the system)
+        for (int c = 0; c < 4; ++c) {
+            if (!L.sm[dir][c]) continue;
+            a.mode = 0; a.cP = c & 1; a.cQ = c >> 1;
+            a.cntA = a.nA[a.cP]; a.cntB = a.nB2[a.cQ];
+            a.rs.slot0 = (unsigned)a.base[c];
+            const i64 n = a.cntA * a.cntB;
+            a.sm = L.sm[dir][c]; a.smn = L.smn[dir][c];
+            if (!broken) qpl_scantab_launch<T>(1, 0, dim3(xcd_grid((n + lpg - 1) / lpg)), stream, a);
+        }
+        check_launch();
+    }
     // name of the kernel instantiation the last line-sweep launch selected (bench.py's roofline object and the
     // sweep-level parity tests report it instead of guessing from the grid size)
     char sweep_name[64] = "";
@@ -1578,6 +1627,10 @@ struct MG : emg3d_mg {
         case SweepFamily::qpl:
         case SweepFamily::qpl_chain: {  // (16 NW) / seg lines per workgroup; single-wave workgroups load the descriptors of ensure_qdesc
             const i64 lpg = (16 * P.NW) / P.seg;
+            if (a.sm && P.NW == 1 && P.M == 1 && P.family == SweepFamily::qpl) {
+                qpl_scantab_launch<T>(2, a.qd ? 2 : 0, bgrid(xcd_grid((n + lpg - 1) / lpg)), stream, a);
+                break;
+            }
             qpl_launch<T>(P.NW, P.M, false, (P.NW == 1 && a.qd) ? 2 : 0, P.family == SweepFamily::qpl_chain,
                           bgrid(xcd_grid((n + lpg - 1) / lpg)), stream, a);
             break;
@@ -1835,6 +1888,7 @@ struct MG : emg3d_mg {
         if (nu <= 0) return;
         ensure_factor(L, dir);
         ensure_qdesc(L, dir);
+        ensure_scantab(L, dir);
         const FusePlan& F = ensure_fuse(L, dir, nu);
         if (dry) { prepare_work(L, dir); return; }
         if (conv_in) to_work(L, dir);
@@ -1851,6 +1905,7 @@ struct MG : emg3d_mg {
                 a.cntA = a.nA[a.cP]; a.cntB = nB[a.cQ];
                 a.rs.slot0 = (unsigned)a.base[c];
                 a.qd = L.qd[dir][c]; a.qdn = (L.qd[dir][c] ? L.qdn[dir][c] : 0u);
+                a.sm = L.sm[dir][c]; a.smn = (L.sm[dir][c] ? L.smn[dir][c] : 0u);
                 launch_sweep(P, a, a.cntA * a.cntB);
             }
             nu = 0;
@@ -2185,7 +2240,7 @@ struct MG : emg3d_mg {
         auto clear = [](Level<T>& L) {
             for (int d = 0; d < 3; ++d) {
                 L.fac[d] = nullptr; L.fac_kind[d] = 0; L.plan_key[d] = -1; L.fuse_key[d] = -1;
-                for (int c = 0; c < 4; ++c) { L.qd[d][c] = nullptr; L.qdn[d][c] = 0; }
+                for (int c = 0; c < 4; ++c) { L.qd[d][c] = nullptr; L.qdn[d][c] = 0; L.sm[d][c] = nullptr; L.smn[d][c] = 0; }
             }
         };
         if (lv0) clear(*lv0);

@@ -79,6 +79,11 @@ struct LineArgs {
     // model only), written once by the kernel's generating mode; [item][qdn threads]; nullptr: the kernel computes them
     const void* qd;
     unsigned qdn;
+    // ... and the scan tables of THIS colour launch (smooth_qpl.hpp SM): the matrix part of every lane's row after every full scan
+    // step of both passes, [pass][step][k][smn threads], written by the kernel's own scans when the factor is built; nullptr: the
+    // kernel computes them
+    const void* sm;
+    unsigned smn;
     // fused colour passes (k_line_sweep_qpl FZ; sweep_plan.hpp plan_fuse): private copies [system][slab][fnE] with the level's strides,
     // slab axis (0: P, 1: Q), FuseGeom (cells along the axis, own lines per slab, slabs, passes), the colour of pass p in bits
     // 4 p .. 4 p + 1 of fseq, and the descriptor table of each colour

@@ -76,7 +76,7 @@ __device__ __forceinline__ void qpl_args_burst(const LineArgs<T>& a) {
                  "s"(a.rs.off[2]));
     asm volatile("" :: "s"(a.rs.st[0][0]), "s"(a.rs.st[0][1]), "s"(a.rs.st[0][2]), "s"(a.rs.st[1][0]), "s"(a.rs.st[1][1]),
                  "s"(a.rs.st[1][2]), "s"(a.rs.st[2][0]), "s"(a.rs.st[2][1]), "s"(a.rs.st[2][2]), "s"(a.t), "s"(a.jQ0), "s"(a.cnt),
-                 "s"(a.rs.nP), "s"(a.rs.nQ), "s"(a.qd), "s"(a.qdn));
+                 "s"(a.rs.nP), "s"(a.rs.nQ), "s"(a.qd), "s"(a.qdn), "s"(a.sm), "s"(a.smn));
 }
 
 // DM (descriptor mode, colour order only): 0 = the prologue computes indices and coefficients; 1 = it computes them, WRITES them to
@@ -91,8 +91,18 @@ __device__ __forceinline__ void qpl_args_burst(const LineArgs<T>& a) {
 // its private copy of the field (LineArgs::fe), a workgroup barrier between passes and no other synchronisation; the per-line body
 // one() is the unfused launch's, fed with the descriptor index the unfused launch would have given the line.  It never writes the
 // level's e (other slabs may still be copying in): k_scatter_slabs does, in a launch of its own.
-template <class T, int NW, int M, bool HL = false, int DM = 0, bool CH = false, bool FZ = false>      // HL: hyperplane loop (mode 2, lexicographic order)
+// SM (scan tables, colour order, scan form, one wave per workgroup, one block per quad): the matrix part mG of a lane's row at every
+// scan step is a function of the factor and the level's coefficients only -- not of e or s --, so the 16 of the 20 complex
+// multiply-adds of a step that update it repeat, launch after launch, what the launch before computed.  1 = the kernel runs as ever
+// and WRITES mG after every full scan step to LineArgs::sm, [pass][step][k][smn threads], and stores no field value (run once per
+// (level, direction, colour) when the factor is built or recomputed: the table holds what the very instructions of the sweep
+// produce, so the sweeps that load it are bit for bit the sweeps that compute it); 2 = the sweep loads its rows of all steps with
+// the other prologue loads, publishes only the offset mc per step (the exchange buffer shrinks to one number per row) and applies
+// the four multiply-adds of the offset in the order compose_with has them.  Where: SweepPlan::scantab (sweep_plan.hpp).
+constexpr int QPL_SM_STEPS = 3;     // full scan steps of a line inside one wave: log2(seg) - 1, seg <= 16
+template <class T, int NW, int M, bool HL = false, int DM = 0, bool CH = false, bool FZ = false, int SM = 0>      // HL: hyperplane loop (mode 2, lexicographic order)
 __global__ __launch_bounds__(64 * NW) void k_line_sweep_qpl(LineArgs<T> a) {
+    static_assert(SM == 0 || (NW == 1 && M == 1 && !HL && !CH && !FZ && DM != 1), "scan tables: scan form, lines inside one wave, one block per quad, colour order");
     static_assert(DM == 0 || (!HL && (NW == 1 || FZ)), "descriptors: one wave per workgroup, colour order");
     static_assert(!CH || ((NW == 1 || FZ) && M == 1 && !HL), "chain form: lines inside one wave, one block per quad");
     static_assert(!FZ || (DM == 2 && M == 1 && !HL), "fused passes: descriptors, one block per quad, colour order");
@@ -119,7 +129,7 @@ __global__ __launch_bounds__(64 * NW) void k_line_sweep_qpl(LineArgs<T> a) {
     typedef unsigned int u32;
     EMG_SWEEP_WG(a)
     // ---- exchange buffer: per quad the four rows of its map, five numbers each; double buffered --
-    __shared__ T xb[2][(FZ && CH) ? 1 : NQ][4][5];     // (the chain form does not use it)
+    __shared__ T xb[2][(FZ && CH) ? 1 : NQ][4][SM == 2 ? 1 : 5];     // (the chain form does not use it; with loaded scan tables: the offsets only)
     // the field the lines work on: the level's (FZ: the slab's private copy, same strides); the descriptors of the colour
     T* const ebase = FZ ? a.fe + ((i64)bsys_ * a.fns + wg) * a.fnE : a.e + boff_;
     const void* qd_ = a.qd;
@@ -142,6 +152,23 @@ __global__ __launch_bounds__(64 * NW) void k_line_sweep_qpl(LineArgs<T> a) {
     bool lastb[M], inl[M];
     u32 dS[M], dS0[M];          // element offsets of the row's own edge and of the edge along the line (source load = result store)
     constexpr int QD_U4 = 3, QD_D2 = 8;         // per block: 3 x uint4 (11 offsets / flags) + 8 x double2 (15 coefficient products)
+    // scan tables loaded: the rows of all steps of both passes, requested in front of the other prologue loads (one round trip);
+    // tg[pass][i] = the lane's matrix row after full step i
+    T tg[2][QPL_SM_STEPS][4];
+    if constexpr (SM == 2) {
+        const T* const sm = reinterpret_cast<const T*>(a.sm);
+        const u32 smn = a.smn;
+#pragma unroll
+        for (int ps = 0; ps < 2; ++ps) {
+#pragma unroll
+            for (int i = 0; i < QPL_SM_STEPS; ++i) {
+                if (i < lseg - 1) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) tg[ps][i][k] = ld_t(sm, (u32)((ps * (lseg - 1) + i) * 4 + k) * smn + tix);
+                }
+            }
+        }
+    }
     if constexpr (DM == 2) {
         // ================= descriptors loaded: offsets and coefficient products come from the table =================
         const uint4* const q4 = reinterpret_cast<const uint4*>(qd_);
@@ -375,13 +402,25 @@ __global__ __launch_bounds__(64 * NW) void k_line_sweep_qpl(LineArgs<T> a) {
     T mc, mG[4];        // my row of the chunk map: u -> mc + mG . u
     auto publish = [&](int p) {
         xb[p][quad][r][0] = mc;
+        if constexpr (SM != 2) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) xb[p][quad][r][1 + k] = mG[k];
+            for (int k = 0; k < 4; ++k) xb[p][quad][r][1 + k] = mG[k];
+        }
+    };
+    // scan tables: the generating launch writes the row after full step i of pass ps; the loading launch runs the scan of a pass on the
+    // offsets alone, the row of step i from the table (step 0: the row fwd_row / bwd_row just formed) -- compose_c_only IS the offset
+    // part of compose_with, so every step, the last included, is that one call
+    auto sm_write = [&](int ps, int i) {
+        T* const sm = reinterpret_cast<T*>(const_cast<void*>(a.sm));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sm[(size_t)((ps * (lseg - 1) + i) * 4 + k) * a.smn + tix] = mG[k];
     };
     // my row <- my row o (map of quad src): c += G c', G <- G G'
     auto compose_with = [&](int p, int src) {
         const T g0 = mG[0], g1 = mG[1], g2 = mG[2], g3 = mG[3];
-        if (NW >= 4 || M > 1) {
+        if constexpr (SM == 2) {
+            // (never called: the other maps' matrices are not in the exchange buffer)
+        } else if (NW >= 4 || M > 1) {
             // throughput regime (many waves per SIMD): streamed by rows of the other map (rank-1
             // updates), one row = five LDS reads at a time: 5 numbers live instead of 20 -> fewer
             // registers, more waves per SIMD
@@ -464,12 +503,31 @@ __global__ __launch_bounds__(64 * NW) void k_line_sweep_qpl(LineArgs<T> a) {
         compose_with(p, quad);
         p ^= 1;
     }
+    if constexpr (SM == 2) {
+#pragma unroll
+        for (int i = 0; i <= QPL_SM_STEPS; ++i) {
+            const int st = 1 << i;
+            if (st < seg) {
+                if (i > 0) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) mG[k] = tg[0][i - 1][k];
+                }
+                publish(p);
+                sync();
+                if (ch >= st) compose_c_only(p, quad - st);
+                p ^= 1;
+            }
+        }
+    } else {
+        int fi = 0;     // (full steps so far)
 #pragma unroll 1
-    for (int st = 1; st < seg; st <<= 1) {
-        publish(p);
-        sync();
-        if (ch >= st) { if (2 * st < seg) compose_with(p, quad - st); else compose_c_only(p, quad - st); }
-        p ^= 1;
+        for (int st = 1; st < seg; st <<= 1) {
+            publish(p);
+            sync();
+            if (ch >= st) { if (2 * st < seg) compose_with(p, quad - st); else compose_c_only(p, quad - st); }
+            if constexpr (SM == 1) { if (2 * st < seg) sm_write(0, fi++); }
+            p ^= 1;
+        }
     }
     publish(p);
     sync();
@@ -540,12 +598,31 @@ __global__ __launch_bounds__(64 * NW) void k_line_sweep_qpl(LineArgs<T> a) {
         compose_with(p, quad);
         p ^= 1;
     }
+    if constexpr (SM == 2) {
+#pragma unroll
+        for (int i = 0; i <= QPL_SM_STEPS; ++i) {
+            const int st = 1 << i;
+            if (st < seg) {
+                if (i > 0) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) mG[k] = tg[1][i - 1][k];
+                }
+                publish(p);
+                sync();
+                if (ch + st < seg) compose_c_only(p, quad + st);
+                p ^= 1;
+            }
+        }
+    } else {
+        int fi = 0;
 #pragma unroll 1
-    for (int st = 1; st < seg; st <<= 1) {
-        publish(p);
-        sync();
-        if (ch + st < seg) { if (2 * st < seg) compose_with(p, quad + st); else compose_c_only(p, quad + st); }
-        p ^= 1;
+        for (int st = 1; st < seg; st <<= 1) {
+            publish(p);
+            sync();
+            if (ch + st < seg) { if (2 * st < seg) compose_with(p, quad + st); else compose_c_only(p, quad + st); }
+            if constexpr (SM == 1) { if (2 * st < seg) sm_write(1, fi++); }
+            p ^= 1;
+        }
     }
     publish(p);
     sync();
@@ -561,7 +638,7 @@ __global__ __launch_bounds__(64 * NW) void k_line_sweep_qpl(LineArgs<T> a) {
 #pragma unroll
         for (int l = 0; l < 4; ++l) { cmsc(x0, W0[j][l + 1], v[l]); cmsc(xr, Wr[j][l + 1], v[l]); }
         const int i = ch * M + j;
-        if (live && inl[j]) {       // (inside the line the clamped load offsets ARE the store offsets)
+        if (SM != 1 && live && inl[j]) {       // (inside the line the clamped load offsets ARE the store offsets; the generating launch stores no field)
             if (r == 0) eo[dS0[j]] = x0;
             if (!lastb[j]) eo[dS[j]] = xr;
         }

@@ -32,6 +32,9 @@ template <class T> void qpl_launch(int nw, int m, bool hl, int dm, bool chain, d
 // k_line_sweep_qpl<T, 8, 1, false, 2, true, true>: all colour passes of a smoothing call in one launch, a workgroup of 8 waves per slab
 // and system (LineArgs::fe ...; sweep_plan.hpp plan_fuse), chain form; lab build: also the scan form, <T, 4, 1, false, 2, false, true>.
 template <class T> void qpl_fused_launch(bool chain, dim3 grid, hipStream_t st, const LineArgs<T>& a);
+// k_line_sweep_qpl<T, 1, 1, false, dm, false, false, sm>: the scan form with scan tables (LineArgs::sm), sm: 1 generate (dm = 0: the
+// sweep as it runs without a table, writing the scanned matrices and no field) | 2 load (dm 0 | 2)
+template <class T> void qpl_scantab_launch(int sm, int dm, dim3 grid, hipStream_t st, const LineArgs<T>& a);
 
 // k_residual<T, mode> (kz <= 1) / k_residual_zm<T, mode, kz> (stencil.hpp; reference core.amat_x, emg3d/core.py:29-177, and
 // solver.residual, solver.py:980-1039): mode 0 = r -= A e (the operator itself), 1 = r = s - A e, 2 = the norm's partial sums only;

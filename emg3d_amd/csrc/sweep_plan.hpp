@@ -57,6 +57,7 @@ inline i64 sweep_tha_lds_bytes(i64 nL, int tsize) {
 //   tha_min_lines  1.07 S [1100]  measured crossover of the affine kernel against the scan kernel on 33..64-block lines
 //   tha_big_lines   8 CUs [2048]  65..128-block lines in the affine kernel: one workgroup of 8 lines per CU, ONE round
 //   qdesc_max      8.8 S  [9000]  threads of a colour launch up to which the descriptor table is cheaper than the arithmetic
+constexpr i64 SCANTAB_THREADS = 40000;     // (sweep_scantab below)
 struct SweepKnobs {
     // the device and the handle
     i64 simds = 1024;                   // 4 per CU
@@ -126,6 +127,12 @@ struct SweepKnobs {
     // In-kernel stamps at 128 x 4 x 4: 8330 -> 7500 cycles.
     int use_qdesc = (int)LAB_ENV("EMG3D_QDESC", 1);
     i64 qdesc_max_threads_env = LAB_ENV("EMG3D_QDESC_MAX", 0);
+    // Scan tables of the scan kernel's colour launches (MG::ensure_scantab, smooth_qpl.hpp SM; the rule: sweep_scantab below):
+    // -1 by the rule, 0 never, 1 wherever the kernel form allows it whatever the launch's size (lab); threads of a colour launch up to
+    // which a table is admitted (0: scantab_max_threads()); bytes the four colours' tables of a (level, direction) may take
+    int use_scantab = (int)LAB_ENV("EMG3D_QPL_SCANTAB", -1);
+    i64 scantab_max_threads_env = LAB_ENV("EMG3D_QPL_SCANTAB_MAX", 0);
+    i64 scantab_max_bytes = LAB_ENV("EMG3D_QPL_SCANTAB_BYTES", (i64)64 << 20);
     // Fused colour passes of a smoothing call on the levels of short lines (plan_fuse below): lines of at most fuse_max_seg quads (0:
     // never); own lines per slab (0: 2); bytes of private copies a
     // (level, direction) may take
@@ -153,6 +160,7 @@ struct SweepKnobs {
     i64 twist_max_lines() const { return twist_max_lines_env > 0 ? twist_max_lines_env : q_min_lines(); }
     i64 qpl_few_lines() const { return qpl_few_lines_env > 0 ? qpl_few_lines_env : simds; }
     i64 qdesc_max_threads() const { return qdesc_max_threads_env > 0 ? qdesc_max_threads_env : (9000 * simds + 1023) / 1024; }
+    i64 scantab_max_threads() const { return scantab_max_threads_env > 0 ? scantab_max_threads_env : (SCANTAB_THREADS * simds + 1023) / 1024; }
     i64 tha_min_lines() const { return tha_min_lines_env > 0 ? tha_min_lines_env : (1100 * simds + 1023) / 1024; }
     i64 tha_big_max_lines() const { return tha_big_max_lines_env > 0 ? tha_big_max_lines_env : (i64)SWEEP_THA_LPW * (simds / 4); }
 };
@@ -206,6 +214,8 @@ struct SweepPlan {
     i64 fac_entries = 0;        // factor entries per line
     i64 mid = 0;                // middle block of the two-sided factor (one-sided: the last block)
     bool qdesc = false;         // the colour launches of the scan kernel load per-lane descriptors (MG::ensure_qdesc)
+    bool scantab = false;       // ... and the scanned map matrices of every step (MG::ensure_scantab; sweep_scantab)
+    i64 scantab_bytes = 0;      // bytes of the four colours' tables (0: the kernel form has no table)
     i64 nmax = 0;               // lines of the largest colour
     i64 lpw = 0;                // lines per wave (thm: per pair of waves; tha, qpl: per workgroup; thread per line: 64)
     i64 rounds = 0;             // rounds of waves / workgroups of the largest colour's launch
@@ -299,6 +309,33 @@ inline int sweep_balanced_lpw(const SweepKnobs& K, i64 lines) {
     return (int)std::min<i64>(16, std::max<i64>(lpw, 8));
 }
 
+// ---- scan tables of the scan kernel (smooth_qpl.hpp SM) -----------------------------------------------------------------------------
+// The matrix part of a lane's row after every full Kogge-Stone step depends on the factor and the level's coefficients only; a table
+// [pass][step][k][threads] written once per factor build replaces 16 of the 20 complex multiply-adds, 4 of the 5 LDS writes and 16 of
+// the 20 LDS reads of a step by 2 (log2(seg) - 1) 4 tsize bytes of loads per lane and launch (256 B at seg = 8, 384 B at seg = 16,
+// complex128).  The kernel form: scan form in colour order, lines inside ONE wave (NW = 1), one block per quad.  The size rule: the
+// colour launch has at most scantab_max_threads() threads -- the table is read from memory by every launch, and a launch of many
+// threads reads more table than it saves arithmetic -- and the four colours' tables fit scantab_max_bytes.  threads: of the largest
+// colour's launch, one system (batched systems share the table).
+// Measured (profiles/scan_tables_ab.txt, HISTORY part S; 128^3 F-cycle, lab library, three alternating repetitions, ms per cycle):
+// no table 8.217 / 8.242 / 8.214; launches of <= 9000 threads (the 140 launches on 8-block lines: 8192 threads, 2 MB per colour)
+// 8.102 / 8.109 / 8.076; <= 40 000 threads (also the 112 launches on 16-block lines) 8.078 / 8.026 / 8.063; every launch the kernel
+// form allows 8.080 / 8.070 / 8.061 (the same launches: the cycle has no larger one of this form).  Both classes pay, so
+// SCANTAB_THREADS is the largest size that was measured to, 40 000 threads on 1024 SIMDs; nothing larger has been measured, and
+// the one larger scan class of that cycle (32-block lines, two blocks per quad, 65 k threads) would read 33 MB of table in a launch
+// of 13.7 us: it has no table by its form.
+inline i64 sweep_scantab_bytes(int seg, i64 threads, int tsize) {
+    int lseg = 0;
+    while ((1 << lseg) < seg) ++lseg;
+    return 4 * (((threads / 64 + 7) / 8) * 8 * 64) * 2 * (i64)(lseg - 1) * 4 * tsize;     // (grids are rounded up to the 8 XCDs)
+}
+inline bool sweep_scantab(const SweepKnobs& K, SweepFamily family, int NW, int M, int seg, i64 threads, int tsize) {
+    if (K.use_scantab == 0 || K.order != 1 || family != SweepFamily::qpl || NW != 1 || M != 1 || seg < 4 || seg > 16) return false;
+    const i64 bytes = sweep_scantab_bytes(seg, threads, tsize);
+    if (bytes > K.scantab_max_bytes || bytes >= ((i64)1 << 32)) return false;
+    return K.use_scantab == 1 || threads <= K.scantab_max_threads();
+}
+
 // ---- THE selection ------------------------------------------------------------------------------------------------------------
 // Decided by the level's largest colour, for every colour launch of the (level, direction); the factor's layout follows the family.
 inline SweepPlan plan_sweep(const SweepKnobs& K, const SweepShape& G, int dir) {
@@ -346,6 +383,9 @@ inline SweepPlan plan_sweep(const SweepKnobs& K, const SweepShape& G, int dir) {
         p.lpw = (16 * p.NW) / p.seg; p.rounds = (((nmax + p.lpw - 1) / p.lpw) * p.NW * K.nsys + S - 1) / S;
         p.qdesc = K.use_qdesc && K.order == 1 && p.NW == 1 && G.lines_tot(dir) * p.fac_entries < ((i64)1 << 32) &&
                   ((nmax + p.lpw - 1) / p.lpw) * 64 <= K.qdesc_max_threads();
+        if (p.family == SweepFamily::qpl && p.NW == 1 && p.M == 1 && K.order == 1)
+            p.scantab_bytes = sweep_scantab_bytes(p.seg, ((nmax + p.lpw - 1) / p.lpw) * 64, G.tsize);
+        p.scantab = sweep_scantab(K, p.family, p.NW, p.M, p.seg, ((nmax + p.lpw - 1) / p.lpw) * 64, G.tsize);
     } else if ((rp_fits || p.big) && p.fac_kind == 4) {
         // lines per wave: aim at >= ~1000 waves (one per SIMD) before filling lanes
         p.family = p.big ? SweepFamily::qc_big : SweepFamily::qc;

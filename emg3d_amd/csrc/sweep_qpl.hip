@@ -48,6 +48,18 @@ void qpl_fused_launch(bool chain, dim3 grid, hipStream_t st, const LineArgs<T>& 
 #endif
     hipLaunchKernelGGL((k_line_sweep_qpl<T, 8, 1, false, 2, true, true>), grid, dim3(512), 0, st, a);
 }
+template <class T>
+void qpl_scantab_launch(int sm, int dm, dim3 grid, hipStream_t st, const LineArgs<T>& a) {
+    if (sm == 1) hipLaunchKernelGGL((k_line_sweep_qpl<T, 1, 1, false, 0, false, false, 1>), grid, dim3(64), 0, st, a);
+    else if (dm == 2) hipLaunchKernelGGL((k_line_sweep_qpl<T, 1, 1, false, 2, false, false, 2>), grid, dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((k_line_sweep_qpl<T, 1, 1, false, 0, false, false, 2>), grid, dim3(64), 0, st, a);
+}
+#if EMG3D_UNIT_T != 1
+template void qpl_scantab_launch<double>(int, int, dim3, hipStream_t, const LineArgs<double>&);
+#endif
+#if EMG3D_UNIT_T != 0
+template void qpl_scantab_launch<c128>(int, int, dim3, hipStream_t, const LineArgs<c128>&);
+#endif
 #if EMG3D_UNIT_T != 1
 template void qpl_launch<double>(int, int, bool, int, bool, dim3, hipStream_t, const LineArgs<double>&);
 template void qpl_fused_launch<double>(bool, dim3, hipStream_t, const LineArgs<double>&);

@@ -37,7 +37,7 @@ extern "C" {
 /* ---- library / device ------------------------------------------------- */
 /* ABI version: bumped whenever an entry point is added or a signature changes; emg3d_hip_version() returns the value the
  * library was built with, and the Python binding (emg3d_amd/_lib.py: ABI_VERSION) refuses a library of another version. */
-#define EMG3D_HIP_ABI_VERSION 120
+#define EMG3D_HIP_ABI_VERSION 121
 int emg3d_hip_version(void);
 int emg3d_hip_device_count(int* count);
 int emg3d_hip_set_device(int device);
@@ -118,6 +118,13 @@ int emg3d_restrict_model(int is_complex, int64_t nx, int64_t ny, int64_t nz, voi
  * numbers per block, 3 mirrored two-sided, 4 compact 11 numbers), parity-split working copies (0 / 1), 64-bit field offsets (0 / 1). */
 int emg3d_sweep_plan(int dtype, int64_t nx, int64_t ny, int64_t nz, int dir, int order, int nsys, int cu_count, char* name,
                      int64_t* info);
+
+/* The same plan's answer on the scan tables of the scan kernel (csrc/sweep_plan.hpp, sweep_scantab; the arguments of
+ * emg3d_sweep_plan, shape logic only, callable without a GPU when cu_count > 0): do the colour launches load the scanned map
+ * matrices of every scan step from a table written when the factor is built?  A call of its own, so that callers of
+ * emg3d_sweep_plan keep their six-entry buffers.  info[4]: table on (0 / 1), bytes of the four colours' tables (0: the kernel form
+ * has none), quads per line (0: not the scan kernel), the threads of a colour launch up to which a table is admitted. */
+int emg3d_sweep_scantab(int dtype, int64_t nx, int64_t ny, int64_t nz, int dir, int order, int nsys, int cu_count, int64_t* info);
 
 /* How many forward steps of a half of a line keep their intermediate result z in LDS where the two-sided chain kernel
  * (k_line_sweep_thm) serves such a level -- csrc/sweep_plan.hpp, sweep_thm_zkeep; the arguments of emg3d_sweep_plan, shape logic only,
