@@ -140,15 +140,17 @@ def check_norms(got, ref, snorm, oracle_dev=None, strict_above=1e-5):
     return widened
 
 
-def device_run(em, grid, model, sfield, ordering, maxit=MAXIT, trace=True, drain_at_end=False, **kw):
+def device_run(em, grid, model, sfield, ordering, maxit=MAXIT, trace=True, drain_at_end=False, vmodel=None, **kw):
     """The level-0 loop of emg3d_amd.solver.multigrid on a handle of its own, with the device's full-precision trace:
     (records, norms, error_at_cycle, field).  Level 0 reports it = -1 (the host counts the cycles): mapped to the cycle.
     ``drain_at_end``: the records of all cycles are fetched with one get_trace() after the last cycle (the handle has to hold
-    them all); the cycle of a level-0 record is then counted from the pre-smoothing calls of level 0."""
+    them all); the cycle of a level-0 record is then counted from the pre-smoothing calls of level 0.
+    ``vmodel``: the handle's model arrays (an object with eta_x, eta_y, eta_z, zeta) given directly -- ``model`` is then not
+    looked at and ``sfield`` may be the plain source buffer [fx | fy | fz] of the handle's dtype."""
     from emg3d_amd.solver import DeviceMG, MGParameters
     var = MGParameters(verb=0, sslsolver=False, vnC=grid.vnC, ordering=ordering, maxit=maxit, tol=TOL, cycle=kw['cycle'],
                        semicoarsening=kw['semicoarsening'], linerelaxation=kw['linerelaxation'])
-    vm = em.VolumeModel(grid, model, sfield)
+    vm = em.VolumeModel(grid, model, sfield) if vmodel is None else vmodel
     raw = []
     with DeviceMG(grid, vm, sfield.dtype) as dev:
         dev.set_params(var)

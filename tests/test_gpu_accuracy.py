@@ -16,7 +16,11 @@ at 150 x and 5000 x.  The floor covers a few final roundings where
 `family shape direction dtype generator err(ref) err(hip) ratio`, ratio = err(hip) / max(err(ref), floor): what is held below 10.
 
 Which kernel a case runs is asserted by name on the handle (and on the CPU in tests/test_accuracy_plan.py); the residual kernels
-k_residual and k_residual_zm are held to the extended amat_x in the same way."""
+k_residual and k_residual_zm are held to the extended amat_x in the same way.
+
+The field is not the only measure: on the layered marine model of tests/_hard_models.py the lines of the air layer are close to singular,
+every elimination order is then equally far from the truth in the field, and what tells a sound line solve from an unsound one is the
+residual it leaves (`test_layered_sweep_residual`, at the end of this file)."""
 import os
 from types import SimpleNamespace
 
@@ -24,6 +28,7 @@ import numpy as np
 import pytest
 
 import _hard_cases as hc
+import _hard_models as hm
 
 pytestmark = pytest.mark.gpu
 
@@ -132,3 +137,52 @@ def test_residual(orc, monkeypatch, shape, kernel, env, dtype):
     assert np.isfinite(r).all() and np.abs(r).max() > 0
     bad = _report(name, shape, 0, dtype, "hard", hc.err(ref, truth), hc.err(r, truth))
     assert not bad, bad
+
+
+class OffTheBound(AssertionError):
+    """A measure above hc.bound: the only failure the expected-failure marks below stand for."""
+
+
+# ---- the residual a line solve leaves on the layered model -------------------------------------------------------------------------
+# Found by tests/test_gpu_cycle_accuracy.py and isolated here (tests/_hard_models.py, `sweep_references`): one smoothing call of two
+# sweeps on level 0 of the layered 16 x 16 x 16 model, started from the field after the first cycle.  Lines in the air layer are
+# close to singular; every kernel, like the float64 oracle, is then 1e-8 from the truth in the field -- the measure of the tests
+# above --, but only the one-sided eliminations (the oracle's order: k_line_sweep_qc, _rp, the thread-per-line kernel) leave the
+# oracle's residual, 1e-13 ||s||.  The scan kernel and the two-sided kernel leave 1e-7 ... 1e-6 ||s||, in the air cells.
+_KNOWN = ("known defect (profiles/HISTORY.md, part T): ||A (e - e_truth)|| / ||s|| after one smoothing call, x- / y- / z-lines, measured on an "
+          "MI355X against the float64 oracle's 6e-14 ... 8e-14: ")
+LAYERED_SWEEP_CASES = [
+    ("qpl", "product", {}, "k_line_sweep_qpl<{t},1,1>", _KNOWN + "complex 7.0e-7 / 1.1e-7 / 2.4e-7, float64 9.5e-7 / 9.3e-8 / 2.8e-7"),
+    ("thm", "lab", dict(hc._THM), "k_line_sweep_thm<{t},3,8>", _KNOWN + "complex 2.5e-8 / 6.8e-7 / 3.7e-12, float64 1.3e-8 / 5.1e-7 / 2.3e-12"),
+    ("qc", "lab", dict(hc._QOFF, EMG3D_Q="2"), "k_line_sweep_qc<{t},3,4>", None),
+    ("rp", "lab", dict(hc._QOFF, EMG3D_TWIST="0", EMG3D_LPW="4"), "k_line_sweep_rp<{t},4>", None),
+    ("tpl", "lab", {"EMG3D_SWEEP": "tpl"}, "k_line_sweep<{t}>", None),
+]
+
+
+@pytest.mark.parametrize("dtype", hc.DTYPES, ids=hc.tname)
+@pytest.mark.parametrize("name,library,env,kernel,known", [
+    pytest.param(*c, marks=[pytest.mark.xfail(strict=True, raises=OffTheBound, reason=c[4])] if c[4] else [], id=c[0]) for c in LAYERED_SWEEP_CASES])
+def test_layered_sweep_residual(orc, lab, monkeypatch, name, library, env, kernel, known, dtype):
+    """err(hip) <= hc.bound(err(float64 oracle)) for the field AND for the residual ||A (e - e_truth)|| / ||s||, per direction."""
+    _set_env(monkeypatch, env)
+    prev = lab.use(lab.LAB_PATH if library == "lab" else lab.LIB_PATH)
+    bad = []
+    try:
+        for direction in (1, 2, 3):
+            p, truth, e_ref = hm.sweep_references(orc, dtype, direction)
+            with _handle(p, dtype, "colour") as dev:
+                dev.set_efield(p['e0'])
+                dev.smooth(2, direction)
+                e = dev.get_efield()
+                got = dev.last_sweep_kernel()
+            assert got.startswith(kernel.format(t=hc.tname(dtype))), (direction, got)
+            assert np.isfinite(e).all() and not np.array_equal(e, p['e0'])
+            e_hip = hm.sweep_errors(orc, p, e, truth)
+            for m in ("field", "anorm"):
+                bad.append(_report(got, hm.SWEEP_SHAPE, direction, dtype, "layered-" + m, e_ref[m], e_hip[m]))
+    finally:
+        lab.use(prev)
+    bad = [b for b in bad if b]
+    if bad:
+        raise OffTheBound(bad)
