@@ -49,10 +49,8 @@ def solve_frequencies(grid, model, src, freqs, device=0, strength=0, concurrent=
         sfield = fields.SourceField(grid, freq=f) if solver_opts.get('sslsolver') else fields.FrequencySpec(f)
         if handles is not None:
             dev = handles.target(sfield)
-        elif parts is not None:
-            dev = solver.DeviceMG.from_model(grid, parts, sfield, device=device)
         else:
-            dev = solver.DeviceMG(grid, models.VolumeModel(grid, model, sfield), sfield.dtype, device=device)
+            dev = solver.DeviceMG.open(grid, model, sfield, device=device, parts=parts)
         try:
             # receivers only (multigrid path): the solution stays in HBM -- no nE-sized download that would be thrown away
             keep = not (rec is not None and not return_field and not solver_opts.get('sslsolver'))
@@ -73,8 +71,6 @@ def solve_frequencies(grid, model, src, freqs, device=0, strength=0, concurrent=
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=min(int(concurrent), len(freqs))) as pool:
             return list(pool.map(one, freqs))
-    if parts is None:
-        return [one(f) for f in freqs]
     # frequencies solved one after the other share ONE handle per dtype: only eta and what is derived from it
     # (coarse models, line factorisations) is recomputed (DeviceMG.retarget) -- the results are those of a fresh
     # handle bit for bit; hierarchy, buffers and launch graphs are not rebuilt (15-20 ms per frequency at 128^3)

@@ -141,6 +141,16 @@ class DeviceMG:
         return cls.from_model_parts(grid, *parts, smu0=spec.smu0, device=device, epsilon_r=getattr(parts, 'epsilon_r', None),
                                     sval=spec.sval, map_code=getattr(parts, 'map_code', None))
 
+    @classmethod
+    def open(cls, grid, model, spec, device=0, parts=None):
+        """A handle for (grid, model, frequency of the field / frequency object ``spec``): ``from_model`` where the device can
+        form VolumeModel's eta bit for bit from sigma and V (``_exact_parts``; ``parts``: the caller's ``models.model_parts(grid,
+        model, raw=True)``, computed once for several frequencies), else eta from ``models.VolumeModel`` on the host."""
+        parts = _exact_parts(grid, model, spec.smu0) if parts is None else parts
+        if parts is not None:
+            return cls.from_model(grid, parts, spec, device=device)
+        return cls(grid, models.VolumeModel(grid, model, spec), spec.dtype, device=device)
+
     def _model_arrays(self, grid, parts):
         """The checks of ``set_model`` -- all of them before anything is uploaded -- and the arrays it uploads."""
         if tuple(int(n) for n in grid.vnC) != self._vnC:
@@ -1285,16 +1295,8 @@ def solve(grid, model, sfield, efield=None, cycle='F', sslsolver=False, semicoar
 
     info = ""
     if handle is None:
-        parts = _exact_parts(grid, model, sfield.smu0)
-        if parts is not None:
-            # eta = (smu0 V) sigma bit for bit as VolumeModel would give it, formed on the device from sigma and V
-            vmodel = None
-            dev = DeviceMG.from_model(grid, parts, sfield, device=device)
-        else:
-            vmodel = models.VolumeModel(grid, model, sfield)
-            dev = DeviceMG(grid, vmodel, sfield.dtype, device=device)
+        dev = DeviceMG.open(grid, model, sfield, device=device)
     else:
-        vmodel = None       # the device handle holds eta, zeta
         dev = handle
         if dev.dtype != sfield.dtype:
             raise ValueError(f"`handle` is {dev.dtype}, the source field {sfield.dtype}.")
@@ -1356,11 +1358,11 @@ def solve(grid, model, sfield, efield=None, cycle='F', sslsolver=False, semicoar
         elif var.cycle:
             var.cprint(header + f"{'[abs. error, last/prev]':>29}   l s\n", 3)
 
-        if var.sslsolver:
-            krylov(grid, vmodel, sfield, efield, var, dev=dev)
+        if var.sslsolver:               # (model None: the handle holds eta and zeta, for SciPy's iterations on host vectors too)
+            krylov(grid, None, sfield, efield, var, dev=dev)
         elif var.cycle:
             var._dev_efield_current = True
-            multigrid(grid, vmodel, sfield, efield if download else None, var, dev=dev)
+            multigrid(grid, None, sfield, efield if download else None, var, dev=dev)
             if not download and var.do_return:
                 efield = None
     finally:
@@ -1384,28 +1386,30 @@ def solve(grid, model, sfield, efield=None, cycle='F', sslsolver=False, semicoar
     elif var.verb == 1 and exit_status == 1:
         var.cprint(f"* WARNING :: {var.exit_message}", 0)
 
-    if var.return_info:
-        info_dict = {
-            'exit': exit_status,
-            'exit_message': var.exit_message,
-            'abs_error': var.l2,
-            'rel_error': var.l2 / var.l2_refe,
-            'ref_error': var.l2_refe,
-            'tol': var.tol,
-            'it_mg': var.it,
-            'it_ssl': var._ssl_it,
-            'time': var.runtime_at_cycle[-1],
-            'runtime_at_cycle': var.runtime_at_cycle,
-            'error_at_cycle': var.error_at_cycle,
-            'log': var.log_message,
-        }
-
     if var.do_return and var.return_info:
-        return efield, info_dict
+        return efield, _info_dict(var)
     elif var.do_return:
         return efield
     elif var.return_info:
-        return info_dict
+        return _info_dict(var)
+
+
+def _info_dict(var):
+    """The ``info_dict`` of a finished solve (reference solver.py:408-422)."""
+    return {
+        'exit': int(var.exit_message != 'CONVERGED'),
+        'exit_message': var.exit_message,
+        'abs_error': var.l2,
+        'rel_error': var.l2 / var.l2_refe,
+        'ref_error': var.l2_refe,
+        'tol': var.tol,
+        'it_mg': var.it,
+        'it_ssl': var._ssl_it,
+        'time': var.runtime_at_cycle[-1],
+        'runtime_at_cycle': var.runtime_at_cycle,
+        'error_at_cycle': var.error_at_cycle,
+        'log': var.log_message,
+    }
 
 
 def _exact_parts(grid, model, smu0):
@@ -1433,12 +1437,15 @@ def _rotation_partitions(states, active):
     return list(groups.values())
 
 
-def _batched_multigrid(dev, vars_, active):
-    """Level-0 loop of ``multigrid`` for the systems ``active[b]`` != 0 of a batched handle (mask already on the device), which
-    stand at the same point of the direction rotation and start together: initial norm, optional initial smoothing, then
-    cycles until every system has met one of its own termination tests (a finished system is frozen).  Returns the
-    systems for which ``_terminate`` raised ``_ConvergenceError`` (a failing preconditioner) and the mask the device holds at
-    the end."""
+def _batched_multigrid(dev, vars_, active, trace=False):
+    """THE level-0 loop of the multigrid solver (reference emg3d/solver.py:434-607; ``multigrid`` runs it for one system), for the
+    systems ``active[b]`` != 0 of the handle (mask already on the device), which stand at the same point of the direction rotation
+    and start together: initial norm, optional initial smoothing, then cycles until every system has met one of its own
+    termination tests (a finished system is frozen).  Returns the systems for which ``_terminate`` raised ``_ConvergenceError`` (a
+    failing preconditioner) and the mask the device holds at the end.
+
+    ``trace`` (``multigrid`` at verb = 5, one system; solver.py:498-515): also log the norm after every smoothing call of every
+    level -- the device reports them."""
     active = np.array(active, dtype=np.int32)
     on_device = active.copy()
     idx = [b for b in range(len(vars_)) if active[b]]
@@ -1450,22 +1457,35 @@ def _batched_multigrid(dev, vars_, active):
     dev.begin(lead.sc_dir)
     l2_last = np.atleast_1d(dev.residual_norm()).copy()
     l2_stag = {b: np.ones(maxc) * l2_last[b] for b in idx}
+    if trace:
+        cm0 = 1 if lead.clevel[lead.sc_dir] == 0 else lead.cycmax       # level 0's cycmax, fixed on entry (solver.py:480-485)
+        lead.cprint("     it cycmax               error", 4)
+        lead.cprint("      level [  dimension  ]            info\n", 4)
+        lead.cprint(_print_gs_info(0, 0, cm0, lead.vnC, l2_last[0]) + "initial error", 4)
+        dev.set_trace(True)
     if lead.nu_init > 0:
         dev.smooth(lead.nu_init, lead.lr_dir)
+        if trace:
+            lead.cprint(_print_gs_info(0, 0, cm0, lead.vnC, dev.residual_norm()) + "initial smoothing", 4)
     it = 0
     while active.any():
         live = [b for b in idx if active[b]]
         l2_prev = l2_last.copy()
         for b in idx:
             l2_stag[b][(it - 1) % maxc] = l2_last[b]
-        # the rotation of the directions depends on the cycle count only: one state for the systems of the group, each
-        # of which advances its own iterators (it may enter a later call in another group)
+        # the rotation of the directions (solver.py:597-600) depends on the cycle count only: one state for the systems of the
+        # group, each of which advances its own iterators (it may enter a later call in another group).  It is known before
+        # the cycle: the handle prepares the next pair's hierarchy / factorisations / launch graph on the host meanwhile
         cur = (vars_[live[0]].sc_dir, vars_[live[0]].lr_dir)
         for b in live:
             v = vars_[b]
             nxt = (next(v.sc_cycle) if v.sc_cycle else v.sc_dir, next(v.lr_cycle) if v.lr_cycle else v.lr_dir)
         ahead = PREPARE_AHEAD and nxt != cur and it + 1 < lead.maxit
         norms = np.atleast_1d(dev.cycle(cur[0], cur[1], nxt=nxt if ahead else None))
+        if trace:
+            for rit, level, cm, kind, vnC, norm in dev.get_trace():
+                lead.cprint(_print_gs_info(it if level == 0 else rit, level, cm, vnC, norm) +
+                            ("coarsest level", "pre-smoothing", "post-smoothing")[kind], 4)
         it += 1
         changed = False
         for b in live:
@@ -1482,7 +1502,7 @@ def _batched_multigrid(dev, vars_, active):
                 changed = True
                 continue
             if done:
-                var.l2 = l2_last[b]
+                var.l2 = float(l2_last[b])
                 active[b] = 0
                 changed = True
         if changed and active.any():
@@ -1595,11 +1615,7 @@ def solve_sources(grid, model, sources, frequency, strength=0, cycle='F', semico
         if dev.dtype != proto.dtype:
             raise ValueError(f"solve_sources: `handle` is {dev.dtype}, the frequency needs {proto.dtype}.")
     else:
-        parts = _exact_parts(grid, model, proto.smu0)
-        if parts is not None:
-            dev = DeviceMG.from_model(grid, parts, proto, device=device)
-        else:
-            dev = DeviceMG(grid, models.VolumeModel(grid, model, proto), proto.dtype, device=device)
+        dev = DeviceMG.open(grid, model, proto, device=device)
     try:
         dev.set_params(v0)
         if resident is not None and n > dev.nsys:
@@ -1655,12 +1671,7 @@ def solve_sources(grid, model, sources, frequency, strength=0, cycle='F', semico
     for var in vars_:
         if var.verb == 1 and var.exit_message != 'CONVERGED':
             var.cprint(f"* WARNING :: {var.exit_message}", 0)
-        infos.append({
-            'exit': int(var.exit_message != 'CONVERGED'), 'exit_message': var.exit_message, 'abs_error': var.l2,
-            'rel_error': var.l2 / var.l2_refe, 'ref_error': var.l2_refe, 'tol': var.tol, 'it_mg': var.it,
-            'it_ssl': var._ssl_it, 'time': var.runtime_at_cycle[-1], 'runtime_at_cycle': var.runtime_at_cycle,
-            'error_at_cycle': var.error_at_cycle, 'log': var.log_message,
-        })
+        infos.append(_info_dict(var))
     if rec is not None:
         return efields, infos, np.array(resp)
     return efields, infos
@@ -1673,11 +1684,11 @@ def multigrid(grid, model, sfield, efield, var, dev=None, **kwargs):
     """Level-0 loop of the multigrid solver (reference emg3d/solver.py:434-607).
 
     The coarse-level recursion (V/W/F scheduling, restriction, prolongation,
-    smoothing) of one cycle runs inside ``emg3d_mg_cycle`` on the device; this
-    function owns what the reference does once per cycle on the finest grid:
-    initial residual, optional initial smoothing, the end-of-cycle norm,
-    sc_dir/lr_dir rotation, logging and the termination tests.  ``efield`` is
-    updated in place.
+    smoothing) of one cycle runs inside ``emg3d_mg_cycle`` on the device; what
+    the reference does once per cycle on the finest grid -- initial residual,
+    optional initial smoothing, the end-of-cycle norm, sc_dir/lr_dir rotation,
+    logging and the termination tests -- is ``_batched_multigrid``, the loop of
+    ``solve_sources`` too, here with one system.  ``efield`` is updated in place.
     """
     if kwargs:
         raise TypeError("the coarse-level recursion lives on the device; `level`/`new_cycmax` "
@@ -1687,60 +1698,18 @@ def multigrid(grid, model, sfield, efield, var, dev=None, **kwargs):
         dev = DeviceMG(grid, model, sfield.dtype)
         dev.set_params(var)
         dev.set_sfield(sfield)
+    trace = var.verb > 4 and dev.nsys == 1
     try:
         if own or not var._dev_efield_current:
             dev.set_efield(efield)
-        dev.begin(var.sc_dir)
-        it = 0
-        l2_last = dev.residual_norm()
-        l2_stag = np.ones(var._maxcycle) * l2_last
-
-        # verb = 5 (solver.py:498-515): the norm after every smoothing call of every level -- the device reports them
-        tracing = var.verb > 4 and dev.nsys == 1
-        cm0 = 1 if var.clevel[var.sc_dir] == 0 else var.cycmax      # level 0's cycmax, fixed on entry (solver.py:480-485)
-        var.cprint("     it cycmax               error", 4)
-        var.cprint("      level [  dimension  ]            info\n", 4)
-        if tracing:
-            var.cprint(_print_gs_info(it, 0, cm0, grid.vnC, l2_last) + "initial error", 4)
-            dev.set_trace(True)
-
-        if var.nu_init > 0:
-            dev.smooth(var.nu_init, var.lr_dir)
-            if tracing:
-                var.cprint(_print_gs_info(it, 0, cm0, grid.vnC, dev.residual_norm()) + "initial smoothing", 4)
-
-        if var._first_cycle and var.verb > 3:
-            var._level_all = _first_cycle_levels(var)       # with the sc_dir of the first cycle
-
-        while True:
-            l2_prev = l2_last
-            l2_stag[(it - 1) % var._maxcycle] = l2_last
-
-            # the rotation of the directions (solver.py:597-600) is known before the cycle: the device handle prepares
-            # the next pair's hierarchy / factorisations / launch graph on the host while the device runs this cycle
-            nxt = (next(var.sc_cycle) if var.sc_cycle else var.sc_dir, next(var.lr_cycle) if var.lr_cycle else var.lr_dir)
-            ahead = PREPARE_AHEAD and nxt != (var.sc_dir, var.lr_dir) and it + 1 < var.maxit
-            l2_last = dev.cycle(var.sc_dir, var.lr_dir, nxt=nxt if ahead else None)
-            if tracing:
-                for rit, level, cm, kind, vnC, norm in dev.get_trace():
-                    var.cprint(_print_gs_info(it if level == 0 else rit, level, cm, vnC, norm) +
-                               ("coarsest level", "pre-smoothing", "post-smoothing")[kind], 4)
-
-            it += 1
-            var.it += 1
-            _print_cycle_info(var, l2_last, l2_prev)
-
-            var.sc_dir, var.lr_dir = nxt
-
-            if _terminate(var, l2_last, l2_stag[(it - 1) % var._maxcycle], it):
-                break
-        var.l2 = l2_last
+        if _batched_multigrid(dev, [var], [1], trace=trace)[0]:
+            raise _ConvergenceError         # a failing preconditioner: var.l2 and the field stay as they are
         if efield is not None:          # None: the caller picks the field up on the device
             dev.get_efield(np.asarray(efield))
     finally:
         if own:
             dev.close()
-        elif var.verb > 4 and dev.nsys == 1:
+        elif trace:
             dev.set_trace(False)
 
 
@@ -2488,7 +2457,6 @@ class MGParameters:
     def __post_init__(self):
         if self.ordering not in ORDERINGS:
             raise ValueError(f"`ordering` must be one of {list(ORDERINGS)}; provided: {self.ordering!r}.")
-        self._level_all = list()
         self._first_cycle = True
         self._dev_efield_current = False
         self.it = 0
@@ -2757,7 +2725,7 @@ def _print_cycle_info(var, l2_last, l2_prev):
         return
     info = "\n" if var.verb > 4 else ""
     if var._first_cycle:
-        info += _cycle_qc_figure(var._level_all or _first_cycle_levels(var))
+        info += _cycle_qc_figure(_first_cycle_levels(var))
         var._first_cycle = False
     info += f"   [{var.time.now}]   {l2_last/var.l2_refe:.3e}  "
     if var.sslsolver:
